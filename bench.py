@@ -8,7 +8,13 @@ one RCCL all-gather of the per-candidate costs and an identical stable ranking o
 scores its own strided 4096-candidate shard (candidates rank, rank + world, ...) of a
 (4096 x world)-candidate grid.
 
-Launch:  python bench.py [--gpus 1 --steps K --warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR
+also writes what the last timed step computed (DIR/<name>.npy).  Everything else the benchmark
+measures -- the kernel time from HIP events and the roofline fields built on it, the PCIe-inclusive
+rate of the host-buffer entry point, the CPU baselines and their comparison with the GPU costs --
+runs only with --full.
+
+Launch:  python bench.py [--gpus 1 --steps K --warmup W] [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 Prints one JSON line on rank 0.
 """
@@ -285,11 +291,25 @@ def cpu_model() -> str:
     return "unknown CPU"
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write the arrays of the last timed step as DIR/<name>.npy, float64 (the integer
+    status and iteration records are exact in float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a.detach().cpu().numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 20; 2 for the other workloads, whose step is a whole grid)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 3; 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: kernel time and roofline "
+                         "fields, the host-buffer entry point's rate, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (rank 0's shard)")
     ap.add_argument("--candidates", type=int, default=4096, help="candidates per GPU per step")
     ap.add_argument("--n2", type=int, default=30)
     ap.add_argument("--nu", type=int, default=5)
@@ -303,6 +323,10 @@ def main():
     args = ap.parse_args()
     if args.workload != "shell3x3":
         return other_workload(args)
+    if args.steps is None:
+        args.steps = 20
+    if args.warmup is None:
+        args.warmup = 3
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -359,7 +383,7 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        order = step(True)
+        order = step(args.full)  # HIP events around the kernel feed the roofline fields only
     torch.cuda.synchronize(dev)
     if dist:
         tdist.barrier()
@@ -369,34 +393,74 @@ def main():
         te = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         tdist.all_reduce(te, op=tdist.ReduceOp.MAX)
         elapsed = float(te.item())
-    kms = float(np.mean([a.elapsed_time(b) for a, b in kev]))  # ms per kernel launch
     status = out["status"].cpu().numpy()
-    iters = out["qp_iters"].cpu().numpy()
     nbad = int(np.count_nonzero(status))
-    I_as = float(iters.mean() / sc.nit)
     sims = world * C * args.steps
     value = sims / elapsed
-    fl = algorithmic_flops_per_sim(sc, args.n2, args.nu, I_as) * C
-    achieved = fl / (kms * 1e-3) / 1e12
-    from mpct.engine import kernel_instance
-
-    kernel_name = kernel_instance(sc)
-
-    # PCIe-inclusive rate of the host-buffer entry point (mpct_eval_batch: H2D candidates,
-    # kernel, D2H costs), after the timed region; reported beside `value`, never as `value`
-    from mpct.engine import eval_batch
-
-    hN2, hNu, hd, hl = sN2, sNu, sd, sl
-    eval_batch(sc, hN2, hNu, hd, hl, r[None], device=local)
-    t2 = time.perf_counter()
-    for _ in range(3):
-        eval_batch(sc, hN2, hNu, hd, hl, r[None], device=local)
-    host_rate = 3 * C / (time.perf_counter() - t2)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(out, order=order))
+    extra = {}
+    if args.full:
+        extra = full_fields(args, sc, out, kev, (N2, Nu, d, l), (sN2, sNu, sd, sl), r, local, world, rank)
 
     if rank != 0:
         if dist:
             tdist.destroy_process_group()
         return
+
+    line = {
+        "metric": "closed-loop GPC sims/sec (Shell 3x3, N2=30 Nu=5) over tuning grid",
+        "value": value,
+        "unit": "sims/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic candidate grid (numpy default_rng(20250307)) on the reference's Shell 3x3 "
+                "scenario (Shell3x3.m caso 2, L/R from Shell3x3_Tuning_25Jul2023_12_06.mat)",
+        "config": {"workload": "Shell3x3 GAM scoring: %d candidates/GPU x nit=500 closed loop + J1 + "
+                               "RCCL all-gather + ranking" % C,
+                   "candidates_per_gpu": C, "N2": args.n2, "Nu": args.nu, "nit": sc.nit,
+                   "parallelism": "dp%d" % world},
+        "full": args.full,
+        "status_nonzero": nbad,
+        "top_candidate": int(order[0].item()),
+    }
+    line.update(extra)
+    print(json.dumps(line), flush=True)
+    if dist:
+        tdist.destroy_process_group()
+
+
+def full_fields(args, sc, out, kev, grid, shard, r, local, world, rank):
+    """--full, Shell 3x3: the result line's fields beyond the headline figure.  Every rank times the
+    host-buffer entry point; rank 0 builds the roofline from the timed steps' HIP events and the
+    committed PMC / latency passes, and times the CPU baselines against the GPU's costs."""
+    from mpct.engine import eval_batch, kernel_instance
+
+    N2, Nu, d, l = grid
+    C = out["status"].numel()
+    kms = float(np.mean([a.elapsed_time(b) for a, b in kev]))  # ms per kernel launch
+    iters = out["qp_iters"].cpu().numpy()
+    I_as = float(iters.mean() / sc.nit)
+    fl = algorithmic_flops_per_sim(sc, args.n2, args.nu, I_as) * C
+    achieved = fl / (kms * 1e-3) / 1e12
+    kernel_name = kernel_instance(sc)
+
+    # PCIe-inclusive rate of the host-buffer entry point (mpct_eval_batch: H2D candidates,
+    # kernel, D2H costs), after the timed region; reported beside `value`, never as `value`
+    hN2, hNu, hd, hl = shard
+    eval_batch(sc, hN2, hNu, hd, hl, r[None], device=local)
+    t2 = time.perf_counter()
+    for _ in range(3):
+        eval_batch(sc, hN2, hNu, hd, hl, r[None], device=local)
+    host_rate = 3 * C / (time.perf_counter() - t2)
+    if rank != 0:
+        return {}
 
     traffic, traffic_source, fp64c = pmc_traffic(C, args.n2, args.nu)
     lat_frac, lat_source = latency_roofline()
@@ -437,24 +501,7 @@ def main():
     if not args.no_cpu_baseline and world == 1 and args.ref_seconds > 0:
         cpu_ref = reference_structured_baseline(N2, Nu, d, l, out["J1"].cpu().numpy(), args.ref_seconds)
 
-    line = {
-        "metric": "closed-loop GPC sims/sec (Shell 3x3, N2=30 Nu=5) over tuning grid",
-        "value": value,
-        "unit": "sims/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic candidate grid (numpy default_rng(20250307)) on the reference's Shell 3x3 "
-                "scenario (Shell3x3.m caso 2, L/R from Shell3x3_Tuning_25Jul2023_12_06.mat)",
-        "config": {"workload": "Shell3x3 GAM scoring: %d candidates/GPU x nit=500 closed loop + J1 + "
-                               "RCCL all-gather + ranking" % C,
-                   "candidates_per_gpu": C, "N2": args.n2, "Nu": args.nu, "nit": sc.nit,
-                   "parallelism": "dp%d" % world},
+    return {
         "roofline": {"bound": "fp64-valu", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
                      "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic, "traffic_source": traffic_source,
                      "kernel": kernel_name, "kernel_ms": kms,
@@ -470,12 +517,7 @@ def main():
         "cpu_baseline": cpu,
         "cpu_baseline_reference_structured": cpu_ref,
         "host_api_sims_per_s": host_rate,
-        "status_nonzero": nbad,
-        "top_candidate": int(order[0].item()),
     }
-    print(json.dumps(line), flush=True)
-    if dist:
-        tdist.destroy_process_group()
 
 
 def other_workload(args):
@@ -552,18 +594,19 @@ def other_workload(args):
     kev = []
 
     def step(record):
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        eval_batch_device(sc, t["N2"], t["Nu"], t["d"], t["l"], t["r"], out, v=tv, device=local, stream=stream)
-        e1.record(stream)
         if record:
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+        eval_batch_device(sc, t["N2"], t["Nu"], t["d"], t["l"], t["r"], out, v=tv, device=local, stream=stream)
+        if record:
+            e1.record(stream)
             kev.append((e0, e1))
         # worst case over the draws (config 4), all-gather, ranking (mpct.dist, gloo-tested)
         return gather_and_rank(out["J1"], C, nref, tw, Cg, owners=owners, distributed=dist)[1]
 
-    steps = args.steps if args.steps != 20 else 2   # a step is a whole grid here (seconds)
-    warm = args.warmup if args.warmup != 3 else 1
+    steps = 2 if args.steps is None else args.steps   # a step is a whole grid here (seconds)
+    warm = 1 if args.warmup is None else args.warmup
     for _ in range(warm):
         step(False)
     torch.cuda.synchronize(dev)
@@ -572,7 +615,7 @@ def other_workload(args):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(steps):
-        order = step(True)
+        order = step(args.full)  # HIP events around the evaluation feed the roofline fields only
     torch.cuda.synchronize(dev)
     if dist:
         tdist.barrier()
@@ -582,8 +625,35 @@ def other_workload(args):
         te = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         tdist.all_reduce(te, op=tdist.ReduceOp.MAX)
         elapsed = float(te.item())
-    kms = float(np.mean([a.elapsed_time(b) for a, b in kev]))
     st = out["status"].cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(out, order=order))
+    extra = {}
+    if args.full:
+        roof, kms = other_roofline(args, sc, out, kev, sN2, sNu, nref, world)
+        cpu = None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = other_cpu_baseline(args.workload, N2, Nu, d, l, refs, out["J1"].cpu().numpy(), st,
+                                     args.cpu_seconds)
+        extra = {"roofline": roof, "kernel_ms_rank0": kms, "cpu_baseline": cpu}
+    if rank == 0:
+        sims = (Cg * nref if scaling == "strong" else world * S) * steps
+        line = {"metric": metric, "value": sims / elapsed, "unit": "sims/s", "n_gpus": world, "steps": steps,
+                "warmup": warm, "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": scaling,
+                "vs_baseline": None, "dtype": "f64", "data": "synthetic candidate grid (seed 20250307) on the "
+                "reference's scenario", "config": dict(cfg, parallelism="dp%d" % world), "full": args.full,
+                "status_codes": {int(k): int(n) for k, n in zip(*np.unique(st, return_counts=True))},
+                "top_candidate": int(order[0].item())}
+        line.update(extra)
+        print(json.dumps(line), flush=True)
+    if dist:
+        tdist.destroy_process_group()
+
+
+def other_roofline(args, sc, out, kev, sN2, sNu, nref, world):
+    """--full, configs 3-5: (roofline fields, kernel ms) of this rank's launches from the timed steps'
+    HIP events, the DESIGN §7 flop models and the committed workload PMC pass."""
+    kms = float(np.mean([a.elapsed_time(b) for a, b in kev]))
     iters = out["qp_iters"].cpu().numpy()
     # algorithmic flops of the launch(es) over this rank's simulations (DESIGN §7 models)
     cN2 = np.repeat(sN2, nref).astype(np.int64)
@@ -623,22 +693,7 @@ def other_workload(args):
             "bound_note": "FP64 vector ALU + per-step latency; flops from the DESIGN §7 model with the "
                           "measured %s of every simulation; kernel_ms = HIP events around the whole "
                           "eval call (all class launches)" % ibound}
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = other_cpu_baseline(args.workload, N2, Nu, d, l, refs, out["J1"].cpu().numpy(), st,
-                                 args.cpu_seconds)
-    if rank == 0:
-        sims = (Cg * nref if scaling == "strong" else world * S) * steps
-        line = {"metric": metric, "value": sims / elapsed, "unit": "sims/s", "n_gpus": world, "steps": steps,
-                "warmup": warm, "ms_per_step": elapsed / steps * 1e3, "higher_is_better": True, "scaling": scaling,
-                "vs_baseline": None, "dtype": "f64", "data": "synthetic candidate grid (seed 20250307) on the "
-                "reference's scenario", "config": dict(cfg, parallelism="dp%d" % world),
-                "roofline": roof, "kernel_ms_rank0": kms, "cpu_baseline": cpu,
-                "status_codes": {int(k): int(n) for k, n in zip(*np.unique(st, return_counts=True))},
-                "top_candidate": int(order[0].item())}
-        print(json.dumps(line), flush=True)
-    if dist:
-        tdist.destroy_process_group()
+    return roof, kms
 
 
 if __name__ == "__main__":

@@ -28,14 +28,42 @@ def _cited(text):
     return out
 
 
+def _ignored(rel, pats):
+    """rel (a path below ROOT, '/'-separated) matches one of .gitignore's patterns"""
+    for p in pats:
+        q = p.rstrip("/")
+        if fnmatch.fnmatch(rel if "/" in q else os.path.basename(rel), q.lstrip("/")):
+            return True
+    return False
+
+
+def _tracked(sub=""):
+    """the committed files below ROOT/sub: `git ls-files` in a work tree; in an exported tree (no
+    .git, or one git refuses to read) every file there that .gitignore does not exclude"""
+    try:
+        if os.path.exists(os.path.join(ROOT, ".git")):
+            return subprocess.run(["git", "ls-files", sub or "."], cwd=ROOT, capture_output=True, text=True,
+                                  check=True).stdout.split()
+    except (OSError, subprocess.CalledProcessError):
+        pass
+    with open(os.path.join(ROOT, ".gitignore")) as f:
+        pats = [ln.strip() for ln in f if ln.strip() and not ln.startswith("#")] + [".git"]
+    out = []
+    for d, dirs, files in os.walk(os.path.join(ROOT, sub)):
+        rel = os.path.relpath(d, ROOT).replace(os.sep, "/")
+        rel = "" if rel == "." else rel + "/"
+        dirs[:] = [x for x in dirs if not _ignored(rel + x, pats)]
+        out += [rel + x for x in files if not _ignored(rel + x, pats)]
+    return out
+
+
 def _profiles():
-    return {os.path.basename(p) for p in subprocess.run(["git", "ls-files", "profiles"], cwd=ROOT, capture_output=True,
-                                                        text=True, check=True).stdout.split()}
+    return {os.path.basename(p) for p in _tracked("profiles")}
 
 
 def _sources():
     """tracked text files outside profiles/ (profiles/README.md included)"""
-    for f in subprocess.run(["git", "ls-files"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.split():
+    for f in _tracked():
         if f.startswith("profiles/") and f != "profiles/README.md":
             continue
         if f.endswith((".md", ".py", ".sh", ".m", ".c", ".h", ".hip", ".cpp")) and os.path.exists(os.path.join(ROOT, f)):

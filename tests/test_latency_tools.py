@@ -116,6 +116,26 @@ def test_bench_latency_frac_keyed_to_library(tmp_path, monkeypatch):
     assert frac == 0.3
 
 
+def test_bench_dump_outputs_writes_float64_arrays(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per output, float64, the integer records exact"""
+    import numpy as np
+    import torch
+
+    import bench
+
+    out = {"J1": torch.tensor([[1.5, float("nan")], [0.25, 3.0]], dtype=torch.float64),
+           "status": torch.tensor([0, 8], dtype=torch.int32),
+           "qp_iters": torch.tensor([2 ** 40 + 1, 7], dtype=torch.int64)}
+    d = tmp_path / "a" / "b"
+    bench.dump_outputs(str(d), out)
+    assert sorted(p.name for p in d.iterdir()) == ["J1.npy", "qp_iters.npy", "status.npy"]
+    for k, v in out.items():
+        a = np.load(d / (k + ".npy"))
+        assert a.dtype == np.float64 and a.shape == tuple(v.shape)
+        np.testing.assert_array_equal(a, v.numpy().astype(np.float64))
+    assert np.load(d / "qp_iters.npy")[0] == 2 ** 40 + 1
+
+
 def test_bench_workload_pmc_keyed_to_library(tmp_path, monkeypatch):
     """the other §8d lines' traffic / counter rate come from the PMC pass over bench.py
     (tools/pmc_workloads.sh) only when it profiled the loaded library"""

@@ -13,11 +13,11 @@ timeout -k 10 540 python3 -u -m pytest tests -m gpu -x -v --timeout 120 --timeou
   > "$O/pytest_gpu.log" 2>&1 || { tail -40 "$O/pytest_gpu.log"; exit 1; }
 tail -2 "$O/pytest_gpu.log"
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { tail -20 "$O/smoke.log"; exit 1; }
-timeout -k 10 300 python3 bench.py > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
+timeout -k 10 300 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err" || { tail -20 "$O/bench.err"; exit 1; }
 cat "$O/bench.json"
 export TMPDIR=/tmp
 cd /tmp
-BENCH=(python3 "$R/bench.py" --steps 5 --warmup 1 --no-cpu-baseline)
+BENCH=(python3 "$R/bench.py" --full --steps 5 --warmup 1 --no-cpu-baseline)
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kt" -o kt -- "${BENCH[@]}" > "$O/kt.log" 2>&1
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -o fetch -- "${BENCH[@]}" > "$O/fetch.log" 2>&1
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/write" -o write -- "${BENCH[@]}" > "$O/write.log" 2>&1
