@@ -5,7 +5,7 @@
 // DTC_GPC_WW.m is the unconstrained loop: deltaU = Km * (Ref - yf) (:149) with Km the first-move rows
 // of K = (H'QH + W) \ H'Q (:98-105).  So a scenario in DTC mode whose move bounds are all infinite
 // (what DTC_GPC_WW.m restates) needs, per step, only the nu first-move rows of the gain: no QP, no
-// R^-1, no factor state.  The host marks such scenarios `small_dtc` (mpct_host.cpp dtc_small_plant):
+// R^-1, no factor state.  The host marks such scenarios `small_dtc` (scenario_tables.h dtc_small_plant):
 // DTC mode, my <= 2 outputs, nu <= 2 MVs, nu + nq <= 4 plant inputs (MVs and plant-only
 // disturbances, no measured disturbances), every plant variant's, Pz's and Gz's entry <= 4 terms,
 // filters Fr_i of <= 4 taps, y difference state <= 4 per output, past-control registers <= 8 per

@@ -3,7 +3,7 @@
 //
 // Same simulation as gpc_closed_loop_kernel (closedloop_toolbox.m:36-50 restated as the
 // toolbox-equivalent GPC of DESIGN.md §2, costs GAM_fun.m:110-111 J1 and VNS2.m:172-177 j22), for
-// scenarios the host marks `small` (mpct_host.cpp small_plant): my <= 4 outputs, nu <= 3 MVs, no
+// scenarios the host marks `small` (scenario_tables.h small_plant): my <= 4 outputs, nu <= 3 MVs, no
 // measured or plant-only disturbances, one plant, GPC (not DTC) mode, y difference state <= 12
 // entries (<= 4 per output), past-control registers <= 8 per MV, <= 4 plant terms per entry, and
 // cost-only batches (no open-loop leg, no trajectories).  The Shell 3x3 metric (BASELINE config 2)

@@ -1,4 +1,4 @@
-// mpct_dev.h — device-side scenario layout shared by the host precompute (mpct_host.cpp) and
+// mpct_dev.h — device-side scenario layout shared by the host precompute (scenario_tables.h) and
 // the closed-loop kernel (gpc_kernel.hip).  Plain POD passed by value as a kernel argument.
 #pragma once
 #include <stdint.h>
@@ -68,7 +68,7 @@ struct DevScenario {
   int ne;                   // plant entries my*nin (nin = plant input columns incl. disturbances)
   int pl_maxb, pl_maxa;     // longest plant numerator (incl. delay) / denominator
   int regpath;              // every per-lane history / coefficient set fits the kReg* caps
-  // small plants (gpc_small_kernel eligibility, mpct_host.cpp small_plant) and its lane tables:
+  // small plants (gpc_small_kernel eligibility, scenario_tables.h small_plant) and its lane tables:
   // plant term of lane L = 16 k + 4 i + j (coefficient, history ring offset in the kernel's history
   // region, delay, ring mask) and the state column -> A column map
   int small;
@@ -78,7 +78,7 @@ struct DevScenario {
   const int* sm_hc;       // [64]
   const int* sm_hmask;    // [64]
   const int* sm_acol;     // [nx]
-  // DTC-GPC small plants (dtc_small_kernel, dtc_small.hip; mpct_host.cpp dtc_small_plant): the sm_*
+  // DTC-GPC small plants (dtc_small_kernel, dtc_small.hip; scenario_tables.h dtc_small_plant): the sm_*
   // lane tables are [nvar][64] (plant variant k % nvar) and the filters Fr_i [my][8] (fb 0..3, fa 0..3)
   int small_dtc;
   const double* sm_fr;

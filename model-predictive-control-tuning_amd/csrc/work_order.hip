@@ -92,7 +92,7 @@ __global__ void order_keys(int kind, long long C, int my, int nu, const int* __r
 // went 57 -> 45 us with the register Gauss-Jordan and -> 26 us with the Gram tables,
 // profiles/r05_key_stages.txt):
 //   * nu Nu <= 16, my <= 4 (the metric): H = sum_o q_o G_o'G_o + Lambda from the scenario's Gram
-//     tables (mpct_host.cpp gram_tables), then Gauss-Jordan in registers (gj16).  Correlating the
+//     tables (scenario_tables.h gram_tables), then Gauss-Jordan in registers (gj16).  Correlating the
 //     step table in LDS per workgroup took 21 of the 45 us, the LDS Cholesky and solves 21 of 57;
 //   * larger QPs: H by lanes over its entries (step-table correlations in LDS), Cholesky and the
 //     my solves in LDS (the Gauss-Jordan where the tables were too large to build).
@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(64) order_keys_gpc(const DevScenario sc, long 
   double* sBn = sD + kWave * my;     // b_n per MV (read up front, off the jump passes' chain)
   double* sLw = sBn + nu;            // the move weight of each MV (H's diagonal)
   int* sN1 = reinterpret_cast<int*>(sLw + nu);
-  // H and the right-hand sides from the scenario's Gram tables (mpct_host.cpp gram_tables) when
+  // H and the right-hand sides from the scenario's Gram tables (scenario_tables.h gram_tables) when
   // they cover this QP size; else correlated here from the step table
   const bool tab = sc.gram != nullptr && M <= kGramM && my <= 4;
   if (!tab)
