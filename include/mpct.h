@@ -21,6 +21,9 @@
  *     of a call is complete when mpct_eval_batch returns.  A scenario keeps one context per GPU
  *     it has been evaluated on (table copies, sort buffers, a library-owned stream); the
  *     host-pointer entries synchronise that stream only, never the whole device.
+ *   - robust scoring (mpct_robust_result, mpct_eval_robust, mpct_eval_robust_device,
+ *     mpct_robust_instance) is part of ABI 7: new exports and one new struct, added without a
+ *     version change because no existing struct, export or behaviour changes.
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -327,6 +330,68 @@ int64_t mpct_lds_bytes(const mpct_scenario* s, int32_t N2, int32_t Nu);
 /* The same for the instance a call with these options launches (opts NULL = costs only: the
  * GAM_fun.m:81 call, which the tuning-grid benchmark times). */
 int64_t mpct_lds_bytes_opts(const mpct_scenario* s, const mpct_opts* opts, int32_t N2, int32_t Nu);
+
+/* ---- Robust scoring over plant draws ----------------------
+ * C candidates x D = nref draws, reduced to one record per CANDIDATE on the device.  Simulation
+ * (c, k) is candidate c on reference set k and plant variant k % nplant, exactly as in
+ * mpct_eval_batch; J(c,k) = sum_i J1_i(c,k) is the draw's total cost.
+ *
+ * A draw FAILS when its status is non-zero, or J is not finite, or J > j_bound; every other draw
+ * SURVIVES.  j_bound = 0 means 1e100; +INFINITY is allowed (then only the status and finiteness
+ * decide); a negative or NaN j_bound is MPCT_EINVAL.  A destabilised draw that overflows neither
+ * the status nor double precision (a loop at 1e139 keeps status 0) is thus a failed draw of its
+ * candidate, never a cost.  A skipped or bad-horizon candidate (MPCT_ST_SKIPPED / _BADHORIZON) has
+ * no failed draw: its record carries that status bit, NaN statistics, n_failed = 0, worst_draw = -1.
+ *
+ * Outputs per candidate; any pointer may be NULL (not all of them):
+ *   mean[C*my]     mean over the surviving draws of J1_i; NaN if none survives
+ *   worst[C*my]    max over the surviving draws of J1_i; NaN if none survives
+ *   n_failed[C]    number of failed draws
+ *   worst_draw[C]  the surviving draw with the largest total J, lowest index on ties; -1 if none
+ *   status[C]      OR of the draws' status bits (failed draws included)
+ *   J1[C*D*my]     optional: the per-simulation costs in mpct_eval_batch's layout, from the same launch
+ *
+ * Summation order (fixed): per output i one accumulator over the draws k = 0, 1, .., D-1 in that
+ * order, divided by the number of survivors; J(c,k) is summed over i = 0, 1, .., my-1.  A repeated
+ * call is bitwise identical and a candidate's record does not depend on its place in the batch.
+ * With a finite j_bound no statistic can overflow while D * j_bound < 1.8e308 (the default bound:
+ * any D), since every surviving term is <= j_bound.  With j_bound = +INFINITY a finite J survives
+ * whatever its size and the mean's sum may round to +INFINITY (never NaN: the terms are >= 0).
+ *
+ * Scenarios the cost-only dtc_small_kernel serves (unconstrained DTC, small plant) with
+ * nu * nu_max <= 32 and D <= 128 run the fused dtc_robust_kernel: one workgroup per candidate
+ * builds the gain once and walks the draws.  Every other scenario, and D > 128 (the fused kernel's
+ * LDS record array), runs its per-simulation instance unchanged and then robust_reduce_kernel; both
+ * paths share one reduction, so their records are bitwise equal for equal per-simulation costs. */
+typedef struct mpct_robust_result {
+  double* mean;
+  double* worst;
+  int32_t* n_failed;
+  int32_t* worst_draw;
+  int32_t* status;
+  double* J1;
+} mpct_robust_result;
+
+/* Host pointers.  Arguments as mpct_eval_batch; the call is cost-only: opts->open_loop or
+ * opts->want_traj set is MPCT_EINVAL, as are nref < 1, a bad j_bound and an `out` whose pointers
+ * are all NULL.  Without a device: MPCT_EDEVICE with a message, like mpct_eval_batch. */
+int32_t mpct_eval_robust(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
+                         const double* lambda, int32_t nref, const double* r, const double* v, double j_bound,
+                         const mpct_opts* opts, mpct_robust_result* out);
+
+/* Same, all pointers DEVICE pointers, enqueued on `stream` (NULL = default stream) and NOT
+ * synchronised: the contract of mpct_eval_batch_device, heaviest-first dispatch of batches of 256
+ * or more candidates included.  The per-simulation scratch and candidate lists belong to the
+ * scenario; a later robust call on another stream waits for the one before it. */
+int32_t mpct_eval_robust_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                const double* delta, const double* lambda, int32_t nref, const double* r,
+                                const double* v, double j_bound, const mpct_opts* opts, mpct_robust_result* out,
+                                void* stream);
+
+/* Name of what a robust call launches for this scenario (at a draw count the fused kernel holds),
+ * e.g. "dtc_robust_kernel<16> + dtc_robust_kernel<32>" or "gpc_small_kernel + robust_reduce_kernel".
+ * Same buffer contract as mpct_kernel_instance; no device needed. */
+int32_t mpct_robust_instance(const mpct_scenario* s, const mpct_opts* opts, char* buf, int32_t cap);
 
 #ifdef __cplusplus
 }

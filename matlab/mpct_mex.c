@@ -13,6 +13,12 @@
  *   [J1,j21,j22,Jnu,status,iters,y,u,ys,uopt] = mpct_mex('eval', h, N2, Nu, delta, lambda, r, v, opts)
  *   [...] = mpct_mex('eval_multi', h, devices, N2, Nu, delta, lambda, r, v, opts)
  *   name = mpct_mex('instance', h, opts)             kernel instance an eval launches
+ *   R = mpct_mex('eval_robust', h, N2, Nu, delta, lambda, r, v, j_bound)
+ *                                                    per-candidate statistics over the D pages of r
+ *                                                    (mpct_eval_robust): struct with mean, worst (C x my),
+ *                                                    n_failed, worst_draw, status (C x 1; worst_draw is the
+ *                                                    library's 0-based draw, -1: none) and J1 (S x my);
+ *                                                    j_bound optional (0: 1e100)
  *   mpct_mex('destroy', h)
  *
  * MATLAB layouts (column-major, what the callers already hold):
@@ -414,6 +420,52 @@ static void cmd_eval(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[],
   }
 }
 
+/* R = mpct_mex('eval_robust', h, N2, Nu, delta, lambda, r [, v, j_bound]) */
+static void cmd_eval_robust(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 7) mexErrMsgIdAndTxt("mpct:arg", "usage: R = mpct_mex('eval_robust', h, N2, Nu, delta, lambda, r [, v, j_bound])");
+  mpct_scenario* s = handle(prhs[1]);
+  int my, nu, nv, nit;
+  dims_of(s, &my, &nu, &nv, &nit);
+  const long C = (long)mxGetNumberOfElements(prhs[2]);
+  int32_t* N2 = ints(prhs[2], -1, "N2");
+  int32_t* Nu = ints(prhs[3], C, "Nu");
+  double* delta = rows_of(prhs[4], C, my, "delta");
+  double* lambda = rows_of(prhs[5], C, nu, "lambda");
+  int nref = 0;
+  double* r = signals(prhs[6], my, nit, &nref, "r");
+  const mxArray* va = nrhs > 7 ? prhs[7] : NULL;
+  double* v = NULL;
+  if (nv > 0) {
+    if (!va || mxIsEmpty(va)) mexErrMsgIdAndTxt("mpct:arg", "'v' must be %d x %d (x nref)", nv, nit);
+    v = signals(va, nv, nit, &nref, "v");
+  } else if (va && !mxIsEmpty(va)) {
+    mexErrMsgIdAndTxt("mpct:arg", "'v' given but the scenario has no disturbance inputs");
+  }
+  const double j_bound = (nrhs > 8 && !mxIsEmpty(prhs[8])) ? scalar(prhs[8], "j_bound") : 0.0;
+  const long S = C * nref;
+  mpct_robust_result res;
+  res.mean = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
+  res.worst = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
+  res.n_failed = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  res.worst_draw = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  res.status = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  res.J1 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
+  mpct_opts o = read_opts(NULL);
+  if (mpct_eval_robust(s, C, N2, Nu, delta, lambda, nref, r, v, j_bound, &o, &res) != MPCT_OK) lib_error("mpct:eval_robust");
+  const char* names[6] = {"mean", "worst", "n_failed", "worst_draw", "status", "J1"};
+  mxArray* R = mxCreateStructMatrix(1, 1, 6, names);
+  mxSetField(R, 0, "mean", out_rows(res.mean, C, my));
+  mxSetField(R, 0, "worst", out_rows(res.worst, C, my));
+  const int32_t* iv[3] = {res.n_failed, res.worst_draw, res.status};
+  for (int f = 0; f < 3; ++f) {
+    mxArray* a = mxCreateDoubleMatrix((mwSize)C, 1, mxREAL);
+    for (long k = 0; k < C; ++k) mxGetPr(a)[k] = iv[f][k];
+    mxSetField(R, 0, names[2 + f], a);
+  }
+  mxSetField(R, 0, "J1", out_rows(res.J1, S, my));
+  plhs[0] = R;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (!g_atexit) {
     mexAtExit(destroy_all);
@@ -434,6 +486,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_eval(nlhs, plhs, nrhs, prhs, 0);
   } else if (!strcmp(cmd, "eval_multi")) {
     cmd_eval(nlhs, plhs, nrhs, prhs, 1);
+  } else if (!strcmp(cmd, "eval_robust")) {
+    cmd_eval_robust(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "instance")) {
     if (nrhs < 2) mexErrMsgIdAndTxt("mpct:arg", "usage: name = mpct_mex('instance', h [, opts])");
     mpct_scenario* s = handle(prhs[1]);

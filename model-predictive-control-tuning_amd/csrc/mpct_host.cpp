@@ -13,6 +13,7 @@
 #include "scenario_tables.h"
 #include "launch_fan.h"
 #include "work_order.h"
+#include "dtc_robust.h"
 
 namespace mpct {
 // defined in gpc_kernel_launch.hip
@@ -54,6 +55,14 @@ struct DevCtx {
   hipStream_t stream = nullptr;
   LaunchFan fan;    // auxiliary streams of the class launches (band / NMPC kernels)
   WorkOrder order;  // dispatch-order sort buffers (GPC and NMPC kernels)
+  // robust scoring, device-pointer entry (grow only): per-simulation J1 / status of the generic
+  // path, candidate lists of the fused one.  robust_used is recorded after the launches that use
+  // the buffer; the next robust call's stream waits for it before rewriting
+  void* drobust = nullptr;
+  size_t drobust_bytes = 0;
+  hipEvent_t robust_used = nullptr;
+  bool robust_pending = false;
+  int ncu = 0;  // compute units (grid of the fused robust kernel)
 };
 
 static thread_local std::string g_err;
@@ -100,6 +109,9 @@ static void ctx_release(DevCtx* c) {
   if (c->dtab) (void)hipFree(c->dtab);
   if (c->dscratch) (void)hipFree(c->dscratch);
   if (c->dsig) (void)hipFree(c->dsig);
+  if (c->robust_pending) (void)hipEventSynchronize(c->robust_used);
+  if (c->drobust) (void)hipFree(c->drobust);
+  if (c->robust_used) (void)hipEventDestroy(c->robust_used);
   order_release(c->order);
   c->fan.release();
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -570,16 +582,215 @@ extern "C" int32_t mpct_eval_batch_multi(mpct_scenario* s, int32_t ndev, const i
   return MPCT_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// robust scoring over plant draws (include/mpct.h)
+
+// the argument checks of the robust entries, on top of check_args
+static int check_robust(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* N2, const int32_t* Nu,
+                        const double* delta, const double* lambda, const double* r, const double* v, double j_bound,
+                        const mpct_opts* opts, const mpct_robust_result* out) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (opts && (opts->open_loop || opts->want_traj))
+    return fail(MPCT_EINVAL, "robust scoring is cost-only: open_loop and want_traj must be 0");
+  if (nref < 1) return fail(MPCT_EINVAL, "nref < 1: robust scoring needs at least one draw");
+  if (!(j_bound >= 0.0)) return fail(MPCT_EINVAL, "j_bound must be >= 0 (0 = 1e100, +inf allowed), not negative or NaN");
+  if (!out) return fail(MPCT_EINVAL, "null result");
+  if (!out->mean && !out->worst && !out->n_failed && !out->worst_draw && !out->status && !out->J1)
+    return fail(MPCT_EINVAL, "every output pointer of the robust result is NULL");
+  const mpct_result any{};
+  return check_args(s, C, nref, N2, Nu, delta, lambda, r, v, opts, &any);
+}
+
+// the scenario's robust scratch on this context, at least `bytes`; orders `stream` after the last
+// robust launches that used it
+static int robust_scratch(DevCtx* cx, size_t bytes, hipStream_t stream, char** out) {
+  if (!cx->robust_used && hipEventCreateWithFlags(&cx->robust_used, hipEventDisableTiming) != hipSuccess)
+    return fail(MPCT_EDEVICE, "hipEventCreate failed");
+  if (bytes > cx->drobust_bytes) {
+    if (cx->robust_pending) (void)hipEventSynchronize(cx->robust_used);
+    cx->robust_pending = false;
+    if (cx->drobust) (void)hipFree(cx->drobust);
+    cx->drobust = nullptr;
+    cx->drobust_bytes = 0;
+    if (hipMalloc(&cx->drobust, bytes) != hipSuccess) return fail(MPCT_ENOMEM, "hipMalloc(robust scratch) failed");
+    cx->drobust_bytes = bytes;
+  }
+  if (cx->robust_pending && hipStreamWaitEvent(stream, cx->robust_used, 0) != hipSuccess)
+    return fail(MPCT_EDEVICE, "hipStreamWaitEvent failed");
+  *out = static_cast<char*>(cx->drobust);
+  return MPCT_OK;
+}
+
+// enqueue one robust batch with device pointers on `stream` (ctx's device is current)
+static int launch_robust(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2, const int32_t* Nu,
+                         const double* delta, const double* lambda, int32_t nref, const double* r, const double* v,
+                         double j_bound, const mpct_opts* opts, const mpct_robust_result* out, hipStream_t stream) {
+  if (C == 0) return MPCT_OK;
+  const double bound = j_bound == 0.0 ? kRobustDefaultBound : j_bound;
+  const RobustOut ro{out->mean, out->worst, out->n_failed, out->worst_draw, out->status};
+  const int64_t S = C * nref;
+  std::string err;
+  int rc;
+  char* scr = nullptr;
+  if (dtc_robust_eligible(cx->ds, nref)) {
+    if (cx->ncu == 0 &&
+        (hipDeviceGetAttribute(&cx->ncu, hipDeviceAttributeMultiprocessorCount, cx->dev) != hipSuccess || cx->ncu < 1))
+      return fail(MPCT_EDEVICE, "hipDeviceGetAttribute(MultiprocessorCount) failed");
+    rc = robust_scratch(cx, sizeof(int) * (size_t)(2 * C + 2), stream, &scr);
+    if (rc) return rc;
+    const int* perm = nullptr;
+    rc = order_candidates(kOrderGpc, s->my, s->nu, C, N2, Nu, delta, lambda, cx->order, &perm, stream, &err, &cx->ds,
+                          nref, r);
+    if (rc == 0)
+      rc = launch_dtc_robust(cx->ds, C, nref, N2, Nu, delta, lambda, r, v, perm, reinterpret_cast<int*>(scr), bound, ro,
+                             out->J1, cx->ncu, &cx->fan, stream, &err);
+    if (perm) order_mark_used(cx->order, stream);
+    if (rc) return fail(rc, err);
+  } else {
+    // the per-simulation instance, unchanged, into the caller's J1 or the scenario's scratch
+    const size_t jb = out->J1 ? 0 : ((size_t)S * s->my * 8 + 255) & ~(size_t)255;
+    rc = robust_scratch(cx, jb + (size_t)S * 4, stream, &scr);
+    if (rc) return rc;
+    mpct_result per{};
+    per.J1 = out->J1 ? out->J1 : reinterpret_cast<double*>(scr);
+    per.status = reinterpret_cast<int32_t*>(scr + jb);
+    rc = launch_batch(s, cx, C, N2, Nu, delta, lambda, nref, r, v, opts, &per, stream);
+    if (rc) return rc;
+    rc = launch_robust_reduce(C, nref, s->my, bound, per.J1, per.status, ro, stream, &err);
+    if (rc) return fail(rc, err);
+  }
+  cx->robust_pending = hipEventRecord(cx->robust_used, stream) == hipSuccess;
+  return MPCT_OK;
+}
+
+extern "C" int32_t mpct_eval_robust_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                           const double* delta, const double* lambda, int32_t nref,
+                                           const double* r, const double* v, double j_bound, const mpct_opts* opts,
+                                           mpct_robust_result* out, void* stream) {
+  int rc = check_robust(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, out);
+  if (rc) return rc;
+  DevCtx* cx = nullptr;
+  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  if (rc) return rc;
+  return launch_robust(s, cx, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, out, static_cast<hipStream_t>(stream));
+}
+
+// Test hook, deliberately not declared in include/mpct.h: the generic path's reduction alone, on
+// per-simulation records the caller supplies (device pointers, enqueued on `stream`).  The tests
+// reduce the fused kernel's own J1 sample with it to pin that both paths share one robust_reduce.
+extern "C" int32_t mpct_internal_robust_reduce(int64_t C, int32_t D, int32_t my, double j_bound, const double* J1,
+                                               const int32_t* status, const mpct_robust_result* out, void* stream) {
+  if (C < 0 || D < 1 || my < 1 || !J1 || !status || !out || !(j_bound >= 0.0)) return fail(MPCT_EINVAL, "bad argument");
+  const RobustOut ro{out->mean, out->worst, out->n_failed, out->worst_draw, out->status};
+  std::string err;
+  const int rc = launch_robust_reduce(C, D, my, j_bound == 0.0 ? kRobustDefaultBound : j_bound, J1, status, ro,
+                                      static_cast<hipStream_t>(stream), &err);
+  return rc ? fail(rc, err) : MPCT_OK;
+}
+
+extern "C" int32_t mpct_eval_robust(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                    const double* delta, const double* lambda, int32_t nref, const double* r,
+                                    const double* v, double j_bound, const mpct_opts* opts, mpct_robust_result* out) {
+  int rc = check_robust(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, out);
+  if (rc) return rc;
+  DevCtx* cx = nullptr;
+  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;
+  // host buffers in, host buffers out on the context's own stream (as eval_host): one scratch blob
+  const int my = s->my, nu = s->nu, nit = s->nit, nv = s->nd + s->nq;
+  const int64_t S = C * nref;
+  hipStream_t st = cx->stream;
+  size_t off = 0;
+  auto slot = [&](size_t bytes) {
+    size_t o = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return o;
+  };
+  const size_t rb = (size_t)nref * my * nit * 8, vb = (size_t)nref * nv * nit * 8;
+  const size_t o_N2 = slot(C * 4), o_Nu = slot(C * 4), o_d = slot(C * my * 8), o_l = slot(C * nu * 8);
+  const size_t o_r = slot(rb), o_v = slot(vb);
+  const size_t o_mean = slot(C * my * 8), o_worst = slot(C * my * 8), o_nf = slot(C * 4), o_wd = slot(C * 4);
+  const size_t o_st = slot(C * 4), o_J1 = out->J1 ? slot(S * my * 8) : 0;
+  if (off > cx->dscratch_bytes) {
+    if (cx->dscratch) {
+      (void)hipStreamSynchronize(st);
+      (void)hipFree(cx->dscratch);
+    }
+    cx->dscratch = nullptr;
+    cx->dscratch_bytes = 0;
+    if (hipMalloc(&cx->dscratch, off) != hipSuccess) return fail(MPCT_ENOMEM, "hipMalloc(scratch) failed");
+    cx->dscratch_bytes = off;
+  }
+  char* b = static_cast<char*>(cx->dscratch);
+  auto h2d = [&](size_t o, const void* p, size_t bytes) {
+    return bytes == 0 || hipMemcpyAsync(b + o, p, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
+  };
+  if (!h2d(o_N2, N2, C * 4) || !h2d(o_Nu, Nu, C * 4) || !h2d(o_d, delta, C * my * 8) || !h2d(o_l, lambda, C * nu * 8) ||
+      !h2d(o_r, r, rb) || !h2d(o_v, v, vb)) {
+    (void)hipStreamSynchronize(st);
+    return fail(MPCT_EDEVICE, "hipMemcpyAsync(inputs) failed");
+  }
+  mpct_robust_result dres{};
+  dres.mean = reinterpret_cast<double*>(b + o_mean);
+  dres.worst = reinterpret_cast<double*>(b + o_worst);
+  dres.n_failed = reinterpret_cast<int32_t*>(b + o_nf);
+  dres.worst_draw = reinterpret_cast<int32_t*>(b + o_wd);
+  dres.status = reinterpret_cast<int32_t*>(b + o_st);
+  dres.J1 = out->J1 ? reinterpret_cast<double*>(b + o_J1) : nullptr;
+  rc = launch_robust(s, cx, C, reinterpret_cast<const int32_t*>(b + o_N2), reinterpret_cast<const int32_t*>(b + o_Nu),
+                     reinterpret_cast<const double*>(b + o_d), reinterpret_cast<const double*>(b + o_l), nref,
+                     reinterpret_cast<const double*>(b + o_r), nv > 0 ? reinterpret_cast<const double*>(b + o_v) : nullptr,
+                     j_bound, opts, &dres, st);
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  auto d2h = [&](void* dst, const void* src, size_t bytes) {
+    return !dst || bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
+  };
+  const bool ok = d2h(out->mean, dres.mean, C * my * 8) && d2h(out->worst, dres.worst, C * my * 8) &&
+                  d2h(out->n_failed, dres.n_failed, C * 4) && d2h(out->worst_draw, dres.worst_draw, C * 4) &&
+                  d2h(out->status, dres.status, C * 4) && d2h(out->J1, dres.J1, S * my * 8);
+  const hipError_t se = hipStreamSynchronize(st);
+  if (se != hipSuccess) return fail(MPCT_EDEVICE, std::string("kernel execution failed: ") + hipGetErrorString(se));
+  if (!ok) return fail(MPCT_EDEVICE, "hipMemcpyAsync(results) failed");
+  return MPCT_OK;
+}
+
+static int32_t copy_name(const std::string& nm, char* buf, int32_t cap) {
+  if (buf && cap > 0) {
+    const size_t n = std::min<size_t>(nm.size(), (size_t)cap - 1);
+    std::memcpy(buf, nm.data(), n);
+    buf[n] = '\0';
+  }
+  return (int32_t)nm.size();
+}
+
+static std::string per_simulation_instance(const mpct_scenario* s, bool ext) {
+  if (s->nmpc) return "nmpc_closed_loop_kernel (QP-size x LDS-tier class launches)";
+  if (s->mdband) return "mdband_closed_loop_kernel (QP-size x LDS-tier class launches)";
+  return closed_loop_instance(dev_scenario(s), s->nu * s->numax, ext);
+}
+
+extern "C" int32_t mpct_robust_instance(const mpct_scenario* s, const mpct_opts* opts, char* buf, int32_t cap) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (opts && (opts->open_loop || opts->want_traj))
+    return fail(MPCT_EINVAL, "robust scoring is cost-only: open_loop and want_traj must be 0");
+  std::string nm;
+  if (!s->nmpc && !s->mdband && dtc_robust_eligible(dev_scenario(s), 1)) {
+    nm = "dtc_robust_kernel<16>";
+    if (s->nu * s->numax > 16) nm += " + dtc_robust_kernel<32>";
+  } else {
+    nm = per_simulation_instance(s, false) + " + robust_reduce_kernel";
+  }
+  return copy_name(nm, buf, cap);
+}
+
 extern "C" int32_t mpct_kernel_instance(const mpct_scenario* s, const mpct_opts* opts, char* buf, int32_t cap) {
   if (!s) return fail(MPCT_EINVAL, "null scenario");
-  std::string nm;
   const bool ext = opts && (opts->open_loop || opts->want_traj);
-  if (s->nmpc)
-    nm = "nmpc_closed_loop_kernel (QP-size x LDS-tier class launches)";
-  else if (s->mdband)
-    nm = "mdband_closed_loop_kernel (QP-size x LDS-tier class launches)";
-  else
-    nm = closed_loop_instance(dev_scenario(s), s->nu * s->numax, ext);
+  const std::string nm = per_simulation_instance(s, ext);
   if (buf && cap > 0) {
     const size_t n = std::min<size_t>(nm.size(), (size_t)cap - 1);
     std::memcpy(buf, nm.data(), n);

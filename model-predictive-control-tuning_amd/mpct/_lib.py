@@ -81,11 +81,16 @@ class MpctResult(C.Structure):
                 ("y", c_double_p), ("u", c_double_p), ("ys", c_double_p), ("uopt", c_double_p)]
 
 
+class MpctRobustResult(C.Structure):
+    _fields_ = [("mean", c_double_p), ("worst", c_double_p), ("n_failed", c_int32_p), ("worst_draw", c_int32_p),
+                ("status", c_int32_p), ("J1", c_double_p)]
+
+
 EXPORTS = [
     "mpct_abi_version", "mpct_last_error", "mpct_scenario_create", "mpct_scenario_destroy",
     "mpct_scenario_table", "mpct_eval_batch", "mpct_eval_batch_device", "mpct_lds_bytes", "mpct_lds_bytes_opts",
     "mpct_nmpc_scenario_create", "mpct_eval_batch_multi", "mpct_shard_candidates", "mpct_kernel_instance",
-    "mpct_rank_device",
+    "mpct_rank_device", "mpct_eval_robust", "mpct_eval_robust_device", "mpct_robust_instance",
 ]
 
 ABI_VERSION = 7
@@ -149,6 +154,17 @@ def load():
     lib.mpct_kernel_instance.restype = C.c_int32
     lib.mpct_rank_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mpct_rank_device.restype = C.c_int32
+    robust_args = batch_args[:9] + [C.c_double, C.POINTER(MpctOpts), C.POINTER(MpctRobustResult)]
+    lib.mpct_eval_robust.argtypes = robust_args
+    lib.mpct_eval_robust.restype = C.c_int32
+    lib.mpct_eval_robust_device.argtypes = robust_args + [C.c_void_p]
+    lib.mpct_eval_robust_device.restype = C.c_int32
+    lib.mpct_robust_instance.argtypes = [C.c_void_p, C.POINTER(MpctOpts), C.c_char_p, C.c_int32]
+    lib.mpct_robust_instance.restype = C.c_int32
+    # the reduction of the generic robust path alone: a test hook, not part of include/mpct.h
+    lib.mpct_internal_robust_reduce.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                                C.POINTER(MpctRobustResult), C.c_void_p]
+    lib.mpct_internal_robust_reduce.restype = C.c_int32
     if lib.mpct_abi_version() != ABI_VERSION:
         raise ImportError("libmpct ABI version mismatch")
     _lib = lib

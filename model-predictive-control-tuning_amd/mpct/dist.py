@@ -246,7 +246,12 @@ def gather_and_rank(J: torch.Tensor, n: int, nref: int, weights: torch.Tensor, C
     """The data-parallel epilogue of one scoring step: the rank's simulation records J [n*nref, K]
     -> per-candidate records (worst_over_draws) -> one all-gather (gather_costs, owners as
     plan_shards returns them) -> the ranking every rank computes (rank_candidates) over the C real
-    candidates.  Returns (gathered records [>= C, K], order [C])."""
+    candidates.  Returns (gathered records [>= C, K], order [C]).
+
+    The per-candidate records of engine.eval_robust_device plug in directly: pass the rank's
+    ``worst`` (or ``mean``) tensor [n, my], with the candidates whose ``n_failed`` exceeds the
+    tolerated count set to NaN (RobustResult.scores does the same on the host), as J with nref = 1:
+    ``gather_and_rank(worst, n, 1, weights, C)``.  NaN records rank last."""
     local = worst_over_draws(J, n, nref)
     costs = gather_costs(local, owners=owners) if distributed else local
     return costs, rank_candidates(costs, weights, C)

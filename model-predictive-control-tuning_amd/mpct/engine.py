@@ -375,3 +375,103 @@ def eval_batch_multi(sc: Scenario, devices, N2, Nu, delta, lam, refs, v=None, op
     if rc != 0:
         raise MpctError("mpct_eval_batch_multi failed (%d): %s" % (rc, _lib.last_error()))
     return res
+
+
+# --------------------------------------------------------------------------------------------
+# robust scoring over plant draws (mpct_eval_robust, include/mpct.h)
+@dataclass
+class RobustResult:
+    """One record per candidate over its D draws.  A draw fails when its status is non-zero, its
+    total cost J = sum_i J1_i is not finite, or J > j_bound; the statistics run over the others."""
+    mean: np.ndarray          # (C, my) mean over the surviving draws of J1_i; NaN if none survives
+    worst: np.ndarray         # (C, my) max over the surviving draws of J1_i; NaN if none survives
+    n_failed: np.ndarray      # (C,) failed draws
+    worst_draw: np.ndarray    # (C,) surviving draw with the largest J (lowest index on ties); -1 if none
+    status: np.ndarray        # (C,) OR of the draws' status bits
+    draws: int = 1
+    J1: np.ndarray | None = None   # (C * draws, my) per-simulation costs of the same launch (want_J1)
+
+    def scores(self, max_failed: int = 0, stat: str = "worst") -> np.ndarray:
+        """(C, my) costs for ranking: the chosen statistic ('worst' or 'mean'), NaN for every
+        candidate with more than ``max_failed`` failed draws (rank_candidates and mpct_rank_device
+        sort NaN last)."""
+        if stat not in ("worst", "mean"):
+            raise ValueError("stat must be 'worst' or 'mean'")
+        s = np.array(self.worst if stat == "worst" else self.mean, dtype=float, copy=True)
+        s[np.asarray(self.n_failed) > int(max_failed)] = np.nan
+        return s
+
+
+def eval_robust(sc: Scenario, N2, Nu, delta, lam, refs, v=None, j_bound=0.0, device=-1, want_J1=False,
+                max_qp_iter=0, feas_tol=0.0) -> RobustResult:
+    """Score C candidates over the D = len(refs) draws (reference set k, plant variant k % nplant)
+    and reduce on the device to per-candidate statistics (host arrays in and out).  ``j_bound``:
+    a draw whose total cost exceeds it fails (0 = 1e100, inf allowed)."""
+    N2 = np.ascontiguousarray(np.atleast_1d(N2), dtype=np.int32)
+    Cn = N2.size
+    Nu = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(Nu), (Cn,)), dtype=np.int32)
+    delta = np.ascontiguousarray(np.asarray(delta, dtype=float).reshape(Cn, sc.my))
+    lam = np.ascontiguousarray(np.asarray(lam, dtype=float).reshape(Cn, sc.nu))
+    refs = np.ascontiguousarray(np.asarray(refs, dtype=float).reshape(-1, sc.my, sc.nit))
+    D = refs.shape[0]
+    vv = None
+    if sc.nd + sc.nq:
+        vv = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=float).reshape(-1, sc.nd + sc.nq, sc.nit),
+                                                  (D, sc.nd + sc.nq, sc.nit)))
+    res = RobustResult(mean=np.zeros((Cn, sc.my)), worst=np.zeros((Cn, sc.my)), n_failed=np.zeros(Cn, dtype=np.int32),
+                       worst_draw=np.zeros(Cn, dtype=np.int32), status=np.zeros(Cn, dtype=np.int32), draws=D,
+                       J1=np.zeros((Cn * D, sc.my)) if want_J1 else None)
+    r = _lib.MpctRobustResult()
+    r.mean, r.worst = _dp(res.mean), _dp(res.worst)
+    r.n_failed, r.worst_draw, r.status = _ip(res.n_failed), _ip(res.worst_draw), _ip(res.status)
+    if want_J1:
+        r.J1 = _dp(res.J1)
+    o = _opts(False, False, device, max_qp_iter, feas_tol)
+    rc = sc.lib.mpct_eval_robust(sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data, lam.ctypes.data,
+                                 D, refs.ctypes.data, vv.ctypes.data if vv is not None else None, float(j_bound),
+                                 C.byref(o), C.byref(r))
+    if rc != 0:
+        raise MpctError("mpct_eval_robust failed (%d): %s" % (rc, _lib.last_error()))
+    return res
+
+
+def _robust_struct(out: dict):
+    r = _lib.MpctRobustResult()
+
+    def ptr(t, ty):
+        return C.cast(C.c_void_p(t.data_ptr()), ty) if t is not None else None
+
+    r.mean, r.worst = ptr(out.get("mean"), _lib.c_double_p), ptr(out.get("worst"), _lib.c_double_p)
+    r.n_failed, r.worst_draw = ptr(out.get("n_failed"), _lib.c_int32_p), ptr(out.get("worst_draw"), _lib.c_int32_p)
+    r.status, r.J1 = ptr(out.get("status"), _lib.c_int32_p), ptr(out.get("J1"), _lib.c_double_p)
+    return r
+
+
+def eval_robust_device(sc: Scenario, N2, Nu, delta, lam, refs, out: dict, v=None, j_bound=0.0, device=-1,
+                       stream=None):
+    """Device-pointer entry of eval_robust: every argument is a CUDA (HIP) torch tensor; the records
+    are written into the tensors of ``out`` (keys mean, worst: float64 [C, my]; n_failed, worst_draw,
+    status: int32 [C]; J1: float64 [C * D, my]; any may be absent).  Enqueued on ``stream`` (torch
+    stream; default: current) and not synchronised."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    r = _robust_struct(out)
+    o = _opts(False, False, device)
+    rc = sc.lib.mpct_eval_robust_device(
+        sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+        C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+        C.c_void_p(v.data_ptr()) if v is not None else None, float(j_bound), C.byref(o), C.byref(r),
+        C.c_void_p(stream.cuda_stream))
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+def robust_instance(sc: Scenario) -> str:
+    """mpct_robust_instance: what eval_robust launches for this scenario."""
+    buf = C.create_string_buffer(192)
+    n = sc.lib.mpct_robust_instance(sc.handle, None, buf, len(buf))
+    if n < 0:
+        raise MpctError(_lib.last_error())
+    return buf.value.decode()
