@@ -132,7 +132,11 @@ typedef struct mpct_scenario_desc {
   const mpct_dtf* dist;
   /* nplant     number of simulated-plant variants (plant-mismatch Monte-Carlo draws, SURVEY
    *            §8d config 4); 0 or 1 -> the single plant above.  Simulation s = c*nref + k runs
-   *            variant k % nplant (the draws ride on the reference dimension)
+   *            variant k % nplant (the draws ride on the reference dimension).  Variants do not
+   *            change which kernel runs: a GPC-mode scenario stays on gpc_small_kernel (cost-only
+   *            batches) when every entry of EVERY variant is within its limits (<= 4 plant terms,
+   *            taps within the input ring), e.g. the Shell 3x3 model-error draws of
+   *            Shell3x3.m:34-48; one variant outside them and the general kernel runs all
    * plant_var  [nplant][my*(nu+nd)] variant plants (replace plant when nplant > 1)           */
   int32_t nplant;
   const mpct_dtf* plant_var;

@@ -4,10 +4,14 @@
 // Same simulation as gpc_closed_loop_kernel (closedloop_toolbox.m:36-50 restated as the
 // toolbox-equivalent GPC of DESIGN.md §2, costs GAM_fun.m:110-111 J1 and VNS2.m:172-177 j22), for
 // scenarios the host marks `small` (scenario_tables.h small_plant): my <= 4 outputs, nu <= 3 MVs, no
-// measured or plant-only disturbances, one plant, GPC (not DTC) mode, y difference state <= 12
-// entries (<= 4 per output), past-control registers <= 8 per MV, <= 4 plant terms per entry, and
-// cost-only batches (no open-loop leg, no trajectories).  The Shell 3x3 metric (BASELINE config 2)
-// is such a scenario.  Others run the general kernel.
+// measured or plant-only disturbances, GPC (not DTC) mode, y difference state <= 12 entries (<= 4
+// per output), past-control registers <= 8 per MV, <= 4 plant terms per entry of every plant
+// variant, and cost-only batches (no open-loop leg, no trajectories).  The Shell 3x3 metric
+// (BASELINE config 2) is such a scenario, and so is its model-error study (mpct.scenarios
+// shell3x3_mc: the controller keeps the nominal model, simulation k runs plant variant k % nvar).
+// Others run the general kernel.  The variant only selects which 64 rows of the host's lane tables
+// a simulation reads before its step loop; prologue, QP, LDS layout and launch are the same for
+// every variant.
 //
 // Lane layout (lane L = 16 k + e, e = 4 i + j):
 //   * plant: lane (k, e) holds term k of entry (output i, input j): a numerator tap b times a
@@ -130,9 +134,12 @@ __global__ void __launch_bounds__(64, 4)
   // the plant coefficient lives across the loop (round 5 spilled it to scratch and reloaded it at
   // the top of every step; re-reading it from the scenario table instead measured 2.5 % slower on
   // the heaviest 256; the bounds in LDS freed the registers in round 6)
-  const double pcoef = sc.sm_coef[lane];
-  const int pbase = L.hist + sc.sm_hoff[lane];
-  const int pc = sc.sm_hc[lane], pmask = sc.sm_hmask[lane];
+  // (the tables are [nvar][64]: this simulation's plant variant is Monte-Carlo draw kref % nvar, read
+  // here once, so the loop carries nothing more than it does for one plant)
+  const int pv = sc.nvar > 1 ? (kref % sc.nvar) * kWave : 0;
+  const double pcoef = sc.sm_coef[pv + lane];
+  const int pbase = L.hist + sc.sm_hoff[pv + lane];
+  const int pc = sc.sm_hc[pv + lane], pmask = sc.sm_hmask[pv + lane];
   const int ke = sc.sm_ke;
   // output lane 4 i (i < my): y difference state offset and length
   const int oi = (lane >> 2) & 3;

@@ -632,27 +632,32 @@ struct SmallTables {
 };
 
 // gpc_small_kernel's lane tables (gpc_small.hip; lane L = 16 k + 4 i + j), or false when the scenario
-// is not a small plant: my <= 4 outputs, nu <= 3 MVs, no MD / plant-only inputs, one plant, GPC mode,
-// y difference state <= kSmY entries (<= 4 per output), past-control registers <= kSmR, <= 4 plant
-// terms per entry
+// is not a small plant: my <= 4 outputs, nu <= 3 MVs, no MD / plant-only inputs, GPC mode, y difference
+// state <= kSmY entries (<= 4 per output), past-control registers <= kSmR, and every entry of every
+// plant variant <= 4 plant terms with rings the kernel holds (one variant outside the limits and the
+// whole scenario is not small).  Tables: coef / hoff / hc / hmask [nvar][64], variant v's lane L at
+// v * 64 + L (dtc_small_plant's convention); ke, and with it the LDS layout, is one per scenario: the
+// maximum over the variants
 inline bool small_plant(const mpct_scenario* s, SmallTables* tb) {
-  if (s->mdband || s->nmpc || s->dtc || s->nd || s->nq || s->nvar != 1) return false;
+  if (s->mdband || s->nmpc || s->dtc || s->nd || s->nq || s->nvar < 1) return false;
   if (s->my > 4 || s->nu > 3 || s->npin != s->nu || s->nyh > kSmY) return false;
   for (int i = 0; i < s->my; ++i)
     if (s->nyhi[i] > 4) return false;
   for (int n = 0; n < s->nu; ++n)
     if (s->dum[n] > kSmR) return false;
   int na_max = 0;
-  for (int e = 0; e < s->ne; ++e) {
+  for (int e = 0; e < s->nvar * s->ne; ++e) {
     const int nbz = s->pl.nb[e] - s->pl.off[e], na1 = s->pl.na[e] - 1;
     if (nbz + na1 > 4 || na1 >= kSmE || s->pl.nb[e] > kSmU) return false;
     na_max = std::max(na_max, na1);
   }
-  tb->init(kWave, na_max);
-  for (int L = 0; L < kWave; ++L) {
-    const int k = L >> 4, ep = L & 15, i = ep >> 2, j = ep & 3;
-    if (i < s->my && j < s->nu) tb->tap(L, k, s->pl, i * s->npin + j, j, ep, kSmEOff);
-  }
+  tb->init((size_t)s->nvar * kWave, na_max);
+  for (int v = 0; v < s->nvar; ++v)
+    for (int L = 0; L < kWave; ++L) {
+      const int k = L >> 4, ep = L & 15, i = ep >> 2, j = ep & 3;
+      if (i < s->my && j < s->nu)
+        tb->tap((size_t)v * kWave + L, k, s->pl, (size_t)v * s->ne + i * s->npin + j, j, ep, kSmEOff);
+    }
   tb->map_columns(s);
   return true;
 }

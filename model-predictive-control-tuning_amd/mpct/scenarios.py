@@ -65,6 +65,48 @@ def shell3x3(n2_max=30, nu_max=5, nit=SHELL3_NIT, L=SHELL3_L, R=SHELL3_R, window
     return sc, r, yref
 
 
+# Shell3x3.m:43-45 "model error case": the simulated plant's gains are K + DK * e_j (column j)
+SHELL3_DK = np.array([[2.11, 0.39, 0.59], [3.29, 0.57, 0.89], [3.11, 0.73, 1.33]])
+SHELL3_EMAX = (0.2, 0.2, 0.3)   # Shell3x3.m:38 (nominal = false)
+
+
+def shell3x3_mc_plants(draws, seed=20250307, e_max=SHELL3_EMAX, max_dshift=0, L=SHELL3_L, R=SHELL3_R):
+    """Plant-mismatch draws around Shell3x3.m's model error case (:34-48): gains K[i, j] + DK[i, j] * e_j,
+    time constants and delays of the nominal model, scaled by L, R like shell3x3_plant.  Draw 0 is the
+    reference's case, e = e_max exactly (and no delay shift); draws k >= 1 take e_j ~ U(-e_max_j,
+    e_max_j) from numpy default_rng(seed), three numbers per draw.  max_dshift > 0 adds U{0..max_dshift}
+    * Ts to every entry's delay of the draws k >= 1, drawn after that draw's gains from a stream of its
+    own (default_rng([seed, 1])), so the gains are the same for every max_dshift.  e = 0 gives
+    shell3x3_plant.  Returns a list of 3x3 plants (mpct.lti.Tf)."""
+    e_max = np.broadcast_to(np.asarray(e_max, dtype=float), (3,))
+    rng = np.random.default_rng(seed)
+    rng_d = np.random.default_rng([seed, 1]) if max_dshift > 0 else None
+    out = []
+    for k in range(draws):
+        e = e_max if k == 0 else rng.uniform(-e_max, e_max)
+        sh = np.zeros((3, 3), dtype=int) if k == 0 or rng_d is None else rng_d.integers(0, max_dshift + 1, (3, 3))
+        out.append([[c2d([SHELL3_K[i, j] + SHELL3_DK[i, j] * e[j]], [SHELL3_TAU[i, j], 1.0], SHELL3_TS,
+                         SHELL3_DELAY[i, j] + sh[i, j] * SHELL3_TS).scale(L[i] * R[j])
+                     for j in range(3)] for i in range(3)])
+    return out
+
+
+def shell3x3_mc(draws=8, n2_max=30, nu_max=5, nit=SHELL3_NIT, seed=20250307, e_max=SHELL3_EMAX, max_dshift=0,
+                L=SHELL3_L, R=SHELL3_R):
+    """The constrained Shell 3x3 loop of shell3x3() over `draws` mismatched plants (shell3x3_mc_plants;
+    variant k runs with reference row k): the controller keeps the nominal model, bounds and Yref are
+    those of shell3x3().  Returns (Scenario, refs [draws, 3, nit], plants)."""
+    P = shell3x3_plant(L, R)
+    plants = shell3x3_mc_plants(draws, seed, e_max, max_dshift, L, R)
+    X = shell3x3_xsp(nit)
+    yref = L[:, None] * shell3x3_yref(X)
+    r = L[:, None] * X
+    sc = Scenario(plants[0], P, nu=3, du_min=-0.05 / R, du_max=0.05 / R, u_min=-1.0 / R, u_max=0.5 / R,
+                  yref=yref, n2_max=n2_max, nu_max=nu_max, Ts=SHELL3_TS, window="toolbox",
+                  plant_variants=plants)
+    return sc, np.broadcast_to(r, (draws, 3, nit)).copy(), plants
+
+
 def vns_step_refs(my, nit, inK=10):
     """VNS2.m:58-61 + 147-150: one simulation per output with a unit step on that output."""
     R = np.zeros((my, my, nit))

@@ -9,7 +9,13 @@ Warm-up launches, then HIP-event timings of REPS repetitions per route, interlea
 so that clock drift hits both alike; median, min, max and the spread are reported, with the bytes
 each route writes.  Also counts the candidates with no failed draw at the default bound.
 
-python tools/robust_bench.py [--candidates C] [--draws D] [--reps N] [--out profiles/r07_robust_bench.json]"""
+--workload shell3x3: the Shell 3x3 model-error study (mpct.scenarios.shell3x3_mc): the 4,096 metric
+candidates x 8 plant draws through eval_robust_device, timed the same way.  With --baseline-lib (a
+libmpct.so of another build, e.g. the parent commit's, loaded beside this build's in one process) the
+two libraries are the two routes, interleaved, and their records are compared.
+
+python tools/robust_bench.py [--candidates C] [--draws D] [--reps N] [--out profiles/r07_robust_bench.json]
+python tools/robust_bench.py --workload shell3x3 [--baseline-lib PATH] [--out profiles/r08_robust_shell3x3.json]"""
 import argparse
 import json
 import os
@@ -23,14 +29,111 @@ from mpct.dtc import config4_candidates, woodberry_mc
 from mpct.engine import eval_batch_device, eval_robust_device, kernel_instance, robust_instance
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--candidates", type=int, default=10000)
-ap.add_argument("--draws", type=int, default=32)
+ap.add_argument("--workload", choices=("config4", "shell3x3"), default="config4")
+ap.add_argument("--baseline-lib", default=None, help="shell3x3: another build's libmpct.so to time against")
+ap.add_argument("--candidates", type=int, default=None)
+ap.add_argument("--draws", type=int, default=None)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--reps", type=int, default=11)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_robust_bench.json"))
+ap.add_argument("--out", default=None)
 a = ap.parse_args()
-Cn, D, my = a.candidates, a.draws, 2
 JB = 1e100  # the default bound (j_bound = 0)
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def stats(t):
+    t = np.sort(np.asarray(t))
+    return {"median_ms": float(np.median(t)), "min_ms": float(t[0]), "max_ms": float(t[-1]),
+            "spread_pct": float(100.0 * (t[-1] - t[0]) / np.median(t)), "all_ms": [float(x) for x in t]}
+
+
+def write(res, default_name):
+    out = a.out or os.path.join(ROOT, "profiles", default_name)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
+def shell3x3_workload():
+    """4,096 metric candidates x 8 model-error draws of Shell 3x3, eval_robust_device on this build
+    and, with --baseline-lib, on that library too (its scenario is created through that library)."""
+    from mpct import _lib
+    from mpct.scenarios import candidate_grid, shell3x3_mc
+
+    Cn, D, my = a.candidates or 4096, a.draws or 8, 3
+    dev = torch.device("cuda", 0)
+    builds = {"this_build": shell3x3_mc(draws=D)}
+    if a.baseline_lib:
+        os.environ["MPCT_LIB"] = os.path.abspath(a.baseline_lib)
+        _lib._lib = None  # the next Scenario loads and keeps the baseline library; the first keeps its own
+        builds["baseline"] = shell3x3_mc(draws=D)
+    N2, Nu, dl, lm = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in candidate_grid(Cn))
+    run, outs = {}, {}
+    for name, (sc, refs, _) in builds.items():
+        refs_d = torch.from_numpy(refs).to(dev)
+        out = dict(mean=torch.empty((Cn, my), dtype=torch.float64, device=dev),
+                   worst=torch.empty((Cn, my), dtype=torch.float64, device=dev),
+                   n_failed=torch.empty(Cn, dtype=torch.int32, device=dev),
+                   worst_draw=torch.empty(Cn, dtype=torch.int32, device=dev),
+                   status=torch.empty(Cn, dtype=torch.int32, device=dev))
+        outs[name] = out
+        run[name] = (lambda sc=sc, refs_d=refs_d, out=out: eval_robust_device(sc, N2, Nu, dl, lm, refs_d, out))
+    for _ in range(a.warmup):
+        for fn in run.values():
+            fn()
+    torch.cuda.synchronize()
+    t = {name: [] for name in run}
+    for _ in range(a.reps):
+        for name, fn in run.items():
+            t[name].append(timed(fn))
+    torch.cuda.synchronize()
+    res = {"tool": "tools/robust_bench.py --workload shell3x3",
+           "workload": "Shell 3x3 model-error draws (shell3x3_mc): metric candidates x plant draws, nit = 500",
+           "device": torch.cuda.get_device_name(0), "candidates": Cn, "draws": D, "nit": 500, "warmup": a.warmup,
+           "reps": a.reps, "timing": "HIP events around each eval_robust_device call, builds interleaved",
+           "j_bound": JB}
+    host = {}
+    for name, (sc, _, _) in builds.items():
+        o = {k: v.cpu().numpy() for k, v in outs[name].items()}
+        host[name] = o
+        st, cnt = np.unique(o["status"], return_counts=True)
+        nf, ncnt = np.unique(o["n_failed"], return_counts=True)
+        res[name] = dict(stats(t[name]), instance=robust_instance(sc), per_simulation_instance=kernel_instance(sc),
+                         sims_per_s=float(Cn * D / (np.median(t[name]) * 1e-3)),
+                         status_counts={str(int(k)): int(v) for k, v in zip(st, cnt)},
+                         n_failed_counts={str(int(k)): int(v) for k, v in zip(nf, ncnt)},
+                         candidates_without_failed_draw=int(np.count_nonzero(o["n_failed"] == 0)))
+    line = {"this_build_median_ms": res["this_build"]["median_ms"]}
+    if a.baseline_lib:
+        x, y = host["this_build"], host["baseline"]
+        both = np.isfinite(x["worst"]) & np.isfinite(y["worst"])
+        res["ratio_this_over_baseline_median"] = float(np.median(t["this_build"]) / np.median(t["baseline"]))
+        res["records_agree"] = {
+            "status_equal": bool(np.array_equal(x["status"], y["status"])),
+            "n_failed_equal": bool(np.array_equal(x["n_failed"], y["n_failed"])),
+            "worst_draw_equal_fraction": float(np.mean(x["worst_draw"] == y["worst_draw"])),
+            "worst_max_rel_diff": float(np.max(np.abs(x["worst"][both] - y["worst"][both]) / np.abs(y["worst"][both])))
+            if both.any() else None}
+        line |= {"baseline_median_ms": res["baseline"]["median_ms"], "ratio": res["ratio_this_over_baseline_median"]}
+    write(res, "r08_robust_shell3x3.json")
+    print(json.dumps(line | {"instance": res["this_build"]["instance"],
+                             "n_failed_counts": res["this_build"]["n_failed_counts"]}))
+
+
+if a.workload == "shell3x3":
+    shell3x3_workload()
+    sys.exit(0)
+
+Cn, D, my = a.candidates or 10000, a.draws or 32, 2
 
 sc, refs, v, _ = woodberry_mc(draws=D, n2_max=30, nu_max=10)
 dev = torch.device("cuda", 0)
@@ -65,15 +168,6 @@ def route_b():
     eval_robust_device(sc, N2, Nu, dl, lm, refs_d, rob, v=v_d)
 
 
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
-
-
 for _ in range(a.warmup):
     route_a()
     route_b()
@@ -86,13 +180,6 @@ ra = route_a()
 route_b()
 torch.cuda.synchronize()
 nf_a, nf_b = ra[2].cpu().numpy(), rob["n_failed"].cpu().numpy()
-
-
-def stats(t):
-    t = np.sort(np.asarray(t))
-    return {"median_ms": float(np.median(t)), "min_ms": float(t[0]), "max_ms": float(t[-1]),
-            "spread_pct": float(100.0 * (t[-1] - t[0]) / np.median(t)), "all_ms": [float(x) for x in t]}
-
 
 rec_bytes = Cn * (2 * my * 8 + 3 * 4)
 res = {"tool": "tools/robust_bench.py", "workload": "config 4: DTC-GPC WoodBerry, plant-mismatch draws",
@@ -107,10 +194,7 @@ res = {"tool": "tools/robust_bench.py", "workload": "config 4: DTC-GPC WoodBerry
        "candidates_without_failed_draw": int(np.count_nonzero(nf_b == 0)),
        "candidates_all_draws_failed": int(np.count_nonzero(nf_b == D)),
        "j_bound": JB}
-os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-with open(a.out, "w") as f:
-    json.dump(res, f, indent=1)
-    f.write("\n")
+write(res, "r07_robust_bench.json")
 print(json.dumps({k: res[k] for k in ("ratio_b_over_a_median", "n_failed_agree", "candidates_without_failed_draw")}
                  | {"a_median_ms": res["a_per_simulation_plus_torch"]["median_ms"],
                     "b_median_ms": res["b_eval_robust_device"]["median_ms"]}))
