@@ -146,8 +146,9 @@ typedef struct mpct_scenario_desc {
    *             columns nu..nu+nd-1 of plant/model enter the prediction held at v(t)
    *             (mpcsimopt MDLookAhead 'off'); OV Min/Max are softened by MinECR/MaxECR with ONE
    *             slack eps >= 0 weighted by rho_ecr (Weights.ECR); Weights.OV / Weights.MVRate act
-   *             over the ScaleFactors.  Requires plant == model (closedloop_toolbox.m:50 sims the
-   *             model), n1[i] == 1 (PredictionHorizon window), dtc == 0, nq == 0, nplant <= 1 and
+   *             over the ScaleFactors.  mpct_scenario_create requires plant == model
+   *             (closedloop_toolbox.m:50 sims the model) and nplant <= 1; mpct_scenario_create_est with
+   *             MPCT_EST_OUTPUT_BIAS lifts both.  Requires n1[i] == 1 (PredictionHorizon window), dtc == 0, nq == 0 and
    *             nu*nu_max + 1 <= 64.  na/carima_A/nb/carima_B/dp may be NULL (no Diophantine tables).
    * y_min, y_max [my]      OV Min / Max, already scaled (MPCTuning.m:180-181); +-INFINITY: none
    * ecr_min, ecr_max [my]  OV MinECR / MaxECR (0: hard output bound)
@@ -257,6 +258,24 @@ const char* mpct_last_error(void);
  * rows; see DESIGN.md §Data layout).  Does NOT touch the GPU (device copies are made on first
  * evaluation), so it is usable on a CPU-only host for inspection.  Returns MPCT_OK. */
 int32_t mpct_scenario_create(const mpct_scenario_desc* desc, mpct_scenario** out);
+
+/* Build a band-kernel scenario whose simulated plant differs from the controller's model (an
+ * addition to ABI 7: no struct, export or behaviour of mpct_scenario_create changes).
+ *   estimator  0: exactly mpct_scenario_create.
+ *              MPCT_EST_OUTPUT_BIAS: requires mdband = 1.  desc->plant may differ from desc->model and
+ *              nplant > 1 / plant_var ([nplant][my*(nu+nd)], MD columns included) give the plant
+ *              draws; simulation s = c*nref + k runs variant k % nplant.  The controller keeps
+ *              desc->model and corrects its prediction by the deadbeat output-disturbance observer
+ *              (the DMC / IMC bias): b_i(t) = y_i(t) - ym_i(t), ym the model driven from rest by the
+ *              applied MVs u(0..t-1) and the measured v(0..t); the QP at step t sees the free
+ *              response plus b_i(t) on every row k = 1..N2 of output i, in the tracking term and
+ *              the band rows alike.  A stated substitute for the toolbox's default
+ *              Kalman estimator, not a restatement of it.  With plant == model b is exactly 0 and
+ *              the loop is the nominal one.  dtc and nq > 0 stay rejected.  Closed loop only:
+ *              evaluating such a scenario with open_loop = 1 returns MPCT_EINVAL.
+ *   any other estimator id, or a non-zero one with mdband = 0: MPCT_EINVAL. */
+#define MPCT_EST_OUTPUT_BIAS 1
+int32_t mpct_scenario_create_est(const mpct_scenario_desc* desc, int32_t estimator, mpct_scenario** out);
 void mpct_scenario_destroy(mpct_scenario* s);
 
 /* Host-table inspection (testing / MATLAB-side debugging; no device needed).

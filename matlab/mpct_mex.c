@@ -8,7 +8,8 @@
  * reference's own mpc / nlmpc objects and call:
  *
  *   v = mpct_mex('version')                          ABI version of the loaded libmpct
- *   h = mpct_mex('create', desc)                     linear scenario (mpct_scenario_create)
+ *   h = mpct_mex('create', desc)                     linear scenario (mpct_scenario_create, or
+ *                                                    mpct_scenario_create_est when desc.estimator ~= 0)
  *   h = mpct_mex('create_nmpc', desc)                NMPC scenario (mpct_nmpc_scenario_create)
  *   [J1,j21,j22,Jnu,status,iters,y,u,ys,uopt] = mpct_mex('eval', h, N2, Nu, delta, lambda, r, v, opts)
  *   [...] = mpct_mex('eval_multi', h, devices, N2, Nu, delta, lambda, r, v, opts)
@@ -264,8 +265,12 @@ static void cmd_create(int nlhs, mxArray* plhs[], const mxArray* d) {
     if (field(d, "u_scale", 0)) D.u_scale = doubles(field(d, "u_scale", 0), D.nu, "u_scale");
     D.rho_ecr = fscalar(d, "rho_ecr", 1e4);
   }
+  /* optional scalar field estimator: absent or 0 is mpct_scenario_create; MPCT_EST_OUTPUT_BIAS (1)
+   * lets plant / plant_var differ from model on a band scenario (mpct_scenario_create_est) */
+  const int32_t estimator = (int32_t)fscalar(d, "estimator", 0);
   mpct_scenario* s = NULL;
-  if (mpct_scenario_create(&D, &s) != MPCT_OK) lib_error("mpct:create");
+  if ((estimator ? mpct_scenario_create_est(&D, estimator, &s) : mpct_scenario_create(&D, &s)) != MPCT_OK)
+    lib_error("mpct:create");
   if (nlhs >= 0) plhs[0] = new_handle(s);
 }
 

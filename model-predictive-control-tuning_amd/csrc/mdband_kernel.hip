@@ -89,7 +89,8 @@ constexpr long long kBandCapsKb[] = {20, 26, 32, 40, 53, 80, 160};
 
 
 // full_ri: R^-1 is a full triangle (some OV weight > 0); in band mode R is diagonal and only its
-// inverse diagonal is kept.  ncopy: 2 with the open-loop prediction (a second plant copy), else 1
+// inverse diagonal is kept.  ncopy: 2 with the open-loop prediction (a second plant copy) or the
+// output-bias estimator (the parallel model runs in that copy), else 1
 __host__ __device__ inline BandLayout band_layout(const DevScenario& sc, int N2, int M, bool full_ri = true,
                                                   int ncopy = 2) {
   const int Mz = M + 1, my = sc.my, nu = sc.nu, nin = sc.nin, ne = sc.ne;
@@ -285,7 +286,14 @@ struct BandMark {
   }
 };
 
-template <int MAXM>
+// EST: the output-bias estimator (DevScenario::est).  Simulation (c, k) runs plant
+// variant k % nvar in copy 0; copy 1 is the controller's model driven by the same u and v (the same
+// entry recursion on the mz tables), b_i(t) = y_i(t) - ym_i(t) on lanes i < my, and the QP sees the
+// window plus b_i through a shifted reference and shifted output bounds (r_i - b_i in solve's
+// argument, y_min/y_max - b_i in sob): no biased copy of the window, nothing more live in the step
+// loop.  Tables equal to the model's give b = +0.0 exactly and x - 0.0 = x: the nominal loop, bitwise.
+// The open-loop leg shares copy 1 and is not run (the host rejects open_loop on such scenarios)
+template <int MAXM, bool EST>
 __global__ void __launch_bounds__(64, 1)
     mdband_closed_loop_kernel(const DevScenario sc, long long C, int nref, const int* __restrict__ N2v,
                               const int* __restrict__ Nuv, const double* __restrict__ deltav,
@@ -337,7 +345,9 @@ __global__ void __launch_bounds__(64, 1)
   };
   bool any_q = false;  // some OV tracked: R full; band mode: R (and J = R^-1) diagonal
   for (int i = 0; i < my; ++i) any_q = any_q || qw(i) > 0.0;
-  const BandLayout L = band_layout(sc, N2, M, any_q, o.open_loop ? 2 : 1);
+  const bool open_loop = !EST && o.open_loop;
+  const BandLayout L = band_layout(sc, N2, M, any_q, EST || o.open_loop ? 2 : 1);
+  const int vo = EST ? (kref % sc.nvar) * ne : 0;  // this simulation's plant variant: tables [nvar][ne]
   // this launch serves one (QP size, LDS) class: the others' simulations leave at once
   if (Mz <= mz_lo || Mz > MAXM || (long long)L.total * 8 <= lds_lo || (long long)L.total * 8 > lds_hi) return;
   const int tls = sc.tlen;
@@ -370,10 +380,10 @@ __global__ void __launch_bounds__(64, 1)
 
   // ------------------------------------------------------------------ prologue
   for (int e = lane; e < ne * sc.pl_maxbc; e += kWave) {
-    const int en = e / sc.pl_maxbc, l = e - en * sc.pl_maxbc, off = sc.pl_off[en];
-    splb[e] = off + l < sc.pl_nb[en] ? sc.pl_b[en * sc.pl_maxb + off + l] : 0.0;
+    const int en = e / sc.pl_maxbc, l = e - en * sc.pl_maxbc, off = sc.pl_off[vo + en];
+    splb[e] = off + l < sc.pl_nb[vo + en] ? sc.pl_b[(vo + en) * sc.pl_maxb + off + l] : 0.0;
   }
-  for (int e = lane; e < ne * sc.pl_maxa; e += kWave) spla[e] = sc.pl_a[e];
+  for (int e = lane; e < ne * sc.pl_maxa; e += kWave) spla[e] = sc.pl_a[vo * sc.pl_maxa + e];
   for (int e = lane; e < ne * sc.mz_maxbc; e += kWave) {
     const int en = e / sc.mz_maxbc, l = e - en * sc.mz_maxbc, off = sc.mz_off[en];
     smzb[e] = off + l < sc.mz_nb[en] ? sc.mz_b[en * sc.mz_maxb + off + l] : 0.0;
@@ -949,7 +959,7 @@ __global__ void __launch_bounds__(64, 1)
   // closedloop_toolbox.m:86-91: initial state, yo = 0, reference r(:,end), MD v(:,end) held from
   // time 0: the window is the MD step responses times v_end
   double jnu = 0.0;
-  if (o.open_loop) {
+  if (open_loop) {
     for (int g = lane; g < P; g += kWave) {
       const int i = g / N2, k = g - i * N2;
       double f = 0.0;
@@ -981,7 +991,7 @@ __global__ void __launch_bounds__(64, 1)
   PSTAMP(PROF_PROLOGUE);
   // ------------------------------------------------------------------ closed loop
   double j1 = 0.0, j21 = 0.0, j22 = 0.0;
-  const int ncopy = o.open_loop ? 2 : 1;
+  const int ncopy = EST || o.open_loop ? 2 : 1;
   double r_t = 0.0, yr_t = 0.0;
   if (lane < my) {
     r_t = rr[lane * nit];
@@ -998,19 +1008,22 @@ __global__ void __launch_bounds__(64, 1)
       const int cpy = e / nd, j = e - cpy * nd;
       sur[(cpy * nin + nu + j) * L.ur + (t & umask)] = vvk[j * nit + t];
     }
-    if (o.open_loop && lane < nu) {
+    if (open_loop && lane < nu) {
       const int l = t < Nu - 1 ? t : Nu - 1;
       sur[(nin + lane) * L.ur + (t & umask)] = sucum[lane * Nu + l];
     }
     lds_sync();
-    // plant entries y_e(t) (copy 0 closed loop, copy 1 open loop driven by uopt)
+    // plant entries y_e(t) (copy 0 closed loop; copy 1 open loop driven by uopt, or with EST the
+    // model's entries driven by the closed loop's own u and v)
     for (int e = lane; e < ncopy * ne; e += kWave) {
       const int cpy = e / ne, ee = e - cpy * ne, j = ee % nin;
-      const double* eb = splb + ee * sc.pl_maxbc - sc.pl_off[ee];  // tap l at eb[l], l >= off
-      const double* ea = spla + ee * sc.pl_maxa;
+      const bool mdl = EST && cpy == 1;
+      const int nb = mdl ? sc.mz_nb[ee] : sc.pl_nb[vo + ee], na = mdl ? sc.mz_na[ee] : sc.pl_na[vo + ee];
+      const int off = mdl ? sc.mz_off[ee] : sc.pl_off[vo + ee];
+      const double* eb = (mdl ? smzb + ee * sc.mz_maxbc : splb + ee * sc.pl_maxbc) - off;  // tap l at eb[l], l >= off
+      const double* ea = mdl ? smza + ee * sc.mz_maxa : spla + ee * sc.pl_maxa;
       const double* eur = sur + (cpy * nin + j) * L.ur;
       double* eyh = syeh + e * L.yh;
-      const int nb = sc.pl_nb[ee], na = sc.pl_na[ee], off = sc.pl_off[ee];
       double a0 = 0.0, a1 = 0.0;
       for (int l = off; l < nb; ++l) a0 += eb[l] * eur[(t - l) & umask];
       for (int l = 1; l < na; ++l) a1 -= ea[l] * eyh[(t - l) & ymask];
@@ -1019,21 +1032,30 @@ __global__ void __launch_bounds__(64, 1)
       sye[e] = acc;
     }
     lds_sync();
+    double bias = 0.0;  // EST: b_i(t) = y_i(t) - ym_i(t)
     if (lane < my) {
       const int i = lane;
       double y = 0.0;
       for (int j = 0; j < nin; ++j) y += sye[i * nin + j];
+      if (EST) {
+        double ym = 0.0;
+        for (int j = 0; j < nin; ++j) ym += sye[ne + i * nin + j];
+        bias = y - ym;
+        // the band rows' shifted bounds (read by the QP after the syncs of the window update)
+        sob[i] = sc.obnd[i] - bias;
+        sob[my + i] = sc.obnd[my + i] - bias;
+      }
       const double e1 = y - yr_t;
       j1 += e1 * e1;
       if (t >= sc.ink0) j22 += e1 * e1;
       double ysv = 0.0;
-      if (o.open_loop) {
+      if (open_loop) {
         for (int j = 0; j < nin; ++j) ysv += sye[ne + i * nin + j];
         if (t >= sc.ink0) j21 += (y - ysv) * (y - ysv);
       }
       if (o.want_traj) {
         if (out.y) out.y[(sim * my + i) * nit + t] = y;
-        if (o.open_loop && out.ys) out.ys[(sim * my + i) * nit + t] = ysv;
+        if (open_loop && out.ys) out.ys[(sim * my + i) * nit + t] = ysv;
       }
     }
     // ---- free-response window F_{t-1} -> F_t
@@ -1109,7 +1131,7 @@ __global__ void __launch_bounds__(64, 1)
 #ifdef MPCT_DEBUG_BAND
     dbg_t = t;
     dbg_reb = dbg_pol = dbg_git = 0;
-    const int it_dbg = solve(Fc, r_t);
+    const int it_dbg = solve(Fc, EST ? r_t - bias : r_t);
     iters += it_dbg;
     if (sim == 0 && lane == 0 && t == MPCT_DEBUG_BAND - 3)
       for (int m = 0; m < Mz; ++m) printf("X %d %.17e\n", m, sxc[m]);
@@ -1117,7 +1139,7 @@ __global__ void __launch_bounds__(64, 1)
       printf("t=%d it=%d git=%d reb=%d pol=%d q=%d eps=%.9e du=%.9e %.9e %.9e F0=%.9e Fend=%.9e y6=%.9e st=%d\n", t, it_dbg, dbg_git, dbg_reb, dbg_pol, gis.q,
              sxc[M], sxc[0], sxc[Nu], sxc[2 * Nu], Fc[0], Fc[N2 - 1], Fc[6 * N2], st);
 #else
-    iters += solve(Fc, r_t);
+    iters += solve(Fc, EST ? r_t - bias : r_t);
 #endif
 #ifdef MPCT_DEBUG_BAND_STEP
     // diagnostic build: the QP solution and active set of simulation 0 at one step
@@ -1133,9 +1155,10 @@ __global__ void __launch_bounds__(64, 1)
       const double un = suprev[n] + du;
       sdu[n] = du;
       sur[n * L.ur + (t & umask)] = un;
+      if (EST) sur[(nin + n) * L.ur + (t & umask)] = un;  // the parallel model's MVs
       if (o.want_traj) {
         if (out.u) out.u[(sim * nu + n) * nit + t] = un;
-        if (o.open_loop && out.uopt) {
+        if (open_loop && out.uopt) {
           const int l = t < Nu - 1 ? t : Nu - 1;
           out.uopt[(sim * nu + n) * nit + t] = sucum[n * Nu + l];
         }
@@ -1157,9 +1180,9 @@ __global__ void __launch_bounds__(64, 1)
     if (!isfinite(j1)) st |= MPCT_ST_NONFINITE_;
     if (out.J1) out.J1[sim * my + lane] = j1;
     if (out.j22) out.j22[sim * my + lane] = j22;
-    if (out.j21) out.j21[sim * my + lane] = o.open_loop ? j21 : NAN;
+    if (out.j21) out.j21[sim * my + lane] = open_loop ? j21 : NAN;
   }
-  if (lane < nu && out.Jnu) out.Jnu[sim * nu + lane] = o.open_loop ? jnu : NAN;
+  if (lane < nu && out.Jnu) out.Jnu[sim * nu + lane] = open_loop ? jnu : NAN;
   const unsigned long long nf = __ballot(st & MPCT_ST_NONFINITE_);
   if (lane == 0) {
     const int s = st | (nf ? MPCT_ST_NONFINITE_ : 0);
@@ -1174,6 +1197,7 @@ __global__ void __launch_bounds__(64, 1)
 // host-side launch
 #include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "work_order.h"
 
@@ -1195,7 +1219,7 @@ long long mdband_lds_bytes(const DevScenario& sc, int N2, int Nu, int ncopy) {
 // candidates).  Status-only outcomes (padding, bad horizons) are written by the first launch.
 // Heaviest classes first, fanned over the caller's stream and the auxiliary streams of `fan`
 // (launch_fan.h): light classes fill the SIMDs a 1-workgroup-per-CU class leaves idle.
-template <int MAXM>
+template <int MAXM, bool EST>
 static int launch_band_t(const DevScenario& sc, long long C, int nref, const int* N2, const int* Nu,
                          const double* delta, const double* lambda, const double* r, const double* v,
                          const DevOpts& o, const DevResult& out, FanScope& fs, int& nl, int mz_lo, bool& first,
@@ -1206,12 +1230,12 @@ static int launch_band_t(const DevScenario& sc, long long C, int nref, const int
   long long lds_max = 0;
   for (int nu_c = 1; nu_c <= nu_hi; ++nu_c)
     for (int n2 = 1; n2 <= sc.n2max; ++n2)
-      lds_max = std::max(lds_max, mdband_lds_bytes(sc, n2, nu_c, o.open_loop ? 2 : 1));
+      lds_max = std::max(lds_max, mdband_lds_bytes(sc, n2, nu_c, EST || o.open_loop ? 2 : 1));
   if (lds_max > 160 * 1024) {
     *err = "scenario needs more than 160 KiB of LDS per simulation";
     return -4;
   }
-  auto kern = mdband_closed_loop_kernel<MAXM>;
+  auto kern = mdband_closed_loop_kernel<MAXM, EST>;
   const long long* capkb = kBandCapsKb;  // workgroups per CU: 160 KB / cap
   constexpr int kCaps = (int)(sizeof(kBandCapsKb) / sizeof(kBandCapsKb[0]));
   static_assert(kCaps <= 8, "at most 8 LDS tiers");
@@ -1258,10 +1282,15 @@ int launch_mdband(const DevScenario& sc, long long C, int nref, const int* N2, c
   FanScope fs(fan, stream);
   bool first = true;
   int nl = 0;
-  if (Mz > 32) rc = launch_band_t<64>(sc, C, nref, N2, Nu, delta, lambda, r, v, o, out, fs, nl, 32, first, err);
-  if (rc == 0 && Mz > 16)
-    rc = launch_band_t<32>(sc, C, nref, N2, Nu, delta, lambda, r, v, o, out, fs, nl, 16, first, err);
-  if (rc == 0) rc = launch_band_t<16>(sc, C, nref, N2, Nu, delta, lambda, r, v, o, out, fs, nl, 0, first, err);
+  auto classes = [&](auto est) {
+    constexpr bool E = decltype(est)::value;
+    if (Mz > 32) rc = launch_band_t<64, E>(sc, C, nref, N2, Nu, delta, lambda, r, v, o, out, fs, nl, 32, first, err);
+    if (rc == 0 && Mz > 16)
+      rc = launch_band_t<32, E>(sc, C, nref, N2, Nu, delta, lambda, r, v, o, out, fs, nl, 16, first, err);
+    if (rc == 0) rc = launch_band_t<16, E>(sc, C, nref, N2, Nu, delta, lambda, r, v, o, out, fs, nl, 0, first, err);
+  };
+  if (sc.est) classes(std::true_type{});
+  else classes(std::false_type{});
   fs.join();
   return rc;
 }

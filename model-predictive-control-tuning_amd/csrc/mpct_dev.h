@@ -118,6 +118,7 @@ struct DevScenario {
   // MD feed-forward + soft output bands (mdband = 1, mdband_kernel.hip): the model entries of all
   // nin = nu + nd columns are the mz_* tables ([my*nin], z^-1 form with delays)
   int mdband;
+  int est;                // mdband: output-bias estimator (plant variants, parallel model copy)
   double rho;             // Weights.ECR
   const double* step_md;  // [my][nd][tlen]  model MD step responses
   const double* obnd;     // [4][my]  y_min, y_max, MinECR*s_y, MaxECR*s_y (+-inf: no bound)

@@ -90,6 +90,16 @@ extern "C" int32_t mpct_scenario_create(const mpct_scenario_desc* d, mpct_scenar
   return created(build_scenario(*d, &err), err, out);
 }
 
+extern "C" int32_t mpct_scenario_create_est(const mpct_scenario_desc* d, int32_t estimator, mpct_scenario** out) {
+  if (!d || !out) return fail(MPCT_EINVAL, "null argument");
+  *out = nullptr;
+  if (estimator != 0 && estimator != MPCT_EST_OUTPUT_BIAS) return fail(MPCT_EINVAL, "unknown estimator id");
+  if (estimator && !(d->abi_version >= 3 && d->mdband))
+    return fail(MPCT_EINVAL, "the output-bias estimator belongs to the band kernel (mdband = 1)");
+  BuildError err;
+  return created(build_scenario(*d, &err, estimator), err, out);
+}
+
 extern "C" int32_t mpct_nmpc_scenario_create(const mpct_nmpc_desc* d, mpct_scenario** out) {
   if (!d || !out) return fail(MPCT_EINVAL, "null argument");
   *out = nullptr;
@@ -231,6 +241,9 @@ static int check_args(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* 
   if (!out) return fail(MPCT_EINVAL, "null result");
   if (!devlist_ok) return fail(MPCT_EINVAL, "ndev must be 1..64 with a device list");
   if (s->dtc && opts && opts->open_loop) return fail(MPCT_EINVAL, "DTC mode has no open-loop prediction");
+  // the parallel model of the output-bias estimator runs in the open-loop leg's plant copy
+  if (s->est && opts && opts->open_loop)
+    return fail(MPCT_EINVAL, "estimator scenarios are closed-loop only: open_loop must be 0");
   return MPCT_OK;
 }
 
@@ -769,6 +782,8 @@ static int32_t copy_name(const std::string& nm, char* buf, int32_t cap) {
 
 static std::string per_simulation_instance(const mpct_scenario* s, bool ext) {
   if (s->nmpc) return "nmpc_closed_loop_kernel (QP-size x LDS-tier class launches)";
+  if (s->mdband && s->est)
+    return "mdband_closed_loop_kernel (QP-size x LDS-tier class launches) + output-bias estimator";
   if (s->mdband) return "mdband_closed_loop_kernel (QP-size x LDS-tier class launches)";
   return closed_loop_instance(dev_scenario(s), s->nu * s->numax, ext);
 }
@@ -803,7 +818,8 @@ static int64_t lds_bytes_ext(const mpct_scenario* s, int32_t N2, int32_t Nu, boo
   if (!s) return fail(MPCT_EINVAL, "null scenario");
   if (s->nmpc) return nmpc_lds_bytes(s->nu * Nu, N2);
   const DevScenario ds = dev_scenario(s);
-  return s->mdband ? mdband_lds_bytes(ds, N2, Nu, ext ? 2 : 1) : lds_bytes_for(ds, N2, Nu, ext);
+  // an estimator scenario always carries the second (parallel model) copy
+  return s->mdband ? mdband_lds_bytes(ds, N2, Nu, ext || s->est ? 2 : 1) : lds_bytes_for(ds, N2, Nu, ext);
 }
 
 extern "C" int64_t mpct_lds_bytes(const mpct_scenario* s, int32_t N2, int32_t Nu) {

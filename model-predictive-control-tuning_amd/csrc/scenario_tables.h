@@ -59,6 +59,9 @@ struct mpct_scenario {
   // MD feed-forward + soft output bands (abi >= 3): model entries of all nin columns in the mz
   // tables, MD step responses, output bounds, weight scales
   int mdband = 0;
+  // output-feedback estimator of the band kernel (mpct_scenario_create_est): 0 none (plant == model),
+  // MPCT_EST_OUTPUT_BIAS the deadbeat output-disturbance observer
+  int est = 0;
   double rho = 0.0;
   std::vector<double> step_md;  // [my][nd][tlen]
   std::vector<double> obnd;     // [4][my]
@@ -219,8 +222,11 @@ inline bool z_tables(const std::vector<ZEntry>& entries, ZTables& t) {
   return true;
 }
 
-// validate a linear scenario descriptor and precompute its tables (no device needed)
-inline std::unique_ptr<mpct_scenario> build_scenario(const mpct_scenario_desc& d_in, BuildError* err) {
+// validate a linear scenario descriptor and precompute its tables (no device needed).  estimator:
+// 0 (mpct_scenario_create) or MPCT_EST_OUTPUT_BIAS on a band descriptor (mpct_scenario_create_est,
+// which checks both: the plant, and every plant variant, may then differ from the model)
+inline std::unique_ptr<mpct_scenario> build_scenario(const mpct_scenario_desc& d_in, BuildError* err,
+                                                     int estimator = 0) {
   mpct_scenario_desc dcopy = d_in;
   const mpct_scenario_desc* d = &dcopy;
   CarimaTables derived;
@@ -242,7 +248,7 @@ inline std::unique_ptr<mpct_scenario> build_scenario(const mpct_scenario_desc& d
   const int nq = d->abi_version >= 2 ? d->nq : 0;
   const int nplant = (d->abi_version >= 2 && d->nplant > 1) ? d->nplant : 1;
   const int mdband = d->abi_version >= 3 ? (d->mdband ? 1 : 0) : 0;
-  if (mdband && (dtc || nq > 0 || nplant > 1))
+  if (mdband && (dtc || nq > 0 || (nplant > 1 && !estimator)))
     return reject(err, MPCT_EINVAL, "mdband excludes dtc, plant-only disturbances and plant variants");
   if (mdband && (!d->y_min || !d->y_max || !d->ecr_min || !d->ecr_max))
     return reject(err, MPCT_EINVAL, "mdband needs y_min, y_max, ecr_min, ecr_max");
@@ -269,6 +275,7 @@ inline std::unique_ptr<mpct_scenario> build_scenario(const mpct_scenario_desc& d
   s->npin = s->nin + nq;
   s->nvar = nplant;
   s->mdband = mdband;
+  s->est = mdband ? estimator : 0;
   if (s->npin > kMaxIn) return reject(err, MPCT_ERANGE, "too many plant inputs");
   s->nit = d->nit;
   s->n2max = d->n2_max;
@@ -430,6 +437,21 @@ inline std::unique_ptr<mpct_scenario> build_scenario(const mpct_scenario_desc& d
   for (int i = 0; i < (mdband ? 0 : my); ++i)
     if (s->nyhi[i] > kYeHist)
       return reject(err, MPCT_ERANGE, "CARIMA denominator order too high for the device (na <= 7)");
+  // the model of every column (MV and MD) of a band scenario, z^-1 form with its delay: the window
+  // extension and, with the estimator, the parallel model (mdband_kernel.hip)
+  std::vector<ZEntry> mentries;
+  for (int e = 0; e < (mdband ? my * nin : 0); ++e) {
+    if (!valid_dtf(d->model[e])) return reject(err, MPCT_EINVAL, "bad model entry");
+    mentries.push_back({&d->model[e], d->model[e].delay});
+  }
+  // the parallel model runs through the plant copies' rings and row strides: with the estimator the
+  // plant tables' row lengths are the maxima over every variant and the model, and the one length
+  // check below covers the model too
+  for (const ZEntry& m : mentries) {
+    if (!s->est) break;
+    s->pl.maxb = std::max(s->pl.maxb, m.delay + m.tf->len);
+    s->pl.maxa = std::max(s->pl.maxa, m.tf->len);
+  }
   if (!z_tables(entries, s->pl)) return reject(err, MPCT_ERANGE, "plant entry too long for the device history rings");
   if (s->dtc) {
     // Pz entries (e < my*nu, real delays) and Gz entries (delays minus dmin_i = n1_i - 1,
@@ -466,20 +488,16 @@ inline std::unique_ptr<mpct_scenario> build_scenario(const mpct_scenario_desc& d
     }
   }
   if (mdband) {
-    // the model of every column (MV and MD), z^-1 form with its delay: the window extension
-    // (mdband_kernel.hip); plant == model (closedloop_toolbox.m:50 sims the controller's model)
-    entries.clear();
-    for (int e = 0; e < my * nin; ++e) {
+    // without an estimator plant == model (closedloop_toolbox.m:50 sims the controller's model)
+    for (int e = 0; e < (s->est ? 0 : my * nin); ++e) {
       const mpct_dtf& m = d->model[e];
       const mpct_dtf& p = d->plant[e];
-      if (!valid_dtf(m)) return reject(err, MPCT_EINVAL, "bad model entry");
       bool same = p.len == m.len && p.delay == m.delay;
       for (int k = 0; same && k < m.len; ++k) same = p.num[k] == m.num[k] && p.den[k] == m.den[k];
       if (!same)
         return reject(err, MPCT_ERANGE, "mdband: plant must equal the model (the toolbox estimator is not restated)");
-      entries.push_back({&m, m.delay});
     }
-    z_tables(entries, s->mz);  // they fit the history rings: they equal the plant's, which did
+    z_tables(mentries, s->mz);  // they fit the history rings: no longer than the plant tables' rows, which did
     const int nd = s->nd;
     s->step_md.assign((size_t)my * std::max(nd, 1) * s->tlen, 0.0);
     for (int i = 0; i < my; ++i)
@@ -790,6 +808,7 @@ inline DevScenario dev_scenario(const mpct_scenario* s, SmallTables* tb = nullpt
   ds.mz_maxa = s->mz.maxa;
   ds.fr_max = s->fr_max;
   ds.mdband = s->mdband;
+  ds.est = s->est;
   ds.rho = s->rho;
   ds.pl_maxbc = compact_taps(s->pl);
   ds.mz_maxbc = compact_taps(s->mz);

@@ -91,12 +91,14 @@ EXPORTS = [
     "mpct_scenario_table", "mpct_eval_batch", "mpct_eval_batch_device", "mpct_lds_bytes", "mpct_lds_bytes_opts",
     "mpct_nmpc_scenario_create", "mpct_eval_batch_multi", "mpct_shard_candidates", "mpct_kernel_instance",
     "mpct_rank_device", "mpct_eval_robust", "mpct_eval_robust_device", "mpct_robust_instance",
+    "mpct_scenario_create_est",
 ]
 
 ABI_VERSION = 7
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
 ST_SQP_MAXITER, ST_BOUNDS, ST_NOT_RUN = 32, 64, 128
 NMPC_VANDEVUSSE = 1
+EST_OUTPUT_BIAS = 1
 
 _lib = None
 
@@ -130,6 +132,8 @@ def load():
     lib.mpct_last_error.restype = C.c_char_p
     lib.mpct_scenario_create.argtypes = [C.POINTER(MpctScenarioDesc), C.POINTER(C.c_void_p)]
     lib.mpct_scenario_create.restype = C.c_int32
+    lib.mpct_scenario_create_est.argtypes = [C.POINTER(MpctScenarioDesc), C.c_int32, C.POINTER(C.c_void_p)]
+    lib.mpct_scenario_create_est.restype = C.c_int32
     lib.mpct_nmpc_scenario_create.argtypes = [C.POINTER(MpctNmpcDesc), C.POINTER(C.c_void_p)]
     lib.mpct_nmpc_scenario_create.restype = C.c_int32
     lib.mpct_scenario_destroy.argtypes = [C.c_void_p]

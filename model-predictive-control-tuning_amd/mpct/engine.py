@@ -30,6 +30,9 @@ class MpctError(RuntimeError):
     pass
 
 
+ESTIMATORS = {"output_bias": _lib.EST_OUTPUT_BIAS}   # Scenario(estimator=...) -> mpct_scenario_create_est's id
+
+
 class Scenario:
     """Candidate-independent description of one tuning problem (MPCTuning's Par minus N/Nu/
     delta/lambda).  ``plant``/``model`` are my x (nu+nd) lists of :class:`Tf` (scaled, discrete:
@@ -41,11 +44,15 @@ class Scenario:
     rho=1e4) of OV Min/Max, MinECR/MaxECR, ScaleFactors and Weights.ECR.  Scenarios with measured
     disturbances (nd > 0) always use that kernel (unbounded outputs when bands is None).
     ``host_carima``: False passes no CARIMA tables and lets the library derive them from the model
-    (exact LCM, what the MATLAB MEX host does; toolbox window only)."""
+    (exact LCM, what the MATLAB MEX host does; toolbox window only).
+    ``estimator``: None, or "output_bias" (band kernel only, mpct_scenario_create_est with
+    MPCT_EST_OUTPUT_BIAS): ``plant`` and ``plant_variants`` may differ from ``model``; the controller
+    corrects its prediction by the output bias b(t) = y(t) - y_model(t).  Closed loop
+    only: ``open_loop=True`` on such a scenario raises."""
 
     def __init__(self, plant, model, nu, du_min, du_max, u_min, u_max, yref, n2_max, nu_max,
                  Ts=1.0, window="toolbox", weights_squared=True, exact_carima=True, vns_ink=10,
-                 dtc=False, filters=None, dist=None, plant_variants=None, bands=None, host_carima=True):
+                 dtc=False, filters=None, dist=None, plant_variants=None, bands=None, host_carima=True, estimator=None):
         self.lib = _lib.load()
         self.plant, self.model = plant, model
         self.my, self.nin = len(model), len(model[0])
@@ -163,11 +170,19 @@ class Scenario:
             d.y_scale, d.u_scale = _dp(self.bands["y_scale"]), _dp(self.bands["u_scale"])
             d.rho_ecr = self.rho
         h = C.c_void_p()
-        rc = self.lib.mpct_scenario_create(C.byref(d), C.byref(h))
+        if estimator is not None and estimator not in ESTIMATORS:
+            raise ValueError("estimator must be None or one of %s" % sorted(ESTIMATORS))
+        self.estimator = estimator
+        if estimator is None:
+            rc, entry = self.lib.mpct_scenario_create(C.byref(d), C.byref(h)), "mpct_scenario_create"
+        else:
+            rc, entry = self.lib.mpct_scenario_create_est(C.byref(d), ESTIMATORS[estimator], C.byref(h)), \
+                "mpct_scenario_create_est"
         if rc != 0:
-            raise MpctError("mpct_scenario_create failed (%d): %s" % (rc, _lib.last_error()))
+            raise MpctError("%s failed (%d): %s" % (entry, rc, _lib.last_error()))
         self._h = h
         self._keep = keep
+        self._desc = d   # the descriptor as passed (its buffers live in _keep)
         self.n1 = n1
 
     @property

@@ -209,6 +209,57 @@ def shell7x5(n2_max=127, nu_max=15, nit=SHELL7_NIT, L=SHELL7_L, R=SHELL7_R):
     return sc, r, v, yref
 
 
+# Shell7x5.m:46-62 "model error case": the simulated plant's gains are K + DK * e_j (column j of
+# [Gr Dr], the two disturbance columns included)
+SHELL7_DK = np.array([[2.11, 0.39, 0.59, 0.12, 0.16], [3.29, 0.57, 0.89, 0.13, 0.13],
+                      [2.29, 0.35, 0.67, 0.08, 0.08], [2.34, 0.24, 0.32, 0.02, 0.04],
+                      [1.71, 0.93, 0.30, 0.03, 0.02], [2.39, 0.35, 0.72, 0.08, 0.01],
+                      [3.11, 0.73, 1.33, 0.18, 0.10]])
+SHELL7_EMAX = (0.2, 0.2, 0.3, 0.5, 0.5)   # Shell7x5.m:41 (nominal = false)
+
+
+def shell7x5_mc_plants(draws, seed=20250307, e_max=SHELL7_EMAX, max_dshift=0, L=SHELL7_L, R=SHELL7_R):
+    """Plant-mismatch draws around Shell7x5.m's model error case (:38-63): gains K[i, j] + DK[i, j] * e_j
+    over all five columns of [Gr Dr], time constants and delays of the nominal model, scaled by L, R
+    like shell7x5_plant.  Draw 0 is the reference's case, e = e_max exactly (and no delay shift); draws
+    k >= 1 take e_j ~ U(-e_max_j, e_max_j) from numpy default_rng(seed), five numbers per draw.
+    max_dshift > 0 adds U{0..max_dshift} * Ts to every entry's delay of the draws k >= 1, drawn from a
+    stream of its own (default_rng([seed, 1])), so the gains are the same for every max_dshift.
+    e = 0 gives shell7x5_plant.  Returns a list of 7x5 plants (mpct.lti.Tf)."""
+    e_max = np.broadcast_to(np.asarray(e_max, dtype=float), (5,))
+    rng = np.random.default_rng(seed)
+    rng_d = np.random.default_rng([seed, 1]) if max_dshift > 0 else None
+    out = []
+    for k in range(draws):
+        e = e_max if k == 0 else rng.uniform(-e_max, e_max)
+        sh = np.zeros((7, 5), dtype=int) if k == 0 or rng_d is None else rng_d.integers(0, max_dshift + 1, (7, 5))
+        out.append([[c2d([SHELL7_K[i, j] + SHELL7_DK[i, j] * e[j]], [SHELL7_TAU[i, j], 1.0], SHELL7_TS,
+                         SHELL7_DELAY[i, j] + sh[i, j] * SHELL7_TS).scale(L[i] * R[j])
+                     for j in range(5)] for i in range(7)])
+    return out
+
+
+def shell7x5_mc(draws=8, n2_max=127, nu_max=15, nit=SHELL7_NIT, seed=20250307, e_max=SHELL7_EMAX, max_dshift=0,
+                L=SHELL7_L, R=SHELL7_R):
+    """The Shell 7x5 band loop of shell7x5() over `draws` mismatched plants (shell7x5_mc_plants; variant
+    k runs with signal row k): the controller keeps the nominal model [Gs Ds] and corrects its
+    prediction by the output-bias estimator (Shell7x5.m:302-303 simulates with options.Model = plant;
+    the toolbox's own estimator is not restated); bounds, bands and Yref are those of
+    shell7x5().  Returns (Scenario, r [draws, 7, nit], v [draws, 2, nit], yref, plants)."""
+    P = shell7x5_plant(L, R)
+    plants = shell7x5_mc_plants(draws, seed, e_max, max_dshift, L, R)
+    r, v, yref = shell7x5_signals(nit, L=L, R=R)
+    umx = 0.5 / R[:3]
+    yr = 2 * SHELL7_YMX
+    bands = dict(y_min=-L * SHELL7_YMX, y_max=L * SHELL7_YMX, ecr_min=SHELL7_ECR, ecr_max=SHELL7_ECR,
+                 y_scale=np.where(yr != 1.0, L * yr, yr), u_scale=np.ones(3), rho=1e4)
+    inf = np.full(3, np.inf)
+    sc = Scenario(plants[0], P, nu=3, du_min=-inf, du_max=inf, u_min=-umx, u_max=umx, yref=yref,
+                  n2_max=n2_max, nu_max=nu_max, Ts=SHELL7_TS, window="toolbox", bands=bands,
+                  plant_variants=plants, estimator="output_bias")
+    return sc, np.broadcast_to(r, (draws, 7, nit)).copy(), np.broadcast_to(v, (draws, 2, nit)).copy(), yref, plants
+
+
 # ---------------------------------------------------------------------------------------------
 # WoodBerry.m (toolbox MPC, caso = 1, nominal, rest = true): [Gs Ds] with one measured
 # disturbance, Ts = 1, nit = 400.  The reference commits no WoodBerry tuning .mat, so CondMin's
@@ -237,3 +288,39 @@ def woodberry_toolbox(n2_max=30, nu_max=10, nit=400, caso=1, L=np.ones(2), R=np.
     sc = Scenario(P, P, nu=2, du_min=-0.05 / Ru, du_max=0.05 / Ru, u_min=-0.5 / Ru, u_max=0.5 / Ru,
                   yref=L[:, None] * Yref, n2_max=n2_max, nu_max=nu_max, Ts=1.0, window="toolbox")
     return sc, L[:, None] * X, mdv / R[2:, None], L[:, None] * Yref
+
+
+WB_DELTAK, WB_DELTAL = 0.2, 1.0   # WoodBerry.m:40-41 (nominal = false)
+
+
+def woodberry_mc_plants(draws, seed=20250307, dk_max=WB_DELTAK, max_dshift=int(WB_DELTAL), L=np.ones(2), R=np.ones(3)):
+    """Plant-mismatch draws around WoodBerry.m's model error case (:34-46): the MV gains of Gs times
+    (1 + dk) and the MV delays plus dL samples, the disturbance column Ds unchanged.  Draw 0 is the
+    reference's case (dk = dk_max, dL = max_dshift); draws k >= 1 take dk ~ U(-dk_max, dk_max) from
+    numpy default_rng(seed) and dL ~ U{0..max_dshift} from default_rng([seed, 1]), one number each
+    per draw.  dk_max = 0, max_dshift = 0 gives the nominal plant.  Returns a list of 2x3 plants."""
+    rng = np.random.default_rng(seed)
+    rng_d = np.random.default_rng([seed, 1])
+    out = []
+    for k in range(draws):
+        dk = dk_max if k == 0 else rng.uniform(-dk_max, dk_max)
+        dl = max_dshift if k == 0 else int(rng_d.integers(0, max_dshift + 1))
+        out.append([[c2d([WB_K[i, j] * (1.0 + (dk if j < 2 else 0.0))], [WB_TAU[i, j], 1.0], 1.0,
+                         WB_DELAY[i, j] + (dl if j < 2 else 0)).scale(L[i] * R[j]) for j in range(3)]
+                    for i in range(2)])
+    return out
+
+
+def woodberry_toolbox_mc(draws=8, n2_max=30, nu_max=10, nit=400, caso=1, seed=20250307, dk_max=WB_DELTAK,
+                         max_dshift=int(WB_DELTAL), L=np.ones(2), R=np.ones(3)):
+    """WoodBerry.m's toolbox MPC of woodberry_toolbox() over `draws` mismatched plants
+    (woodberry_mc_plants; WoodBerry.m:272-273 simulates with options.Model = plant): nominal model,
+    output-bias estimator.  Returns (Scenario, r [draws, 2, nit], v [draws, 1, nit], yref, plants)."""
+    one, r, v, yref = woodberry_toolbox(n2_max, nu_max, nit, caso, L, R)
+    plants = woodberry_mc_plants(draws, seed, dk_max, max_dshift, L, R)
+    Ru = R[:2]
+    sc = Scenario(plants[0], one.model, nu=2, du_min=-0.05 / Ru, du_max=0.05 / Ru, u_min=-0.5 / Ru, u_max=0.5 / Ru,
+                  yref=yref, n2_max=n2_max, nu_max=nu_max, Ts=1.0, window="toolbox", plant_variants=plants,
+                  estimator="output_bias")
+    one.close()
+    return sc, np.broadcast_to(r, (draws, 2, nit)).copy(), np.broadcast_to(v, (draws, 1, nit)).copy(), yref, plants

@@ -14,8 +14,17 @@ candidates x 8 plant draws through eval_robust_device, timed the same way.  With
 libmpct.so of another build, e.g. the parent commit's, loaded beside this build's in one process) the
 two libraries are the two routes, interleaved, and their records are compared.
 
+--workload shell7x5: the Shell 7x5 model-error study on the band kernel (mpct.scenarios.shell7x5_mc, output-
+bias estimator): the stratified config-3 sample (config3_stratified, 8,192 candidates) x 8 plant draws
+through eval_robust_device, interleaved with the same candidates' nominal single-draw launch
+(shell7x5, eval_batch_device) and with the nominal scenario on the same 8 signal rows (a launch of
+the same size, which fills the GPU alike) and with an estimator scenario whose 8 variants all equal
+the model (the nominal loops bit for bit, so its time over the equal-size nominal launch is what the
+second plant copy and the two-copy LDS tiers cost; the mismatched draws solve other QPs).
+
 python tools/robust_bench.py [--candidates C] [--draws D] [--reps N] [--out profiles/r07_robust_bench.json]
-python tools/robust_bench.py --workload shell3x3 [--baseline-lib PATH] [--out profiles/r08_robust_shell3x3.json]"""
+python tools/robust_bench.py --workload shell3x3 [--baseline-lib PATH] [--out profiles/r08_robust_shell3x3.json]
+python tools/robust_bench.py --workload shell7x5 [--out profiles/r09_robust_shell7x5.json]"""
 import argparse
 import json
 import os
@@ -29,7 +38,7 @@ from mpct.dtc import config4_candidates, woodberry_mc
 from mpct.engine import eval_batch_device, eval_robust_device, kernel_instance, robust_instance
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--workload", choices=("config4", "shell3x3"), default="config4")
+ap.add_argument("--workload", choices=("config4", "shell3x3", "shell7x5"), default="config4")
 ap.add_argument("--baseline-lib", default=None, help="shell3x3: another build's libmpct.so to time against")
 ap.add_argument("--candidates", type=int, default=None)
 ap.add_argument("--draws", type=int, default=None)
@@ -129,8 +138,86 @@ def shell3x3_workload():
                              "n_failed_counts": res["this_build"]["n_failed_counts"]}))
 
 
+def shell7x5_workload():
+    """The stratified config-3 sample x 8 model-error draws of Shell 7x5 through eval_robust_device
+    (band kernel + output-bias estimator), against the same candidates' nominal launch (one draw)."""
+    from mpct.scenarios import config3_grid, config3_stratified, shell7x5, shell7x5_mc
+
+    D, my = a.draws or 8, 7
+    dev = torch.device("cuda", 0)
+    idx = config3_stratified()
+    if a.candidates:
+        idx = idx[:: max(1, idx.size // a.candidates)][:a.candidates]
+    Cn = idx.size
+    N2, Nu, dl, lm = (torch.from_numpy(np.ascontiguousarray(x[idx])).to(dev) for x in config3_grid())
+    sce, r, v, _, _ = shell7x5_mc(draws=D)
+    scn, r1, v1, _ = shell7x5()
+    from mpct.engine import Scenario
+    from mpct.scenarios import shell7x5_plant
+    P = shell7x5_plant()
+    sc0 = Scenario(P, P, nu=3, du_min=scn.bounds[0], du_max=scn.bounds[1], u_min=scn.bounds[2], u_max=scn.bounds[3],
+                   yref=scn.yref, n2_max=scn.n2_max, nu_max=scn.nu_max, Ts=scn.Ts, bands=dict(scn.bands, rho=scn.rho),
+                   plant_variants=[P] * D, estimator="output_bias")
+    rd, vd = torch.from_numpy(r).to(dev), torch.from_numpy(v).to(dev)
+    r1d, v1d = torch.from_numpy(r1[None].copy()).to(dev), torch.from_numpy(v1[None].copy()).to(dev)
+    rob = dict(mean=torch.empty((Cn, my), dtype=torch.float64, device=dev),
+               worst=torch.empty((Cn, my), dtype=torch.float64, device=dev),
+               n_failed=torch.empty(Cn, dtype=torch.int32, device=dev),
+               worst_draw=torch.empty(Cn, dtype=torch.int32, device=dev),
+               status=torch.empty(Cn, dtype=torch.int32, device=dev))
+    per = dict(J1=torch.empty((Cn, my), dtype=torch.float64, device=dev), status=torch.empty(Cn, dtype=torch.int32, device=dev))
+    perd = dict(J1=torch.empty((Cn * D, my), dtype=torch.float64, device=dev),
+                status=torch.empty(Cn * D, dtype=torch.int32, device=dev))
+    run = {"robust": lambda: eval_robust_device(sce, N2, Nu, dl, lm, rd, rob, v=vd),
+           "nominal": lambda: eval_batch_device(scn, N2, Nu, dl, lm, r1d, per, v=v1d),
+           "nominal_all_rows": lambda: eval_batch_device(scn, N2, Nu, dl, lm, rd, perd, v=vd),
+           "estimator_nominal_plants": lambda: eval_batch_device(sc0, N2, Nu, dl, lm, rd, perd, v=vd)}
+    for _ in range(a.warmup):
+        for fn in run.values():
+            fn()
+    torch.cuda.synchronize()
+    t = {name: [] for name in run}
+    for _ in range(a.reps):
+        for name, fn in run.items():
+            t[name].append(timed(fn))
+    torch.cuda.synchronize()
+    o = {k: x.cpu().numpy() for k, x in rob.items()}
+    st, cnt = np.unique(o["status"], return_counts=True)
+    nf, ncnt = np.unique(o["n_failed"], return_counts=True)
+    pst, pcnt = np.unique(per["status"].cpu().numpy(), return_counts=True)
+    mr, mn, mnd = (float(np.median(t[k])) for k in ("robust", "nominal", "nominal_all_rows"))
+    n2c, nuc = int(N2.max()), int(Nu.max())
+    res = {"tool": "tools/robust_bench.py --workload shell7x5",
+           "workload": "Shell 7x5 model-error draws (shell7x5_mc): stratified config-3 sample x plant draws, nit = 200",
+           "device": torch.cuda.get_device_name(0), "candidates": Cn, "draws": D, "nit": 200, "warmup": a.warmup,
+           "reps": a.reps, "timing": "HIP events around each call, the two routes interleaved", "j_bound": JB,
+           "robust": dict(stats(t["robust"]), instance=robust_instance(sce), per_simulation_instance=kernel_instance(sce),
+                          sims_per_s=float(Cn * D / (mr * 1e-3)), lds_bytes_at_largest=sce.lds_bytes(n2c, nuc, costs_only=True),
+                          status_counts={str(int(k)): int(x) for k, x in zip(st, cnt)},
+                          n_failed_counts={str(int(k)): int(x) for k, x in zip(nf, ncnt)},
+                          candidates_without_failed_draw=int(np.count_nonzero(o["n_failed"] == 0))),
+           "nominal": dict(stats(t["nominal"]), instance=kernel_instance(scn), sims_per_s=float(Cn / (mn * 1e-3)),
+                           lds_bytes_at_largest=scn.lds_bytes(n2c, nuc, costs_only=True),
+                           status_counts={str(int(k)): int(x) for k, x in zip(pst, pcnt)}),
+           "nominal_all_rows": dict(stats(t["nominal_all_rows"]), instance=kernel_instance(scn),
+                                    sims_per_s=float(Cn * D / (mnd * 1e-3))),
+           "estimator_nominal_plants": dict(stats(t["estimator_nominal_plants"]), instance=kernel_instance(sc0)),
+           "estimator_overhead_ratio": float(np.median(t["estimator_nominal_plants"]) / mnd),
+           "per_simulation_ratio_robust_over_nominal": (mr / (Cn * D)) / (mn / Cn),
+           "per_simulation_ratio_robust_over_nominal_all_rows": mr / mnd}
+    write(res, "r09_robust_shell7x5.json")
+    print(json.dumps({"robust_median_ms": mr, "nominal_median_ms": mn,
+                      "nominal_all_rows_median_ms": mnd, "estimator_overhead_ratio": res["estimator_overhead_ratio"],
+                      "per_simulation_ratio": res["per_simulation_ratio_robust_over_nominal"],
+                      "per_simulation_ratio_equal_size": res["per_simulation_ratio_robust_over_nominal_all_rows"],
+                      "n_failed_counts": res["robust"]["n_failed_counts"], "instance": res["robust"]["instance"]}))
+
+
 if a.workload == "shell3x3":
     shell3x3_workload()
+    sys.exit(0)
+if a.workload == "shell7x5":
+    shell7x5_workload()
     sys.exit(0)
 
 Cn, D, my = a.candidates or 10000, a.draws or 32, 2
