@@ -351,30 +351,44 @@ static mxArray* out_signals(const double* p, long S, int rows, int nit) {
   return a;
 }
 
+/* the batch arguments both eval commands read from prhs[a0..]: N2, Nu, delta, lambda, r [, v] */
+typedef struct {
+  mpct_scenario* s;
+  int my, nu, nit, nref;
+  long C;
+  int32_t *N2, *Nu;
+  double *delta, *lambda, *r, *v;
+} batch_args;
+
+static batch_args read_batch(int nrhs, const mxArray* prhs[], int a0) {
+  batch_args b = {0};
+  int nv;
+  b.s = handle(prhs[1]);
+  dims_of(b.s, &b.my, &b.nu, &nv, &b.nit);
+  b.C = (long)mxGetNumberOfElements(prhs[a0]);
+  b.N2 = ints(prhs[a0], -1, "N2");
+  b.Nu = ints(prhs[a0 + 1], b.C, "Nu");
+  b.delta = rows_of(prhs[a0 + 2], b.C, b.my, "delta");
+  b.lambda = rows_of(prhs[a0 + 3], b.C, b.nu, "lambda");
+  /* r and v are checked against the scenario's own my x nit and (nd + nq) x nit before anything
+   * is allocated: the library reads nref*my*nit and nref*(nd+nq)*nit doubles from them */
+  b.r = signals(prhs[a0 + 4], b.my, b.nit, &b.nref, "r");
+  const mxArray* va = nrhs > a0 + 5 ? prhs[a0 + 5] : NULL;
+  if (nv > 0) {
+    if (!va || mxIsEmpty(va)) mexErrMsgIdAndTxt("mpct:arg", "'v' must be %d x %d (x nref)", nv, b.nit);
+    b.v = signals(va, nv, b.nit, &b.nref, "v"); /* nv x nit, 1 or nref pages (broadcast) */
+  } else if (va && !mxIsEmpty(va)) {
+    mexErrMsgIdAndTxt("mpct:arg", "'v' given but the scenario has no disturbance inputs");
+  }
+  return b;
+}
+
 static void cmd_eval(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[], int multi) {
   const int a0 = multi ? 3 : 2; /* first candidate argument */
   if (nrhs < a0 + 5) mexErrMsgIdAndTxt("mpct:arg", "usage: mpct_mex('%s', h,%s N2, Nu, delta, lambda, r [, v, opts])",
                                        multi ? "eval_multi" : "eval", multi ? " devices," : "");
-  mpct_scenario* s = handle(prhs[1]);
-  int my, nu, nv, nit;
-  dims_of(s, &my, &nu, &nv, &nit);
-  const long C = (long)mxGetNumberOfElements(prhs[a0]);
-  int32_t* N2 = ints(prhs[a0], -1, "N2");
-  int32_t* Nu = ints(prhs[a0 + 1], C, "Nu");
-  double* delta = rows_of(prhs[a0 + 2], C, my, "delta");
-  double* lambda = rows_of(prhs[a0 + 3], C, nu, "lambda");
-  /* r and v are checked against the scenario's own my x nit and (nd + nq) x nit before anything
-   * is allocated: the library reads nref*my*nit and nref*(nd+nq)*nit doubles from them */
-  int nref = 0;
-  double* r = signals(prhs[a0 + 4], my, nit, &nref, "r");
-  const mxArray* va = nrhs > a0 + 5 ? prhs[a0 + 5] : NULL;
-  double* v = NULL;
-  if (nv > 0) {
-    if (!va || mxIsEmpty(va)) mexErrMsgIdAndTxt("mpct:arg", "'v' must be %d x %d (x nref)", nv, nit);
-    v = signals(va, nv, nit, &nref, "v"); /* nv x nit, 1 or nref pages (broadcast) */
-  } else if (va && !mxIsEmpty(va)) {
-    mexErrMsgIdAndTxt("mpct:arg", "'v' given but the scenario has no disturbance inputs");
-  }
+  const batch_args b = read_batch(nrhs, prhs, a0);
+  const int my = b.my, nu = b.nu, nit = b.nit;
   mpct_opts o = read_opts(nrhs > a0 + 6 ? prhs[a0 + 6] : NULL);
   int32_t* devs = NULL;
   int ndev = 0;
@@ -382,7 +396,7 @@ static void cmd_eval(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[],
     ndev = (int)mxGetNumberOfElements(prhs[2]);
     devs = ints(prhs[2], -1, "devices");
   }
-  const long S = C * nref;
+  const long C = b.C, S = C * b.nref;
   const int traj = o.want_traj != 0, ol = o.open_loop != 0;
   mpct_result res;
   memset(&res, 0, sizeof res);
@@ -400,8 +414,8 @@ static void cmd_eval(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[],
       res.uopt = (double*)mxCalloc((size_t)(S * nu * nit + 1), sizeof(double));
     }
   }
-  const int rc = multi ? mpct_eval_batch_multi(s, ndev, devs, C, N2, Nu, delta, lambda, nref, r, v, &o, &res)
-                       : mpct_eval_batch(s, C, N2, Nu, delta, lambda, nref, r, v, &o, &res);
+  const int rc = multi ? mpct_eval_batch_multi(b.s, ndev, devs, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, &o, &res)
+                       : mpct_eval_batch(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, &o, &res);
   if (rc != MPCT_OK) lib_error(multi ? "mpct:eval_multi" : "mpct:eval");
   mxArray* outs[10] = {NULL};
   outs[0] = out_rows(res.J1, S, my);
@@ -428,26 +442,10 @@ static void cmd_eval(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[],
 /* R = mpct_mex('eval_robust', h, N2, Nu, delta, lambda, r [, v, j_bound]) */
 static void cmd_eval_robust(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (nrhs < 7) mexErrMsgIdAndTxt("mpct:arg", "usage: R = mpct_mex('eval_robust', h, N2, Nu, delta, lambda, r [, v, j_bound])");
-  mpct_scenario* s = handle(prhs[1]);
-  int my, nu, nv, nit;
-  dims_of(s, &my, &nu, &nv, &nit);
-  const long C = (long)mxGetNumberOfElements(prhs[2]);
-  int32_t* N2 = ints(prhs[2], -1, "N2");
-  int32_t* Nu = ints(prhs[3], C, "Nu");
-  double* delta = rows_of(prhs[4], C, my, "delta");
-  double* lambda = rows_of(prhs[5], C, nu, "lambda");
-  int nref = 0;
-  double* r = signals(prhs[6], my, nit, &nref, "r");
-  const mxArray* va = nrhs > 7 ? prhs[7] : NULL;
-  double* v = NULL;
-  if (nv > 0) {
-    if (!va || mxIsEmpty(va)) mexErrMsgIdAndTxt("mpct:arg", "'v' must be %d x %d (x nref)", nv, nit);
-    v = signals(va, nv, nit, &nref, "v");
-  } else if (va && !mxIsEmpty(va)) {
-    mexErrMsgIdAndTxt("mpct:arg", "'v' given but the scenario has no disturbance inputs");
-  }
+  const batch_args b = read_batch(nrhs, prhs, 2);
+  const int my = b.my;
   const double j_bound = (nrhs > 8 && !mxIsEmpty(prhs[8])) ? scalar(prhs[8], "j_bound") : 0.0;
-  const long S = C * nref;
+  const long C = b.C, S = C * b.nref;
   mpct_robust_result res;
   res.mean = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
   res.worst = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
@@ -456,7 +454,7 @@ static void cmd_eval_robust(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   res.status = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
   res.J1 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
   mpct_opts o = read_opts(NULL);
-  if (mpct_eval_robust(s, C, N2, Nu, delta, lambda, nref, r, v, j_bound, &o, &res) != MPCT_OK) lib_error("mpct:eval_robust");
+  if (mpct_eval_robust(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, &res) != MPCT_OK) lib_error("mpct:eval_robust");
   const char* names[6] = {"mean", "worst", "n_failed", "worst_draw", "status", "J1"};
   mxArray* R = mxCreateStructMatrix(1, 1, 6, names);
   mxSetField(R, 0, "mean", out_rows(res.mean, C, my));

@@ -93,9 +93,6 @@ extern "C" int32_t mpct_scenario_create(const mpct_scenario_desc* d, mpct_scenar
 extern "C" int32_t mpct_scenario_create_est(const mpct_scenario_desc* d, int32_t estimator, mpct_scenario** out) {
   if (!d || !out) return fail(MPCT_EINVAL, "null argument");
   *out = nullptr;
-  if (estimator != 0 && estimator != MPCT_EST_OUTPUT_BIAS) return fail(MPCT_EINVAL, "unknown estimator id");
-  if (estimator && !(d->abi_version >= 3 && d->mdband))
-    return fail(MPCT_EINVAL, "the output-bias estimator belongs to the band kernel (mdband = 1)");
   BuildError err;
   return created(build_scenario(*d, &err, estimator), err, out);
 }
@@ -358,6 +355,102 @@ extern "C" int32_t mpct_rank_device(const double* costs, int64_t C, int32_t k, c
   return MPCT_OK;
 }
 
+// Host-pointer staging of one call on the context's own stream, shared by eval_host and
+// mpct_eval_robust: the candidates go into the grow-only scratch blob, the signals r | v through
+// the context's signal cache, the results come back from slots of the same blob.  An entry
+// reserves its result slots, calls upload(), launches on cx->stream, fetch()es and finish()es.
+namespace {
+struct HostStage {
+  DevCtx* cx;
+  hipStream_t st;
+  int64_t C;
+  int my, nu;
+  size_t off = 0;
+  size_t o_N2, o_Nu, o_d, o_l;            // the candidates' slots
+  const double *r = nullptr, *v = nullptr;  // the signals on the device, after upload()
+  bool fetched = true;
+
+  HostStage(const mpct_scenario* s, DevCtx* c, int64_t ncand) : cx(c), st(c->stream), C(ncand), my(s->my), nu(s->nu) {
+    o_N2 = slot(C * 4), o_Nu = slot(C * 4), o_d = slot(C * my * 8), o_l = slot(C * nu * 8);
+  }
+  // reserve a 256-B-aligned slot of the blob; its address holds after upload()
+  size_t slot(size_t bytes) {
+    const size_t o = off;
+    off += (bytes + 255) & ~(size_t)255;
+    return o;
+  }
+  template <class T>
+  T* at(size_t o) const { return reinterpret_cast<T*>(static_cast<char*>(cx->dscratch) + o); }
+  const int32_t* N2() const { return at<int32_t>(o_N2); }
+  const int32_t* Nu() const { return at<int32_t>(o_Nu); }
+  const double* delta() const { return at<double>(o_d); }
+  const double* lambda() const { return at<double>(o_l); }
+
+  // `*buf` holds at least `bytes`: a regrow waits for the stream's work on the old buffer first
+  int ensure(void** buf, size_t* have, size_t bytes, const char* what) {
+    if (bytes <= *have) return MPCT_OK;
+    if (*buf) {
+      (void)hipStreamSynchronize(st);
+      (void)hipFree(*buf);
+    }
+    *buf = nullptr;
+    *have = 0;
+    if (hipMalloc(buf, bytes) != hipSuccess) return fail(MPCT_ENOMEM, std::string("hipMalloc(") + what + ") failed");
+    *have = bytes;
+    return MPCT_OK;
+  }
+
+  // every slot reserved: size the blob and enqueue the H2D copies of the candidates and signals
+  int upload(const mpct_scenario* s, const int32_t* hN2, const int32_t* hNu, const double* hdelta, const double* hlambda,
+             int32_t nref, const double* hr, const double* hv) {
+    int rc = ensure(&cx->dscratch, &cx->dscratch_bytes, off, "scratch");
+    if (rc) return rc;
+    // signals r | v: uploaded only when they differ from what the context's signal buffer holds
+    const size_t rb = (size_t)nref * my * s->nit * 8, vb = (size_t)nref * (s->nd + s->nq) * s->nit * 8;
+    const bool same_sig = cx->sig_host.size() == rb + vb && std::memcmp(cx->sig_host.data(), hr, rb) == 0 &&
+                          (vb == 0 || std::memcmp(cx->sig_host.data() + rb, hv, vb) == 0);
+    if (!same_sig) {
+      if (rb + vb > cx->dsig_bytes) cx->sig_host.clear();
+      rc = ensure(&cx->dsig, &cx->dsig_bytes, rb + vb, "signals");
+      if (rc) return rc;
+      cx->sig_host.assign(reinterpret_cast<const char*>(hr), reinterpret_cast<const char*>(hr) + rb);
+      if (vb) cx->sig_host.insert(cx->sig_host.end(), reinterpret_cast<const char*>(hv), reinterpret_cast<const char*>(hv) + vb);
+    }
+    auto h2d = [&](const void* dst, const void* p, size_t bytes) {
+      return bytes == 0 || hipMemcpyAsync(const_cast<void*>(dst), p, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
+    };
+    // the signals are copied from the context's own host copy (the caller's buffers may change
+    // after the call returns; an earlier launch reading dsig is ordered before this copy on st)
+    if (!h2d(N2(), hN2, C * 4) || !h2d(Nu(), hNu, C * 4) || !h2d(delta(), hdelta, C * my * 8) ||
+        !h2d(lambda(), hlambda, C * nu * 8) || (!same_sig && !h2d(cx->dsig, cx->sig_host.data(), rb + vb))) {
+      // copies enqueued before the failing one may still read the caller's buffers
+      (void)hipStreamSynchronize(st);
+      cx->sig_host.clear();
+      return fail(MPCT_EDEVICE, "hipMemcpyAsync(inputs) failed");
+    }
+    r = static_cast<const double*>(cx->dsig);
+    v = vb ? reinterpret_cast<const double*>(static_cast<const char*>(cx->dsig) + rb) : nullptr;
+    return MPCT_OK;
+  }
+
+  // a failed launch: nothing of this call stays in flight
+  int abandon(int rc) {
+    (void)hipStreamSynchronize(st);
+    return rc;
+  }
+  // enqueue the D2H copy of slot o into the caller's dst (skipped when the caller passed none)
+  void fetch(void* dst, size_t o, size_t bytes) {
+    if (dst && bytes) fetched = hipMemcpyAsync(dst, at<char>(o), bytes, hipMemcpyDeviceToHost, st) == hipSuccess && fetched;
+  }
+  int finish() {
+    const hipError_t se = hipStreamSynchronize(st);
+    if (se != hipSuccess) return fail(MPCT_EDEVICE, std::string("kernel execution failed: ") + hipGetErrorString(se));
+    if (!fetched) return fail(MPCT_EDEVICE, "hipMemcpyAsync(results) failed");
+    return MPCT_OK;
+  }
+};
+}  // namespace
+
 // host buffers in, host buffers out, on the context's own stream: H2D of the candidates and
 // signals, the launch, D2H of the results, then a wait on that stream only
 static int eval_host(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2, const int32_t* Nu,
@@ -365,103 +458,37 @@ static int eval_host(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2,
                      const mpct_opts* opts, mpct_result* out) {
   if (hipSetDevice(cx->dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
   if (C == 0) return MPCT_OK;
-  const int my = s->my, nu = s->nu, nd = s->nd, nit = s->nit;
-  const int64_t S = C * nref;
+  const int my = s->my, nu = s->nu, nit = s->nit;
+  const size_t S = (size_t)(C * nref), yb = S * my * nit * 8, ub = S * nu * nit * 8;
   const bool traj = opts && opts->want_traj;
-  const bool ol = opts && opts->open_loop;
-  hipStream_t st = cx->stream;
-  // device scratch layout
-  size_t off = 0;
-  auto slot = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  size_t o_N2 = slot(C * 4), o_Nu = slot(C * 4), o_d = slot(C * my * 8), o_l = slot(C * nu * 8);
-  size_t o_J1 = slot(S * my * 8), o_j21 = slot(S * my * 8), o_j22 = slot(S * my * 8), o_Jnu = slot(S * nu * 8);
-  size_t o_st = slot(S * 4), o_it = slot(S * 8);
-  size_t o_y = traj ? slot(S * my * nit * 8) : 0, o_u = traj ? slot(S * nu * nit * 8) : 0;
-  size_t o_ys = (traj && ol) ? slot(S * my * nit * 8) : 0, o_uo = (traj && ol) ? slot(S * nu * nit * 8) : 0;
-  if (off > cx->dscratch_bytes) {
-    if (cx->dscratch) {
-      (void)hipStreamSynchronize(st);
-      (void)hipFree(cx->dscratch);
-    }
-    cx->dscratch = nullptr;
-    cx->dscratch_bytes = 0;
-    if (hipMalloc(&cx->dscratch, off) != hipSuccess) return fail(MPCT_ENOMEM, "hipMalloc(scratch) failed");
-    cx->dscratch_bytes = off;
-  }
-  char* b = static_cast<char*>(cx->dscratch);
-  auto h2d = [&](void* dst, const void* p, size_t bytes) {
-    return bytes == 0 || hipMemcpyAsync(dst, p, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
-  };
-  // signals r | v: uploaded only when they differ from what the context's signal buffer holds
-  const size_t rb = (size_t)nref * my * nit * 8, vb = (size_t)nref * (nd + s->nq) * nit * 8;
-  const bool same_sig = cx->sig_host.size() == rb + vb && std::memcmp(cx->sig_host.data(), r, rb) == 0 &&
-                        (vb == 0 || std::memcmp(cx->sig_host.data() + rb, v, vb) == 0);
-  if (!same_sig) {
-    if (rb + vb > cx->dsig_bytes) {
-      if (cx->dsig) {
-        (void)hipStreamSynchronize(st);
-        (void)hipFree(cx->dsig);
-      }
-      cx->dsig = nullptr;
-      cx->dsig_bytes = 0;
-      cx->sig_host.clear();
-      if (hipMalloc(&cx->dsig, rb + vb) != hipSuccess) return fail(MPCT_ENOMEM, "hipMalloc(signals) failed");
-      cx->dsig_bytes = rb + vb;
-    }
-    cx->sig_host.assign(reinterpret_cast<const char*>(r), reinterpret_cast<const char*>(r) + rb);
-    if (vb) cx->sig_host.insert(cx->sig_host.end(), reinterpret_cast<const char*>(v), reinterpret_cast<const char*>(v) + vb);
-  }
-  char* sg = static_cast<char*>(cx->dsig);
-  // the signals are copied from the context's own host copy (the caller's buffers may change
-  // after the call returns; an earlier launch reading dsig is ordered before this copy on st)
-  if (!h2d(b + o_N2, N2, C * 4) || !h2d(b + o_Nu, Nu, C * 4) || !h2d(b + o_d, delta, C * my * 8) ||
-      !h2d(b + o_l, lambda, C * nu * 8) || (!same_sig && !h2d(sg, cx->sig_host.data(), rb + vb))) {
-    // copies enqueued before the failing one may still read the caller's buffers
-    (void)hipStreamSynchronize(st);
-    cx->sig_host.clear();
-    return fail(MPCT_EDEVICE, "hipMemcpyAsync(inputs) failed");
-  }
+  const bool ol = traj && opts->open_loop;
+  HostStage hs(s, cx, C);
+  const size_t o_J1 = hs.slot(S * my * 8), o_j21 = hs.slot(S * my * 8), o_j22 = hs.slot(S * my * 8);
+  const size_t o_Jnu = hs.slot(S * nu * 8), o_st = hs.slot(S * 4), o_it = hs.slot(S * 8);
+  const size_t o_y = traj ? hs.slot(yb) : 0, o_u = traj ? hs.slot(ub) : 0;
+  const size_t o_ys = ol ? hs.slot(yb) : 0, o_uo = ol ? hs.slot(ub) : 0;
+  int rc = hs.upload(s, N2, Nu, delta, lambda, nref, r, v);
+  if (rc) return rc;
   mpct_result dres{};
-  dres.J1 = reinterpret_cast<double*>(b + o_J1);
-  dres.j21 = reinterpret_cast<double*>(b + o_j21);
-  dres.j22 = reinterpret_cast<double*>(b + o_j22);
-  dres.Jnu = reinterpret_cast<double*>(b + o_Jnu);
-  dres.status = reinterpret_cast<int32_t*>(b + o_st);
-  dres.qp_iters = reinterpret_cast<int64_t*>(b + o_it);
-  if (traj) {
-    dres.y = reinterpret_cast<double*>(b + o_y);
-    dres.u = reinterpret_cast<double*>(b + o_u);
-    if (ol) {
-      dres.ys = reinterpret_cast<double*>(b + o_ys);
-      dres.uopt = reinterpret_cast<double*>(b + o_uo);
-    }
-  }
-  int rc = launch_batch(s, cx, C, reinterpret_cast<const int32_t*>(b + o_N2), reinterpret_cast<const int32_t*>(b + o_Nu),
-                        reinterpret_cast<const double*>(b + o_d), reinterpret_cast<const double*>(b + o_l), nref,
-                        reinterpret_cast<const double*>(sg),
-                        nd + s->nq > 0 ? reinterpret_cast<const double*>(sg + rb) : nullptr, opts, &dres, st);
-  if (rc) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
-  auto d2h = [&](void* dst, const void* src, size_t bytes) {
-    return !dst || bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
-  };
-  bool ok = d2h(out->J1, dres.J1, S * my * 8) && d2h(out->j21, dres.j21, S * my * 8) &&
-            d2h(out->j22, dres.j22, S * my * 8) && d2h(out->Jnu, dres.Jnu, S * nu * 8) &&
-            d2h(out->status, dres.status, S * 4) && d2h(out->qp_iters, dres.qp_iters, S * 8);
-  if (traj) {
-    ok = ok && d2h(out->y, dres.y, S * my * nit * 8) && d2h(out->u, dres.u, S * nu * nit * 8);
-    if (ol) ok = ok && d2h(out->ys, dres.ys, S * my * nit * 8) && d2h(out->uopt, dres.uopt, S * nu * nit * 8);
-  }
-  const hipError_t se = hipStreamSynchronize(st);
-  if (se != hipSuccess) return fail(MPCT_EDEVICE, std::string("kernel execution failed: ") + hipGetErrorString(se));
-  if (!ok) return fail(MPCT_EDEVICE, "hipMemcpyAsync(results) failed");
-  return MPCT_OK;
+  dres.J1 = hs.at<double>(o_J1);
+  dres.j21 = hs.at<double>(o_j21);
+  dres.j22 = hs.at<double>(o_j22);
+  dres.Jnu = hs.at<double>(o_Jnu);
+  dres.status = hs.at<int32_t>(o_st);
+  dres.qp_iters = hs.at<int64_t>(o_it);
+  if (traj) dres.y = hs.at<double>(o_y), dres.u = hs.at<double>(o_u);
+  if (ol) dres.ys = hs.at<double>(o_ys), dres.uopt = hs.at<double>(o_uo);
+  rc = launch_batch(s, cx, C, hs.N2(), hs.Nu(), hs.delta(), hs.lambda(), nref, hs.r, hs.v, opts, &dres, hs.st);
+  if (rc) return hs.abandon(rc);
+  hs.fetch(out->J1, o_J1, S * my * 8);
+  hs.fetch(out->j21, o_j21, S * my * 8);
+  hs.fetch(out->j22, o_j22, S * my * 8);
+  hs.fetch(out->Jnu, o_Jnu, S * nu * 8);
+  hs.fetch(out->status, o_st, S * 4);
+  hs.fetch(out->qp_iters, o_it, S * 8);
+  if (traj) hs.fetch(out->y, o_y, yb), hs.fetch(out->u, o_u, ub);
+  if (ol) hs.fetch(out->ys, o_ys, yb), hs.fetch(out->uopt, o_uo, ub);
+  return hs.finish();
 }
 
 extern "C" int32_t mpct_eval_batch(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
@@ -710,65 +737,30 @@ extern "C" int32_t mpct_eval_robust(mpct_scenario* s, int64_t C, const int32_t* 
   rc = device_ctx(s, opts ? opts->device : -1, &cx);
   if (rc) return rc;
   if (C == 0) return MPCT_OK;
-  // host buffers in, host buffers out on the context's own stream (as eval_host): one scratch blob
-  const int my = s->my, nu = s->nu, nit = s->nit, nv = s->nd + s->nq;
-  const int64_t S = C * nref;
-  hipStream_t st = cx->stream;
-  size_t off = 0;
-  auto slot = [&](size_t bytes) {
-    size_t o = off;
-    off += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  const size_t rb = (size_t)nref * my * nit * 8, vb = (size_t)nref * nv * nit * 8;
-  const size_t o_N2 = slot(C * 4), o_Nu = slot(C * 4), o_d = slot(C * my * 8), o_l = slot(C * nu * 8);
-  const size_t o_r = slot(rb), o_v = slot(vb);
-  const size_t o_mean = slot(C * my * 8), o_worst = slot(C * my * 8), o_nf = slot(C * 4), o_wd = slot(C * 4);
-  const size_t o_st = slot(C * 4), o_J1 = out->J1 ? slot(S * my * 8) : 0;
-  if (off > cx->dscratch_bytes) {
-    if (cx->dscratch) {
-      (void)hipStreamSynchronize(st);
-      (void)hipFree(cx->dscratch);
-    }
-    cx->dscratch = nullptr;
-    cx->dscratch_bytes = 0;
-    if (hipMalloc(&cx->dscratch, off) != hipSuccess) return fail(MPCT_ENOMEM, "hipMalloc(scratch) failed");
-    cx->dscratch_bytes = off;
-  }
-  char* b = static_cast<char*>(cx->dscratch);
-  auto h2d = [&](size_t o, const void* p, size_t bytes) {
-    return bytes == 0 || hipMemcpyAsync(b + o, p, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
-  };
-  if (!h2d(o_N2, N2, C * 4) || !h2d(o_Nu, Nu, C * 4) || !h2d(o_d, delta, C * my * 8) || !h2d(o_l, lambda, C * nu * 8) ||
-      !h2d(o_r, r, rb) || !h2d(o_v, v, vb)) {
-    (void)hipStreamSynchronize(st);
-    return fail(MPCT_EDEVICE, "hipMemcpyAsync(inputs) failed");
-  }
+  // host buffers in, host buffers out on the context's own stream, staged as eval_host does
+  const int my = s->my;
+  const size_t S = (size_t)(C * nref);
+  HostStage hs(s, cx, C);
+  const size_t o_mean = hs.slot(C * my * 8), o_worst = hs.slot(C * my * 8), o_nf = hs.slot(C * 4), o_wd = hs.slot(C * 4);
+  const size_t o_st = hs.slot(C * 4), o_J1 = out->J1 ? hs.slot(S * my * 8) : 0;
+  rc = hs.upload(s, N2, Nu, delta, lambda, nref, r, v);
+  if (rc) return rc;
   mpct_robust_result dres{};
-  dres.mean = reinterpret_cast<double*>(b + o_mean);
-  dres.worst = reinterpret_cast<double*>(b + o_worst);
-  dres.n_failed = reinterpret_cast<int32_t*>(b + o_nf);
-  dres.worst_draw = reinterpret_cast<int32_t*>(b + o_wd);
-  dres.status = reinterpret_cast<int32_t*>(b + o_st);
-  dres.J1 = out->J1 ? reinterpret_cast<double*>(b + o_J1) : nullptr;
-  rc = launch_robust(s, cx, C, reinterpret_cast<const int32_t*>(b + o_N2), reinterpret_cast<const int32_t*>(b + o_Nu),
-                     reinterpret_cast<const double*>(b + o_d), reinterpret_cast<const double*>(b + o_l), nref,
-                     reinterpret_cast<const double*>(b + o_r), nv > 0 ? reinterpret_cast<const double*>(b + o_v) : nullptr,
-                     j_bound, opts, &dres, st);
-  if (rc) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
-  auto d2h = [&](void* dst, const void* src, size_t bytes) {
-    return !dst || bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess;
-  };
-  const bool ok = d2h(out->mean, dres.mean, C * my * 8) && d2h(out->worst, dres.worst, C * my * 8) &&
-                  d2h(out->n_failed, dres.n_failed, C * 4) && d2h(out->worst_draw, dres.worst_draw, C * 4) &&
-                  d2h(out->status, dres.status, C * 4) && d2h(out->J1, dres.J1, S * my * 8);
-  const hipError_t se = hipStreamSynchronize(st);
-  if (se != hipSuccess) return fail(MPCT_EDEVICE, std::string("kernel execution failed: ") + hipGetErrorString(se));
-  if (!ok) return fail(MPCT_EDEVICE, "hipMemcpyAsync(results) failed");
-  return MPCT_OK;
+  dres.mean = hs.at<double>(o_mean);
+  dres.worst = hs.at<double>(o_worst);
+  dres.n_failed = hs.at<int32_t>(o_nf);
+  dres.worst_draw = hs.at<int32_t>(o_wd);
+  dres.status = hs.at<int32_t>(o_st);
+  dres.J1 = out->J1 ? hs.at<double>(o_J1) : nullptr;
+  rc = launch_robust(s, cx, C, hs.N2(), hs.Nu(), hs.delta(), hs.lambda(), nref, hs.r, hs.v, j_bound, opts, &dres, hs.st);
+  if (rc) return hs.abandon(rc);
+  hs.fetch(out->mean, o_mean, C * my * 8);
+  hs.fetch(out->worst, o_worst, C * my * 8);
+  hs.fetch(out->n_failed, o_nf, C * 4);
+  hs.fetch(out->worst_draw, o_wd, C * 4);
+  hs.fetch(out->status, o_st, C * 4);
+  hs.fetch(out->J1, o_J1, S * my * 8);
+  return hs.finish();
 }
 
 static int32_t copy_name(const std::string& nm, char* buf, int32_t cap) {
@@ -805,13 +797,7 @@ extern "C" int32_t mpct_robust_instance(const mpct_scenario* s, const mpct_opts*
 extern "C" int32_t mpct_kernel_instance(const mpct_scenario* s, const mpct_opts* opts, char* buf, int32_t cap) {
   if (!s) return fail(MPCT_EINVAL, "null scenario");
   const bool ext = opts && (opts->open_loop || opts->want_traj);
-  const std::string nm = per_simulation_instance(s, ext);
-  if (buf && cap > 0) {
-    const size_t n = std::min<size_t>(nm.size(), (size_t)cap - 1);
-    std::memcpy(buf, nm.data(), n);
-    buf[n] = '\0';
-  }
-  return (int32_t)nm.size();
+  return copy_name(per_simulation_instance(s, ext), buf, cap);
 }
 
 static int64_t lds_bytes_ext(const mpct_scenario* s, int32_t N2, int32_t Nu, bool ext) {

@@ -223,10 +223,13 @@ inline bool z_tables(const std::vector<ZEntry>& entries, ZTables& t) {
 }
 
 // validate a linear scenario descriptor and precompute its tables (no device needed).  estimator:
-// 0 (mpct_scenario_create) or MPCT_EST_OUTPUT_BIAS on a band descriptor (mpct_scenario_create_est,
-// which checks both: the plant, and every plant variant, may then differ from the model)
+// 0 (mpct_scenario_create) or MPCT_EST_OUTPUT_BIAS on a band descriptor (mpct_scenario_create_est;
+// both checked first, here: the plant, and every plant variant, may then differ from the model)
 inline std::unique_ptr<mpct_scenario> build_scenario(const mpct_scenario_desc& d_in, BuildError* err,
                                                      int estimator = 0) {
+  if (estimator != 0 && estimator != MPCT_EST_OUTPUT_BIAS) return reject(err, MPCT_EINVAL, "unknown estimator id");
+  if (estimator && !(d_in.abi_version >= 3 && d_in.mdband))
+    return reject(err, MPCT_EINVAL, "the output-bias estimator belongs to the band kernel (mdband = 1)");
   mpct_scenario_desc dcopy = d_in;
   const mpct_scenario_desc* d = &dcopy;
   CarimaTables derived;

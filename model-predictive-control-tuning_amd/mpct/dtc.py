@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .lti import Tf, c2d, carima, descomp
+from .lti import Tf, fopdt_grid
 
 
 def _solve_mldivide(A, B):
@@ -78,30 +78,32 @@ WB_QTAU = np.array([14.9, 13.2])
 WB_QL = np.array([8.1, 3.4])
 
 
-def woodberry_dtc(n2_max: int = 30, nu_max: int = 10, nit: int = 200, deltak: float = 0.0,
-                  deltaL: float = 0.0, alfa: float = 0.7, raio: float = 0.8, filt: bool = True):
-    """DTC_GPC_WW.m:18-124 configuration (config 1) on the engine, CondMin-free (L = R = I):
-    Ts = 1, real plant P (gain/delay mismatch deltak, deltaL), nominal model Pn, disturbance
-    path Pq; unconstrained; Q = diag(delta), W = diag(lambda) unsquared; BA_MIMO's rounded LCM.
-    Returns (Scenario, r [2 x nit], q [1 x nit])."""
+def _woodberry_dtc_scenario(plant, n2_max, nu_max, nit, alfa, raio, filt=True, **kw):
+    """What woodberry_dtc and woodberry_mc share (DTC_GPC_WW.m:18-124, CondMin-free: L = R = I): Ts = 1,
+    nominal model Pn, disturbance path Pq; unconstrained; Q = diag(delta), W = diag(lambda) unsquared;
+    BA_MIMO's rounded LCM.  Returns (Scenario, r [2 x nit], q [1 x nit])."""
     from .engine import Scenario
 
-    Ts = 1.0
-    P = [[c2d([WB_K[i, j] * (1 + deltak)], [WB_TAU[i, j], 1.0], Ts, WB_L[i, j] + deltaL) for j in range(2)]
-         for i in range(2)]
-    Pn = [[c2d([WB_K[i, j]], [WB_TAU[i, j], 1.0], Ts, WB_L[i, j]) for j in range(2)] for i in range(2)]
-    Pq = [[c2d([WB_QK[i]], [WB_QTAU[i], 1.0], Ts, WB_QL[i])] for i in range(2)]
-    filters = mimofilter(Pn, alfa, raio) if filt else None
+    Pn = fopdt_grid(WB_K, WB_TAU, WB_L, 1.0)
+    Pq = fopdt_grid(WB_QK[:, None], WB_QTAU[:, None], WB_QL[:, None], 1.0)
     r = np.zeros((2, nit))
     r[0, 10:] = 0.8                                  # DTC_GPC_WW.m:117-119
     r[1, 60:] = 0.5
     q = np.zeros((1, nit))
     q[0, 140:] = -0.25                               # DTC_GPC_WW.m:123-124
     inf = np.full(2, np.inf)
-    sc = Scenario(P, Pn, nu=2, du_min=-inf, du_max=inf, u_min=-inf, u_max=inf, yref=r,
-                  n2_max=n2_max, nu_max=nu_max, Ts=Ts, window="gpc", weights_squared=False,
-                  exact_carima=False, dtc=True, filters=filters, dist=Pq)
+    sc = Scenario(plant, Pn, nu=2, du_min=-inf, du_max=inf, u_min=-inf, u_max=inf, yref=r,
+                  n2_max=n2_max, nu_max=nu_max, Ts=1.0, window="gpc", weights_squared=False,
+                  exact_carima=False, dtc=True, filters=mimofilter(Pn, alfa, raio) if filt else None, dist=Pq, **kw)
     return sc, r, q
+
+
+def woodberry_dtc(n2_max: int = 30, nu_max: int = 10, nit: int = 200, deltak: float = 0.0,
+                  deltaL: float = 0.0, alfa: float = 0.7, raio: float = 0.8, filt: bool = True):
+    """DTC_GPC_WW.m:18-124 configuration (config 1) on the engine: the real plant P is the nominal
+    model with gain/delay mismatch deltak, deltaL.  Returns (Scenario, r [2 x nit], q [1 x nit])."""
+    P = fopdt_grid(WB_K * (1 + deltak), WB_TAU, WB_L + deltaL, 1.0)
+    return _woodberry_dtc_scenario(P, n2_max, nu_max, nit, alfa, raio, filt)
 
 
 # --------------------------------------------------------------------------------------------
@@ -109,14 +111,18 @@ def woodberry_mc_plants(draws: int, seed: int = 20250307, gain_spread: float = 0
                         Ts: float = 1.0):
     """SURVEY §8d config 4 plant-mismatch draws modelled on DTC_GPC_WW.m:18-19 (deltak, deltaL):
     each entry's gain x (1 + U(-gain_spread, gain_spread)) and delay + U{0..max_dshift} * Ts,
-    numpy default_rng(seed).  Returns a list of 2x2 plants (mpct.lti.Tf)."""
+    numpy default_rng(seed).  Returns a list of 2x2 plants (mpct.lti.Tf).
+
+    Not mpct.scenarios.woodberry_mc_plants (WoodBerry.m's toolbox MPC): that one returns 2x3 plants
+    [Gs Ds], moves the whole MV block by one gain factor and one delay shift per draw, from two
+    streams, and its draw 0 is the reference's case; here every entry draws its own pair from one
+    stream and draw 0 is random like the rest."""
     rng = np.random.default_rng(seed)
     out = []
     for _ in range(draws):
         g = 1.0 + rng.uniform(-gain_spread, gain_spread, (2, 2))
         dl = rng.integers(0, max_dshift + 1, (2, 2))
-        out.append([[c2d([WB_K[i, j] * g[i, j]], [WB_TAU[i, j], 1.0], Ts, WB_L[i, j] + dl[i, j] * Ts)
-                     for j in range(2)] for i in range(2)])
+        out.append(fopdt_grid(WB_K * g, WB_TAU, WB_L + dl * Ts, Ts))
     return out
 
 
@@ -137,18 +143,8 @@ def woodberry_mc(draws: int = 32, n2_max: int = 30, nu_max: int = 10, nit: int =
     """Config 4 scenario: the DTC-GPC of woodberry_dtc evaluated over `draws` mismatched plants
     (variant k runs with reference row k).  Returns (Scenario, refs [draws, 2, nit],
     v [draws, 1, nit], plants)."""
-    from .engine import Scenario
-
-    base, r, q = woodberry_dtc(n2_max=2, nu_max=1, nit=nit)        # for r, q and the model
     plants = woodberry_mc_plants(draws, seed)
-    Pn = base.model
-    Pq = [[c2d([WB_QK[i]], [WB_QTAU[i], 1.0], 1.0, WB_QL[i])] for i in range(2)]
-    inf = np.full(2, np.inf)
-    sc = Scenario(plants[0], Pn, nu=2, du_min=-inf, du_max=inf, u_min=-inf, u_max=inf, yref=r,
-                  n2_max=n2_max, nu_max=nu_max, Ts=1.0, window="gpc", weights_squared=False,
-                  exact_carima=False, dtc=True, filters=mimofilter(Pn, alfa, raio), dist=Pq,
-                  plant_variants=plants)
-    base.close()
+    sc, r, q = _woodberry_dtc_scenario(plants[0], n2_max, nu_max, nit, alfa, raio, plant_variants=plants)
     refs = np.broadcast_to(r, (draws, 2, nit)).copy()
     v = np.broadcast_to(q, (draws, 1, nit)).copy()
     return sc, refs, v, plants

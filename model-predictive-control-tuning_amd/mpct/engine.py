@@ -26,6 +26,34 @@ def _ip(a):
     return a.ctypes.data_as(_lib.c_int32_p)
 
 
+def _tptr(t, ty):
+    """Device pointer of a torch tensor (None stays NULL)."""
+    return C.cast(C.c_void_p(t.data_ptr()), ty) if t is not None else None
+
+
+def _dtf_array(keep, entries):
+    """mpct_dtf array of ``entries``: Tf's in any nesting of lists (a filter list, a my x nin grid, a
+    list of such grids), flattened row-major.  The array and its coefficient buffers go into ``keep``."""
+    flat = []
+
+    def walk(e):
+        if isinstance(e, Tf):
+            flat.append(e)
+        else:
+            for x in e:
+                walk(x)
+
+    walk(entries)
+    arr = (_lib.MpctDtf * len(flat))()
+    for k, t in enumerate(flat):
+        num = np.ascontiguousarray(t.num, dtype=float)
+        den = np.ascontiguousarray(t.den, dtype=float)
+        keep.extend([num, den])
+        arr[k] = _lib.MpctDtf(len(num), _dp(num), _dp(den), int(t.delay))
+    keep.append(arr)
+    return arr
+
+
 class MpctError(RuntimeError):
     pass
 
@@ -76,18 +104,6 @@ class Scenario:
         dp_desc = (dp - self.dmin[:, None]) if self.dtc else dp
         keep = []  # keep every buffer alive for the descriptor's lifetime
 
-        def dtf_array(P):
-            arr = (_lib.MpctDtf * (self.my * self.nin))()
-            for i in range(self.my):
-                for j in range(self.nin):
-                    t = P[i][j]
-                    num = np.ascontiguousarray(t.num, dtype=float)
-                    den = np.ascontiguousarray(t.den, dtype=float)
-                    keep.extend([num, den])
-                    arr[i * self.nin + j] = _lib.MpctDtf(len(num), _dp(num), _dp(den), int(t.delay))
-            keep.append(arr)
-            return arr
-
         A_cat = np.ascontiguousarray(np.concatenate([np.asarray(a, dtype=float) / a[0] for a in A]))
         B_cat = np.ascontiguousarray(np.concatenate(
             [np.asarray(B[i][j], dtype=float) / A[i][0] for i in range(self.my) for j in range(self.nin)]))
@@ -105,8 +121,8 @@ class Scenario:
         d.weights_squared = int(self.weights_squared)
         d.vns_ink = self.vns_ink
         d.n1 = _ip(n1)
-        d.plant = dtf_array(plant)
-        d.model = dtf_array(model)
+        d.plant = _dtf_array(keep, plant)
+        d.model = _dtf_array(keep, model)
         if host_carima or self.dtc or not exact_carima:
             d.na, d.carima_A, d.nb, d.carima_B, d.dp = _ip(na32), _dp(A_cat), _ip(nb32), _dp(B_cat), _ip(dp32)
         d.du_min, d.du_max, d.u_min, d.u_max = (_dp(b) for b in bnds)
@@ -114,40 +130,13 @@ class Scenario:
         d.dtc = int(self.dtc)
         d.nq = self.nq
         if filters is not None:
-            farr = (_lib.MpctDtf * self.my)()
-            for i, t in enumerate(filters):
-                num = np.ascontiguousarray(t.num, dtype=float)
-                den = np.ascontiguousarray(t.den, dtype=float)
-                keep.extend([num, den])
-                farr[i] = _lib.MpctDtf(len(num), _dp(num), _dp(den), int(t.delay))
-            keep.append(farr)
-            d.filter = farr
+            d.filter = _dtf_array(keep, filters)
         if self.nq:
-            darr = (_lib.MpctDtf * (self.my * self.nq))()
-            for i in range(self.my):
-                for j in range(self.nq):
-                    t = dist[i][j]
-                    num = np.ascontiguousarray(t.num, dtype=float)
-                    den = np.ascontiguousarray(t.den, dtype=float)
-                    keep.extend([num, den])
-                    darr[i * self.nq + j] = _lib.MpctDtf(len(num), _dp(num), _dp(den), int(t.delay))
-            keep.append(darr)
-            d.dist = darr
+            d.dist = _dtf_array(keep, dist)
         self.nplant = len(plant_variants) if plant_variants else 1
-        if plant_variants and len(plant_variants) > 1:
-            n = self.my * self.nin
-            varr = (_lib.MpctDtf * (len(plant_variants) * n))()
-            for v, Pv in enumerate(plant_variants):
-                for i in range(self.my):
-                    for j in range(self.nin):
-                        t = Pv[i][j]
-                        num = np.ascontiguousarray(t.num, dtype=float)
-                        den = np.ascontiguousarray(t.den, dtype=float)
-                        keep.extend([num, den])
-                        varr[v * n + i * self.nin + j] = _lib.MpctDtf(len(num), _dp(num), _dp(den), int(t.delay))
-            keep.append(varr)
-            d.nplant = len(plant_variants)
-            d.plant_var = varr
+        if self.nplant > 1:
+            d.nplant = self.nplant
+            d.plant_var = _dtf_array(keep, plant_variants)
         self.mdband = bands is not None or self.nd > 0
         if self.mdband:
             if window != "toolbox" or self.dtc:
@@ -244,9 +233,10 @@ def _opts(open_loop, want_traj, device=-1, max_qp_iter=0, feas_tol=0.0):
     return _lib.MpctOpts(int(open_loop), int(want_traj), int(max_qp_iter), int(device), float(feas_tol))
 
 
-def eval_batch(sc: Scenario, N2, Nu, delta, lam, refs, v=None, open_loop=False, want_traj=False,
-               device=-1, max_qp_iter=0, feas_tol=0.0) -> EvalResult:
-    """Score C candidates against nref reference sets (host arrays in, host arrays out)."""
+def _batch_args(sc, N2, Nu, delta, lam, refs, v):
+    """The candidates and signals of one call as the contiguous arrays the library reads:
+    (N2, Nu, delta, lam, refs, Cn, nref, vv); vv is None for a scenario without disturbance inputs,
+    else v broadcast over the nref reference sets."""
     N2 = np.ascontiguousarray(np.atleast_1d(N2), dtype=np.int32)
     Cn = N2.size
     Nu = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(Nu), (Cn,)), dtype=np.int32)
@@ -254,11 +244,15 @@ def eval_batch(sc: Scenario, N2, Nu, delta, lam, refs, v=None, open_loop=False, 
     lam = np.ascontiguousarray(np.asarray(lam, dtype=float).reshape(Cn, sc.nu))
     refs = np.ascontiguousarray(np.asarray(refs, dtype=float).reshape(-1, sc.my, sc.nit))
     nref = refs.shape[0]
-    S = Cn * nref
     vv = None
     if sc.nd + sc.nq:
         vv = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=float).reshape(-1, sc.nd + sc.nq, sc.nit),
                                                   (nref, sc.nd + sc.nq, sc.nit)))
+    return N2, Nu, delta, lam, refs, Cn, nref, vv
+
+
+def _eval_result(sc, S, nref, open_loop, want_traj):
+    """An EvalResult for S simulations and the MpctResult that points into it."""
     res = EvalResult(J1=np.zeros((S, sc.my)), j21=np.zeros((S, sc.my)), j22=np.zeros((S, sc.my)),
                      Jnu=np.zeros((S, sc.nu)), status=np.zeros(S, dtype=np.int32),
                      qp_iters=np.zeros(S, dtype=np.int64), nref=nref)
@@ -274,6 +268,14 @@ def eval_batch(sc: Scenario, N2, Nu, delta, lam, refs, v=None, open_loop=False, 
             res.ys = np.zeros((S, sc.my, sc.nit))
             res.uopt = np.zeros((S, sc.nu, sc.nit))
             r.ys, r.uopt = _dp(res.ys), _dp(res.uopt)
+    return res, r
+
+
+def eval_batch(sc: Scenario, N2, Nu, delta, lam, refs, v=None, open_loop=False, want_traj=False,
+               device=-1, max_qp_iter=0, feas_tol=0.0) -> EvalResult:
+    """Score C candidates against nref reference sets (host arrays in, host arrays out)."""
+    N2, Nu, delta, lam, refs, Cn, nref, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    res, r = _eval_result(sc, Cn * nref, nref, open_loop, want_traj)
     o = _opts(open_loop, want_traj, device, max_qp_iter, feas_tol)
     rc = sc.lib.mpct_eval_batch(sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data,
                                 lam.ctypes.data, nref, refs.ctypes.data,
@@ -295,16 +297,12 @@ def eval_batch_device(sc: Scenario, N2, Nu, delta, lam, refs, out: dict, v=None,
     Cn = N2.numel()
     nref = refs.shape[0]
     r = _lib.MpctResult()
-
-    def ptr(t, ty):
-        return C.cast(C.c_void_p(t.data_ptr()), ty) if t is not None else None
-
-    r.J1 = ptr(out.get("J1"), _lib.c_double_p)
-    r.j21 = ptr(out.get("j21"), _lib.c_double_p)
-    r.j22 = ptr(out.get("j22"), _lib.c_double_p)
-    r.Jnu = ptr(out.get("Jnu"), _lib.c_double_p)
-    r.status = ptr(out.get("status"), _lib.c_int32_p)
-    r.qp_iters = ptr(out.get("qp_iters"), _lib.c_int64_p)
+    r.J1 = _tptr(out.get("J1"), _lib.c_double_p)
+    r.j21 = _tptr(out.get("j21"), _lib.c_double_p)
+    r.j22 = _tptr(out.get("j22"), _lib.c_double_p)
+    r.Jnu = _tptr(out.get("Jnu"), _lib.c_double_p)
+    r.status = _tptr(out.get("status"), _lib.c_int32_p)
+    r.qp_iters = _tptr(out.get("qp_iters"), _lib.c_int64_p)
     o = _opts(open_loop, False, device)
     rc = sc.lib.mpct_eval_batch_device(
         sc.handle, Cn, C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
@@ -356,33 +354,8 @@ def eval_batch_multi(sc: Scenario, devices, N2, Nu, delta, lam, refs, v=None, op
     (strided shards, one host thread, context and stream per list entry, results in the caller's
     order; a device may be listed more than once)."""
     devs = np.ascontiguousarray(np.atleast_1d(devices), dtype=np.int32)
-    N2 = np.ascontiguousarray(np.atleast_1d(N2), dtype=np.int32)
-    Cn = N2.size
-    Nu = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(Nu), (Cn,)), dtype=np.int32)
-    delta = np.ascontiguousarray(np.asarray(delta, dtype=float).reshape(Cn, sc.my))
-    lam = np.ascontiguousarray(np.asarray(lam, dtype=float).reshape(Cn, sc.nu))
-    refs = np.ascontiguousarray(np.asarray(refs, dtype=float).reshape(-1, sc.my, sc.nit))
-    nref = refs.shape[0]
-    S = Cn * nref
-    vv = None
-    if sc.nd + sc.nq:
-        vv = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=float).reshape(-1, sc.nd + sc.nq, sc.nit),
-                                                  (nref, sc.nd + sc.nq, sc.nit)))
-    res = EvalResult(J1=np.zeros((S, sc.my)), j21=np.zeros((S, sc.my)), j22=np.zeros((S, sc.my)),
-                     Jnu=np.zeros((S, sc.nu)), status=np.zeros(S, dtype=np.int32),
-                     qp_iters=np.zeros(S, dtype=np.int64), nref=nref)
-    r = _lib.MpctResult()
-    r.J1, r.j21, r.j22, r.Jnu = _dp(res.J1), _dp(res.j21), _dp(res.j22), _dp(res.Jnu)
-    r.status = _ip(res.status)
-    r.qp_iters = res.qp_iters.ctypes.data_as(_lib.c_int64_p)
-    if want_traj:
-        res.y = np.zeros((S, sc.my, sc.nit))
-        res.u = np.zeros((S, sc.nu, sc.nit))
-        r.y, r.u = _dp(res.y), _dp(res.u)
-        if open_loop:
-            res.ys = np.zeros((S, sc.my, sc.nit))
-            res.uopt = np.zeros((S, sc.nu, sc.nit))
-            r.ys, r.uopt = _dp(res.ys), _dp(res.uopt)
+    N2, Nu, delta, lam, refs, Cn, nref, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    res, r = _eval_result(sc, Cn * nref, nref, open_loop, want_traj)
     o = _opts(open_loop, want_traj, -1, max_qp_iter, feas_tol)
     rc = sc.lib.mpct_eval_batch_multi(sc.handle, len(devs), _ip(devs), Cn, N2.ctypes.data, Nu.ctypes.data,
                                       delta.ctypes.data, lam.ctypes.data, nref, refs.ctypes.data,
@@ -422,17 +395,7 @@ def eval_robust(sc: Scenario, N2, Nu, delta, lam, refs, v=None, j_bound=0.0, dev
     """Score C candidates over the D = len(refs) draws (reference set k, plant variant k % nplant)
     and reduce on the device to per-candidate statistics (host arrays in and out).  ``j_bound``:
     a draw whose total cost exceeds it fails (0 = 1e100, inf allowed)."""
-    N2 = np.ascontiguousarray(np.atleast_1d(N2), dtype=np.int32)
-    Cn = N2.size
-    Nu = np.ascontiguousarray(np.broadcast_to(np.atleast_1d(Nu), (Cn,)), dtype=np.int32)
-    delta = np.ascontiguousarray(np.asarray(delta, dtype=float).reshape(Cn, sc.my))
-    lam = np.ascontiguousarray(np.asarray(lam, dtype=float).reshape(Cn, sc.nu))
-    refs = np.ascontiguousarray(np.asarray(refs, dtype=float).reshape(-1, sc.my, sc.nit))
-    D = refs.shape[0]
-    vv = None
-    if sc.nd + sc.nq:
-        vv = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=float).reshape(-1, sc.nd + sc.nq, sc.nit),
-                                                  (D, sc.nd + sc.nq, sc.nit)))
+    N2, Nu, delta, lam, refs, Cn, D, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
     res = RobustResult(mean=np.zeros((Cn, sc.my)), worst=np.zeros((Cn, sc.my)), n_failed=np.zeros(Cn, dtype=np.int32),
                        worst_draw=np.zeros(Cn, dtype=np.int32), status=np.zeros(Cn, dtype=np.int32), draws=D,
                        J1=np.zeros((Cn * D, sc.my)) if want_J1 else None)
@@ -452,13 +415,9 @@ def eval_robust(sc: Scenario, N2, Nu, delta, lam, refs, v=None, j_bound=0.0, dev
 
 def _robust_struct(out: dict):
     r = _lib.MpctRobustResult()
-
-    def ptr(t, ty):
-        return C.cast(C.c_void_p(t.data_ptr()), ty) if t is not None else None
-
-    r.mean, r.worst = ptr(out.get("mean"), _lib.c_double_p), ptr(out.get("worst"), _lib.c_double_p)
-    r.n_failed, r.worst_draw = ptr(out.get("n_failed"), _lib.c_int32_p), ptr(out.get("worst_draw"), _lib.c_int32_p)
-    r.status, r.J1 = ptr(out.get("status"), _lib.c_int32_p), ptr(out.get("J1"), _lib.c_double_p)
+    r.mean, r.worst = _tptr(out.get("mean"), _lib.c_double_p), _tptr(out.get("worst"), _lib.c_double_p)
+    r.n_failed, r.worst_draw = _tptr(out.get("n_failed"), _lib.c_int32_p), _tptr(out.get("worst_draw"), _lib.c_int32_p)
+    r.status, r.J1 = _tptr(out.get("status"), _lib.c_int32_p), _tptr(out.get("J1"), _lib.c_double_p)
     return r
 
 

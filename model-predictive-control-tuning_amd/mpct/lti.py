@@ -88,6 +88,18 @@ def c2d(num, den, Ts: float, delay: float = 0.0) -> Tf:
     return Tf.make(numz, cp, D + 1)
 
 
+def fopdt_grid(K, TAU, DELAY, Ts: float, L=None, R=None):
+    """L * c2d(K / (TAU s + 1) e^(-DELAY s), Ts, 'zoh') * R entry by entry: the discrete plant of a
+    first-order-plus-dead-time transfer matrix under MPCTuning's diagonal scaling (MPCTuning.m:162
+    Pze = L*Pz*R; None: unscaled), as a grid of Tf."""
+    K = np.asarray(K, dtype=float)
+    TAU, DELAY = np.broadcast_to(TAU, K.shape), np.broadcast_to(DELAY, K.shape)
+    L = np.ones(K.shape[0]) if L is None else L
+    R = np.ones(K.shape[1]) if R is None else R
+    return [[c2d([K[i, j]], [TAU[i, j], 1.0], Ts, DELAY[i, j]).scale(L[i] * R[j]) for j in range(K.shape[1])]
+            for i in range(K.shape[0])]
+
+
 def lsim(tf: Tf, u) -> np.ndarray:
     """Discrete simulation from rest (lsim of a discrete tf)."""
     from scipy.signal import lfilter

@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from .engine import Scenario
-from .lti import c2d, lsim
+from .lti import c2d, fopdt_grid, lsim
 
 # Shell3x3.m:52-57 nominal model, Ts, nit
 SHELL3_K = np.array([[4.05, 1.77, 5.88], [5.39, 5.72, 6.9], [4.38, 4.42, 7.2]])
@@ -24,6 +24,23 @@ SHELL3_R = np.array([0.661867070834956, 0.2756082654542081, 0.41172304878568067]
 SHELL3_TUNED = dict(N=24, Nu=(6, 2, 2),
                     delta=(0.010659948215964849, 0.004019856475662751, 0.0007926546087416782),
                     lam=(9.247457388705409e-05, 0.0005523146971406108, 0.0015219790494510478))
+
+
+def _shell_mc_plants(K, DK, TAU, DELAY, Ts, draws, seed, e_max, max_dshift, L, R):
+    """The Shell model-error draws: gains K[i, j] + DK[i, j] * e_j, time constants and delays of the
+    nominal model, scaled by L, R.  Draw 0 is the reference's case, e = e_max exactly and no delay
+    shift; draws k >= 1 take e_j ~ U(-e_max_j, e_max_j) from numpy default_rng(seed), one number per
+    column.  max_dshift > 0 adds U{0..max_dshift} * Ts to every entry's delay of the draws k >= 1, from
+    a stream of its own (default_rng([seed, 1])), so the gains are the same for every max_dshift."""
+    e_max = np.broadcast_to(np.asarray(e_max, dtype=float), (K.shape[1],))
+    rng = np.random.default_rng(seed)
+    rng_d = np.random.default_rng([seed, 1]) if max_dshift > 0 else None
+    out = []
+    for k in range(draws):
+        e = e_max if k == 0 else rng.uniform(-e_max, e_max)
+        sh = np.zeros(K.shape, dtype=int) if k == 0 or rng_d is None else rng_d.integers(0, max_dshift + 1, K.shape)
+        out.append(fopdt_grid(K + DK * e[None, :], TAU, DELAY + sh * Ts, Ts, L, R))
+    return out
 
 
 def shell3x3_xsp(nit=SHELL3_NIT):
@@ -47,22 +64,26 @@ def shell3x3_yref(X, caso=2):
 
 def shell3x3_plant(L=SHELL3_L, R=SHELL3_R):
     """Pze = L * c2d(Ps, Ts, 'zoh') * R  (Shell3x3.m:65, MPCTuning.m:162)."""
-    return [[c2d([SHELL3_K[i, j]], [SHELL3_TAU[i, j], 1.0], SHELL3_TS, SHELL3_DELAY[i, j]).scale(L[i] * R[j])
-             for j in range(3)] for i in range(3)]
+    return fopdt_grid(SHELL3_K, SHELL3_TAU, SHELL3_DELAY, SHELL3_TS, L, R)
+
+
+def _shell3x3_scenario(plant, n2_max, nu_max, nit, L, R, **kw):
+    """What shell3x3 and shell3x3_mc share: the nominal model, bounds (Shell3x3.m:120-123 scaled by R,
+    MPCTuning.m:170-178), r = L*Xsp and yref = L*Yref (MPCTuning.m:188-189).  plant None: the model."""
+    P = shell3x3_plant(L, R)
+    X = shell3x3_xsp(nit)
+    yref = L[:, None] * shell3x3_yref(X)
+    sc = Scenario(P if plant is None else plant, P, nu=3, du_min=-0.05 / R, du_max=0.05 / R, u_min=-1.0 / R,
+                  u_max=0.5 / R, yref=yref, n2_max=n2_max, nu_max=nu_max, Ts=SHELL3_TS, **kw)
+    return sc, L[:, None] * X, yref
 
 
 def shell3x3(n2_max=30, nu_max=5, nit=SHELL3_NIT, L=SHELL3_L, R=SHELL3_R, window="toolbox",
              weights_squared=True, exact_carima=True):
     """Returns (Scenario, r, yref): r = L*Xsp, yref = L*Yref (MPCTuning.m:188-189) as row signals.
     Bounds: Shell3x3.m:120-123 scaled by R (MPCTuning.m:170-178)."""
-    P = shell3x3_plant(L, R)
-    X = shell3x3_xsp(nit)
-    yref = L[:, None] * shell3x3_yref(X)
-    r = L[:, None] * X
-    sc = Scenario(P, P, nu=3, du_min=-0.05 / R, du_max=0.05 / R, u_min=-1.0 / R, u_max=0.5 / R,
-                  yref=yref, n2_max=n2_max, nu_max=nu_max, Ts=SHELL3_TS, window=window,
-                  weights_squared=weights_squared, exact_carima=exact_carima)
-    return sc, r, yref
+    return _shell3x3_scenario(None, n2_max, nu_max, nit, L, R, window=window, weights_squared=weights_squared,
+                              exact_carima=exact_carima)
 
 
 # Shell3x3.m:43-45 "model error case": the simulated plant's gains are K + DK * e_j (column j)
@@ -71,24 +92,9 @@ SHELL3_EMAX = (0.2, 0.2, 0.3)   # Shell3x3.m:38 (nominal = false)
 
 
 def shell3x3_mc_plants(draws, seed=20250307, e_max=SHELL3_EMAX, max_dshift=0, L=SHELL3_L, R=SHELL3_R):
-    """Plant-mismatch draws around Shell3x3.m's model error case (:34-48): gains K[i, j] + DK[i, j] * e_j,
-    time constants and delays of the nominal model, scaled by L, R like shell3x3_plant.  Draw 0 is the
-    reference's case, e = e_max exactly (and no delay shift); draws k >= 1 take e_j ~ U(-e_max_j,
-    e_max_j) from numpy default_rng(seed), three numbers per draw.  max_dshift > 0 adds U{0..max_dshift}
-    * Ts to every entry's delay of the draws k >= 1, drawn after that draw's gains from a stream of its
-    own (default_rng([seed, 1])), so the gains are the same for every max_dshift.  e = 0 gives
-    shell3x3_plant.  Returns a list of 3x3 plants (mpct.lti.Tf)."""
-    e_max = np.broadcast_to(np.asarray(e_max, dtype=float), (3,))
-    rng = np.random.default_rng(seed)
-    rng_d = np.random.default_rng([seed, 1]) if max_dshift > 0 else None
-    out = []
-    for k in range(draws):
-        e = e_max if k == 0 else rng.uniform(-e_max, e_max)
-        sh = np.zeros((3, 3), dtype=int) if k == 0 or rng_d is None else rng_d.integers(0, max_dshift + 1, (3, 3))
-        out.append([[c2d([SHELL3_K[i, j] + SHELL3_DK[i, j] * e[j]], [SHELL3_TAU[i, j], 1.0], SHELL3_TS,
-                         SHELL3_DELAY[i, j] + sh[i, j] * SHELL3_TS).scale(L[i] * R[j])
-                     for j in range(3)] for i in range(3)])
-    return out
+    """Plant-mismatch draws around Shell3x3.m's model error case (:34-48), three e_j per draw
+    (_shell_mc_plants).  e = 0 gives shell3x3_plant.  Returns a list of 3x3 plants (mpct.lti.Tf)."""
+    return _shell_mc_plants(SHELL3_K, SHELL3_DK, SHELL3_TAU, SHELL3_DELAY, SHELL3_TS, draws, seed, e_max, max_dshift, L, R)
 
 
 def shell3x3_mc(draws=8, n2_max=30, nu_max=5, nit=SHELL3_NIT, seed=20250307, e_max=SHELL3_EMAX, max_dshift=0,
@@ -96,14 +102,8 @@ def shell3x3_mc(draws=8, n2_max=30, nu_max=5, nit=SHELL3_NIT, seed=20250307, e_m
     """The constrained Shell 3x3 loop of shell3x3() over `draws` mismatched plants (shell3x3_mc_plants;
     variant k runs with reference row k): the controller keeps the nominal model, bounds and Yref are
     those of shell3x3().  Returns (Scenario, refs [draws, 3, nit], plants)."""
-    P = shell3x3_plant(L, R)
     plants = shell3x3_mc_plants(draws, seed, e_max, max_dshift, L, R)
-    X = shell3x3_xsp(nit)
-    yref = L[:, None] * shell3x3_yref(X)
-    r = L[:, None] * X
-    sc = Scenario(plants[0], P, nu=3, du_min=-0.05 / R, du_max=0.05 / R, u_min=-1.0 / R, u_max=0.5 / R,
-                  yref=yref, n2_max=n2_max, nu_max=nu_max, Ts=SHELL3_TS, window="toolbox",
-                  plant_variants=plants)
+    sc, r, _ = _shell3x3_scenario(plants[0], n2_max, nu_max, nit, L, R, window="toolbox", plant_variants=plants)
     return sc, np.broadcast_to(r, (draws, 3, nit)).copy(), plants
 
 
@@ -175,8 +175,7 @@ def config3_stratified(per_cell=128, per=1024):
 
 def shell7x5_plant(L=SHELL7_L, R=SHELL7_R):
     """Pze = L * c2d([Gs Ds], Ts, 'zoh') * R  (Shell7x5.m:93-98, MPCTuning.m:162)."""
-    return [[c2d([SHELL7_K[i, j]], [SHELL7_TAU[i, j], 1.0], SHELL7_TS, SHELL7_DELAY[i, j]).scale(L[i] * R[j])
-             for j in range(5)] for i in range(7)]
+    return fopdt_grid(SHELL7_K, SHELL7_TAU, SHELL7_DELAY, SHELL7_TS, L, R)
 
 
 def shell7x5_signals(nit=SHELL7_NIT, tmd=20, L=SHELL7_L, R=SHELL7_R):
@@ -192,11 +191,9 @@ def shell7x5_signals(nit=SHELL7_NIT, tmd=20, L=SHELL7_L, R=SHELL7_R):
     return np.zeros((7, nit)), mdv / R[3:, None], L[:, None] * Yref
 
 
-def shell7x5(n2_max=127, nu_max=15, nit=SHELL7_NIT, L=SHELL7_L, R=SHELL7_R):
-    """Returns (Scenario, r, v, yref) for the toolbox MPC of Shell7x5.m after MPCTuning's
-    scaling: MV bounds +-0.5/R (:110-111, 135-138; no rate bounds), soft OV bands L*Ymn..L*Ymx
-    with MinECR/MaxECR (:141-152), OV ScaleFactor = L*Yrange unless Yrange == 1 (:162-168,
-    MPCTuning.m:182-184), MV ScaleFactor 1 (Urange = 1), Weights.ECR = 1e4 (:191)."""
+def _shell7x5_scenario(plant, n2_max, nu_max, nit, L, R, **kw):
+    """What shell7x5 and shell7x5_mc share: the nominal model, signals, MV bounds and output bands
+    (see shell7x5).  plant None: the model.  Returns (Scenario, r, v, yref)."""
     P = shell7x5_plant(L, R)
     r, v, yref = shell7x5_signals(nit, L=L, R=R)
     umx = 0.5 / R[:3]
@@ -204,9 +201,17 @@ def shell7x5(n2_max=127, nu_max=15, nit=SHELL7_NIT, L=SHELL7_L, R=SHELL7_R):
     bands = dict(y_min=-L * SHELL7_YMX, y_max=L * SHELL7_YMX, ecr_min=SHELL7_ECR, ecr_max=SHELL7_ECR,
                  y_scale=np.where(yr != 1.0, L * yr, yr), u_scale=np.ones(3), rho=1e4)
     inf = np.full(3, np.inf)
-    sc = Scenario(P, P, nu=3, du_min=-inf, du_max=inf, u_min=-umx, u_max=umx, yref=yref,
-                  n2_max=n2_max, nu_max=nu_max, Ts=SHELL7_TS, window="toolbox", bands=bands)
+    sc = Scenario(P if plant is None else plant, P, nu=3, du_min=-inf, du_max=inf, u_min=-umx, u_max=umx, yref=yref,
+                  n2_max=n2_max, nu_max=nu_max, Ts=SHELL7_TS, window="toolbox", bands=bands, **kw)
     return sc, r, v, yref
+
+
+def shell7x5(n2_max=127, nu_max=15, nit=SHELL7_NIT, L=SHELL7_L, R=SHELL7_R):
+    """Returns (Scenario, r, v, yref) for the toolbox MPC of Shell7x5.m after MPCTuning's
+    scaling: MV bounds +-0.5/R (:110-111, 135-138; no rate bounds), soft OV bands L*Ymn..L*Ymx
+    with MinECR/MaxECR (:141-152), OV ScaleFactor = L*Yrange unless Yrange == 1 (:162-168,
+    MPCTuning.m:182-184), MV ScaleFactor 1 (Urange = 1), Weights.ECR = 1e4 (:191)."""
+    return _shell7x5_scenario(None, n2_max, nu_max, nit, L, R)
 
 
 # Shell7x5.m:46-62 "model error case": the simulated plant's gains are K + DK * e_j (column j of
@@ -219,24 +224,9 @@ SHELL7_EMAX = (0.2, 0.2, 0.3, 0.5, 0.5)   # Shell7x5.m:41 (nominal = false)
 
 
 def shell7x5_mc_plants(draws, seed=20250307, e_max=SHELL7_EMAX, max_dshift=0, L=SHELL7_L, R=SHELL7_R):
-    """Plant-mismatch draws around Shell7x5.m's model error case (:38-63): gains K[i, j] + DK[i, j] * e_j
-    over all five columns of [Gr Dr], time constants and delays of the nominal model, scaled by L, R
-    like shell7x5_plant.  Draw 0 is the reference's case, e = e_max exactly (and no delay shift); draws
-    k >= 1 take e_j ~ U(-e_max_j, e_max_j) from numpy default_rng(seed), five numbers per draw.
-    max_dshift > 0 adds U{0..max_dshift} * Ts to every entry's delay of the draws k >= 1, drawn from a
-    stream of its own (default_rng([seed, 1])), so the gains are the same for every max_dshift.
-    e = 0 gives shell7x5_plant.  Returns a list of 7x5 plants (mpct.lti.Tf)."""
-    e_max = np.broadcast_to(np.asarray(e_max, dtype=float), (5,))
-    rng = np.random.default_rng(seed)
-    rng_d = np.random.default_rng([seed, 1]) if max_dshift > 0 else None
-    out = []
-    for k in range(draws):
-        e = e_max if k == 0 else rng.uniform(-e_max, e_max)
-        sh = np.zeros((7, 5), dtype=int) if k == 0 or rng_d is None else rng_d.integers(0, max_dshift + 1, (7, 5))
-        out.append([[c2d([SHELL7_K[i, j] + SHELL7_DK[i, j] * e[j]], [SHELL7_TAU[i, j], 1.0], SHELL7_TS,
-                         SHELL7_DELAY[i, j] + sh[i, j] * SHELL7_TS).scale(L[i] * R[j])
-                     for j in range(5)] for i in range(7)])
-    return out
+    """Plant-mismatch draws around Shell7x5.m's model error case (:38-63), five e_j per draw over all
+    columns of [Gr Dr] (_shell_mc_plants).  e = 0 gives shell7x5_plant.  Returns a list of 7x5 plants."""
+    return _shell_mc_plants(SHELL7_K, SHELL7_DK, SHELL7_TAU, SHELL7_DELAY, SHELL7_TS, draws, seed, e_max, max_dshift, L, R)
 
 
 def shell7x5_mc(draws=8, n2_max=127, nu_max=15, nit=SHELL7_NIT, seed=20250307, e_max=SHELL7_EMAX, max_dshift=0,
@@ -246,17 +236,9 @@ def shell7x5_mc(draws=8, n2_max=127, nu_max=15, nit=SHELL7_NIT, seed=20250307, e
     prediction by the output-bias estimator (Shell7x5.m:302-303 simulates with options.Model = plant;
     the toolbox's own estimator is not restated); bounds, bands and Yref are those of
     shell7x5().  Returns (Scenario, r [draws, 7, nit], v [draws, 2, nit], yref, plants)."""
-    P = shell7x5_plant(L, R)
     plants = shell7x5_mc_plants(draws, seed, e_max, max_dshift, L, R)
-    r, v, yref = shell7x5_signals(nit, L=L, R=R)
-    umx = 0.5 / R[:3]
-    yr = 2 * SHELL7_YMX
-    bands = dict(y_min=-L * SHELL7_YMX, y_max=L * SHELL7_YMX, ecr_min=SHELL7_ECR, ecr_max=SHELL7_ECR,
-                 y_scale=np.where(yr != 1.0, L * yr, yr), u_scale=np.ones(3), rho=1e4)
-    inf = np.full(3, np.inf)
-    sc = Scenario(plants[0], P, nu=3, du_min=-inf, du_max=inf, u_min=-umx, u_max=umx, yref=yref,
-                  n2_max=n2_max, nu_max=nu_max, Ts=SHELL7_TS, window="toolbox", bands=bands,
-                  plant_variants=plants, estimator="output_bias")
+    sc, r, v, yref = _shell7x5_scenario(plants[0], n2_max, nu_max, nit, L, R, plant_variants=plants,
+                                        estimator="output_bias")
     return sc, np.broadcast_to(r, (draws, 7, nit)).copy(), np.broadcast_to(v, (draws, 2, nit)).copy(), yref, plants
 
 
@@ -270,13 +252,10 @@ WB_DELAY = np.array([[1.0, 2.0, 8.1], [2.0, 1.0, 3.4]])
 WB_W = np.array([0.1, 0.5])                                        # WoodBerry.m:155
 
 
-def woodberry_toolbox(n2_max=30, nu_max=10, nit=400, caso=1, L=np.ones(2), R=np.ones(3)):
-    """Returns (Scenario, r, v, yref) of WoodBerry.m:43-148: rate bounds +-0.05, amplitude
-    +-0.5 (:118-134, scaled by R), unbounded outputs; Xsp(1, 10:) = 0.8, Xsp(2, 200:) = 0.5
-    (:87-89); mdv(300:) = -0.25 (:92-94); Yref = lsim(Pref, Xsp) with Pref diag(1/(10s+1),
-    1/(7s+1)) (caso 1) or diag(1/(15s+1), 1/(12s+1)), delays [1, 1] (:69-75, :98)."""
-    P = [[c2d([WB_K[i, j]], [WB_TAU[i, j], 1.0], 1.0, WB_DELAY[i, j]).scale(L[i] * R[j]) for j in range(3)]
-         for i in range(2)]
+def _woodberry_scenario(plant, n2_max, nu_max, nit, caso, L, R, **kw):
+    """What woodberry_toolbox and woodberry_toolbox_mc share: the nominal model, signals and bounds
+    (see woodberry_toolbox).  plant None: the model.  Returns (Scenario, r, v, yref)."""
+    P = fopdt_grid(WB_K, WB_TAU, WB_DELAY, 1.0, L, R)
     X = np.zeros((2, nit))
     X[0, 9:] = 0.8
     X[1, 199:] = 0.5
@@ -285,9 +264,17 @@ def woodberry_toolbox(n2_max=30, nu_max=10, nit=400, caso=1, L=np.ones(2), R=np.
     mdv = np.zeros((1, nit))
     mdv[0, 299:] = -0.25
     Ru = R[:2]
-    sc = Scenario(P, P, nu=2, du_min=-0.05 / Ru, du_max=0.05 / Ru, u_min=-0.5 / Ru, u_max=0.5 / Ru,
-                  yref=L[:, None] * Yref, n2_max=n2_max, nu_max=nu_max, Ts=1.0, window="toolbox")
+    sc = Scenario(P if plant is None else plant, P, nu=2, du_min=-0.05 / Ru, du_max=0.05 / Ru, u_min=-0.5 / Ru,
+                  u_max=0.5 / Ru, yref=L[:, None] * Yref, n2_max=n2_max, nu_max=nu_max, Ts=1.0, window="toolbox", **kw)
     return sc, L[:, None] * X, mdv / R[2:, None], L[:, None] * Yref
+
+
+def woodberry_toolbox(n2_max=30, nu_max=10, nit=400, caso=1, L=np.ones(2), R=np.ones(3)):
+    """Returns (Scenario, r, v, yref) of WoodBerry.m:43-148: rate bounds +-0.05, amplitude
+    +-0.5 (:118-134, scaled by R), unbounded outputs; Xsp(1, 10:) = 0.8, Xsp(2, 200:) = 0.5
+    (:87-89); mdv(300:) = -0.25 (:92-94); Yref = lsim(Pref, Xsp) with Pref diag(1/(10s+1),
+    1/(7s+1)) (caso 1) or diag(1/(15s+1), 1/(12s+1)), delays [1, 1] (:69-75, :98)."""
+    return _woodberry_scenario(None, n2_max, nu_max, nit, caso, L, R)
 
 
 WB_DELTAK, WB_DELTAL = 0.2, 1.0   # WoodBerry.m:40-41 (nominal = false)
@@ -298,16 +285,19 @@ def woodberry_mc_plants(draws, seed=20250307, dk_max=WB_DELTAK, max_dshift=int(W
     (1 + dk) and the MV delays plus dL samples, the disturbance column Ds unchanged.  Draw 0 is the
     reference's case (dk = dk_max, dL = max_dshift); draws k >= 1 take dk ~ U(-dk_max, dk_max) from
     numpy default_rng(seed) and dL ~ U{0..max_dshift} from default_rng([seed, 1]), one number each
-    per draw.  dk_max = 0, max_dshift = 0 gives the nominal plant.  Returns a list of 2x3 plants."""
+    per draw.  dk_max = 0, max_dshift = 0 gives the nominal plant.  Returns a list of 2x3 plants.
+
+    Not mpct.dtc.woodberry_mc_plants (config 4, DTC_GPC_WW.m): that one draws the 2x2 MV block alone,
+    a gain factor and a delay shift per entry, both from one stream default_rng(seed), and has no
+    reference draw 0; here one dk and one dL move the whole MV block and the streams are two."""
     rng = np.random.default_rng(seed)
     rng_d = np.random.default_rng([seed, 1])
+    mv = np.array([1.0, 1.0, 0.0])[None, :]   # the MV columns of [Gs Ds]
     out = []
     for k in range(draws):
         dk = dk_max if k == 0 else rng.uniform(-dk_max, dk_max)
         dl = max_dshift if k == 0 else int(rng_d.integers(0, max_dshift + 1))
-        out.append([[c2d([WB_K[i, j] * (1.0 + (dk if j < 2 else 0.0))], [WB_TAU[i, j], 1.0], 1.0,
-                         WB_DELAY[i, j] + (dl if j < 2 else 0)).scale(L[i] * R[j]) for j in range(3)]
-                    for i in range(2)])
+        out.append(fopdt_grid(WB_K * (1.0 + dk * mv), WB_TAU, WB_DELAY + dl * mv, 1.0, L, R))
     return out
 
 
@@ -316,11 +306,7 @@ def woodberry_toolbox_mc(draws=8, n2_max=30, nu_max=10, nit=400, caso=1, seed=20
     """WoodBerry.m's toolbox MPC of woodberry_toolbox() over `draws` mismatched plants
     (woodberry_mc_plants; WoodBerry.m:272-273 simulates with options.Model = plant): nominal model,
     output-bias estimator.  Returns (Scenario, r [draws, 2, nit], v [draws, 1, nit], yref, plants)."""
-    one, r, v, yref = woodberry_toolbox(n2_max, nu_max, nit, caso, L, R)
     plants = woodberry_mc_plants(draws, seed, dk_max, max_dshift, L, R)
-    Ru = R[:2]
-    sc = Scenario(plants[0], one.model, nu=2, du_min=-0.05 / Ru, du_max=0.05 / Ru, u_min=-0.5 / Ru, u_max=0.5 / Ru,
-                  yref=yref, n2_max=n2_max, nu_max=nu_max, Ts=1.0, window="toolbox", plant_variants=plants,
-                  estimator="output_bias")
-    one.close()
+    sc, r, v, yref = _woodberry_scenario(plants[0], n2_max, nu_max, nit, caso, L, R, plant_variants=plants,
+                                         estimator="output_bias")
     return sc, np.broadcast_to(r, (draws, 2, nit)).copy(), np.broadcast_to(v, (draws, 1, nit)).copy(), yref, plants

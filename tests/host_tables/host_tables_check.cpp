@@ -244,14 +244,14 @@ struct Vdv {
 
 // a fresh base descriptor, one fault planted, the builder's answer checked
 template <class Case>
-static void rejects(int code, const char* msg, const std::function<void(Case&)>& plant_fault) {
+static void rejects(int code, const char* msg, const std::function<void(Case&)>& plant_fault, int estimator = 0) {
   Case c;
   plant_fault(c);
   BuildError err;
   if constexpr (std::is_same<Case, Vdv>::value)
     expect_reject(build_nmpc_scenario(c.d, &err), err, code, msg);
   else
-    expect_reject(build_scenario(c.d, &err), err, code, msg);
+    expect_reject(build_scenario(c.d, &err, estimator), err, code, msg);
 }
 
 int main() {
@@ -287,6 +287,9 @@ int main() {
   }
 
   // ---- build_scenario's rejections, in the order of its checks
+  rejects<Band>(MPCT_EINVAL, "unknown estimator id", [](Band&) {}, 2);
+  rejects<Shell>(MPCT_EINVAL, "the output-bias estimator belongs to the band kernel (mdband = 1)", [](Shell&) {},
+                 MPCT_EST_OUTPUT_BIAS);
   rejects<Shell>(MPCT_EINVAL, "bad model entry", [](Shell& c) { c.P[4].den = nullptr; });  // abi-5 derivation
   rejects<Dtc>(MPCT_EINVAL, "bad model entry", [](Dtc& c) { c.model[1].len = 0; });      // step table
   rejects<Band>(MPCT_EINVAL, "bad model entry", [](Band& c) { c.model[1].delay = -1; });  // an MD column

@@ -7,20 +7,7 @@
 //   over the variants, acol is the single-plant map, and the packed blob holds all nvar * 64 rows.
 //   One variant entry outside the kernel's limits makes the whole scenario not small.
 // Exit status 0 when every expectation held.
-#include "scenario_tables.h"
-
-#include <cstdio>
-
-using namespace mpct;
-
-static int g_bad = 0;
-#define CHECK(cond)                                                \
-  do {                                                             \
-    if (!(cond)) {                                                 \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); \
-      ++g_bad;                                                     \
-    }                                                              \
-  } while (0)
+#include "check.h"
 
 // the nominal model (tests/c_abi/mpct_c_demo.c: the saved mpc object's scaled discrete tf) and three
 // plants: 0 the model itself, 1 gains x 1.2 and every delay one sample longer, 2 second-order
@@ -77,16 +64,6 @@ struct Case {
   }
   Case(const Case&) = delete;
 };
-
-static std::unique_ptr<mpct_scenario> build(const mpct_scenario_desc& d) {
-  BuildError err;
-  auto s = build_scenario(d, &err);
-  if (!s) {
-    std::printf("FAILED: rejected %d \"%s\"\n", err.code, err.msg.c_str());
-    ++g_bad;
-  }
-  return s;
-}
 
 int main() {
   Case c;
@@ -206,6 +183,5 @@ int main() {
     std::printf("delay past the rings: rejected %d \"%s\"\n", err.code, err.msg.c_str());
   }
 
-  std::printf(g_bad ? "%d expectation(s) failed\n" : "ok\n", g_bad);
-  return g_bad ? 1 : 0;
+  return finish();
 }

@@ -36,17 +36,11 @@ The reference's J1 on the mismatched plant differs from its J1 on the nominal pl
 (small_4term_ke4), 2.3e-3 (packed_deep) and 2.9e-3 (lds_path) on every candidate and output.
 Every case is some four orders of magnitude inside its tolerance: no kernel or table defect turned up.
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_program
 import plant_family as pf
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "model-predictive-control-tuning_amd", "csrc")
-PROBE_SRC = os.path.join(ROOT, "tests", "host_tables", "layout_probe.cpp")
 
 TRAJ_RTOL = 1e-7   # tests/test_gpu_parity.py: max |a-b| / max |b| per trajectory
 COST_RTOL = 1e-6   # BASELINE.json north_star
@@ -75,19 +69,12 @@ def _traj_err(get, ref, idx=None):
 # CPU
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory):
-    """The layout probe, built with the flags of tests/test_host_tables.py's stand-alone program."""
-    exe = str(tmp_path_factory.mktemp("layout_probe") / "layout_probe")
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-x", "hip", "-O1", "-g", "-std=c++17",
-                    "-Wall", "-Werror", "-Xarch_host", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=undefined", "-I", CSRC, PROBE_SRC, "-o", exe], check=True, timeout=300)
+    """The layout probe, built and run by the recipe of the stand-alone check programs."""
+    exe = host_program.build("layout_probe", tmp_path_factory.mktemp("layout_probe"))
 
     def run(case):
-        env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-        out = subprocess.run([exe], input=pf.descriptor_text(case), capture_output=True, text=True, timeout=60,
-                             env=env)
-        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
-        assert out.stderr.strip() == "", out.stderr[-4000:]  # no sanitizer report
-        fields = dict(kv.split("=", 1) for kv in out.stdout.split())
+        stdout = host_program.run(exe, stdin=pf.descriptor_text(case), ends_ok=False)  # one line of fields, no "ok"
+        fields = dict(kv.split("=", 1) for kv in stdout.split())
         coef = fields.pop("sm_coef", None)
         got = {k: int(v) for k, v in fields.items()}
         got["sm_coef"] = None if coef is None else np.array([float(x) for x in coef.split(",")])

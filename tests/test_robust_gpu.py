@@ -342,6 +342,63 @@ def test_generic_determinism_and_sentinels(gpu):
 
 
 # ---------------------------------------------------------------------------------------------
+# eval_batch and eval_robust interleaved on one scenario: they share the host staging path
+EVAL_FIELDS = ("J1", "j21", "j22", "Jnu", "status", "qp_iters")
+ROBUST_FIELDS = ("mean", "worst", "n_failed", "worst_draw", "status", "J1")
+
+
+def test_host_entries_interleaved_on_one_scenario(gpu):
+    """mpct_eval_batch and mpct_eval_robust alternate on one scenario: one scratch blob, one signal
+    cache, one stream.  The synthetic 2 x (1 MV + 1 MD) band scenario (the one with v), three plant
+    variants, nref = 2:  (a) eval_batch, 3 candidates, signals A;  (b) eval_robust, 5 candidates,
+    signals B != A;  (c) = (a);  (d) = (b).  (c) is (a) and (d) is (b) bit for bit, and both are what
+    fresh scenarios give.  The caller's r and v of (b) are overwritten in place once it has returned
+    (each later call passes a pristine copy), so nothing the library kept may alias them; (e) repeats
+    (d) at once, the call whose signals the cache holds.
+    At 5 candidates every slot still fits its 256-byte granule, so the blob of (a) holds (b) too (the
+    signals no longer live in it); (f), eval_robust on 40 candidates, is the call that makes it regrow,
+    checked against a fresh scenario, and (g) = (a) runs in the regrown blob."""
+    import band_mismatch_ref as bm
+    from mpct.engine import eval_batch, eval_robust
+
+    _, V = bm.synthetic_plants()
+    r, v, _ = bm.synthetic_signals()
+    sigA = np.stack([r, 0.5 * r]), np.stack([v, 0.5 * v])
+    sigB = np.stack([2.0 * r, -r]), np.stack([0.25 * v, v])
+    cands = list(bm.SYN_CANDS) + [(9, 2, np.array([0.2, 0.0]), np.array([0.7])), (12, 1, np.array([1.0, 1.0]), np.array([0.01]))]
+
+    def args(k, rep=1):
+        c = cands[:k] * rep
+        return ([x[0] for x in c], [x[1] for x in c], np.array([x[2] for x in c]), np.array([x[3] for x in c]))
+
+    def batch(sc):
+        return eval_batch(sc, *args(3), sigA[0].copy(), v=sigA[1].copy())
+
+    def robust(sc, rep=1):
+        rB, vB = sigB[0].copy(), sigB[1].copy()
+        res = eval_robust(sc, *args(5, rep), rB, v=vB, want_J1=True)
+        rB[:] = np.nan   # the call has returned: its signals are the library's own copy now
+        vB[:] = 1e6
+        return res
+
+    sc = bm.synthetic_scenario(V)
+    a = batch(sc)
+    b = robust(sc)
+    c = batch(sc)
+    d = robust(sc)
+    e = robust(sc)
+    f = robust(sc, rep=8)
+    g = batch(sc)
+    assert np.all(a.status == 0) and np.all(np.isfinite(a.J1)) and np.all(np.isfinite(b.J1))
+    assert np.any(b.J1[:6] != a.J1)     # B is not A: the same candidates cost something else
+    for x in (c, g, batch(bm.synthetic_scenario(V))):
+        same_bits(x, a, EVAL_FIELDS)
+    for x in (d, e, robust(bm.synthetic_scenario(V))):
+        same_bits(x, b, ROBUST_FIELDS)
+    same_bits(f, robust(bm.synthetic_scenario(V), rep=8), ROBUST_FIELDS)
+
+
+# ---------------------------------------------------------------------------------------------
 # MEX
 EXE = os.path.join(ROOT, "tests", "mex_stub", "mpct_mex_driver_struct")
 

@@ -4,13 +4,12 @@ kernel's register budget, and the host lane tables under the sanitizers
 (tests/host_tables/small_variants_check.cpp)."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "model-predictive-control-tuning_amd", "csrc")
+import host_program
+
 NIT = 200
 
 
@@ -133,17 +132,7 @@ def test_small_kernel_listing_budget(built):
 
 def test_small_variant_tables_under_sanitizers(tmp_path):
     """tests/host_tables/small_variants_check.cpp, host-only, with ASan, LSan and UBSan."""
-    exe = str(tmp_path / "small_variants_check")
-    src = os.path.join(ROOT, "tests", "host_tables", "small_variants_check.cpp")
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "--cuda-host-only", "-x", "hip", "-O1", "-g", "-std=c++17",
-                    "-Wall", "-Werror", "-Xarch_host", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=undefined", "-I", CSRC, src, "-o", exe], check=True, timeout=300)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60, env=env)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
-    assert out.stderr.strip() == "", out.stderr[-4000:]  # no sanitizer report
-    assert out.stdout.rstrip().endswith("ok")
-    assert "valid shell3x3 x 3 variants: ke 4, 192 lane rows" in out.stdout
-    assert "five-term variant entry: small 0" in out.stdout
-    assert 'delay past the rings: rejected -4 "plant entry too long for the device history rings"' in out.stdout
+    stdout = host_program.run(host_program.build("small_variants_check", tmp_path))
+    assert "valid shell3x3 x 3 variants: ke 4, 192 lane rows" in stdout
+    assert "five-term variant entry: small 0" in stdout
+    assert 'delay past the rings: rejected -4 "plant entry too long for the device history rings"' in stdout
