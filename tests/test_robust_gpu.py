@@ -5,8 +5,12 @@ inputs, reduced in numpy here by the semantics of include/mpct.h -- never the ne
 Fused path (dtc_robust_kernel) on the config-4 scenario at D = 1, 3, 5, 32 draws; generic path
 (per-simulation instance + robust_reduce_kernel) on a bounded DTC scenario and Shell 3x3; both
 paths share one reduction (bitwise); determinism, batch-position independence, sentinel and
-bad-horizon candidates; the MEX gateway.  The whole file runs with RuntimeWarning as an error: the
-numpy yardstick masks before it sums."""
+bad-horizon candidates; the MEX gateway.  Large batches: the fused kernels where their workgroups
+stride over the class lists, the classifier runs several passes and a dispatch order exists
+(test_fused_large_batch_strides_and_orders), the generic path at C >= 256, D at and past the fused
+kernel's cap, device-entry calls on two streams across a regrow of the robust scratch.  The
+reduction alone on synthetic records: tests/test_robust_reduce_gpu.py.  The whole file runs with
+RuntimeWarning as an error: the numpy yardstick masks before it sums."""
 import ctypes as C
 import os
 import subprocess
@@ -160,12 +164,26 @@ def mc(D):
     return _scen_cache[D]
 
 
-@pytest.mark.parametrize("D", [1, 3, 5, 32])
+def sample_agrees(got, J1, st):
+    """The optional J1 sample [C, D, my] of a fused call against the per-simulation path's: 1e-9 where
+    the loop stays bounded, 1e-6 where it grows, the same sets (tests/test_dtc.py _costs_agree)."""
+    ok = st == 0
+    np.testing.assert_array_equal(np.isfinite(got).all(axis=2), ok)
+    big_a = np.max(np.abs(np.where(np.isfinite(got), got, 0.0)), axis=2) >= 1e12
+    big_b = np.max(np.abs(np.where(np.isfinite(J1), J1, 0.0)), axis=2) >= 1e12
+    np.testing.assert_array_equal(big_a[ok], big_b[ok])
+    np.testing.assert_allclose(got[ok & ~big_b], J1[ok & ~big_b], rtol=1e-9, atol=0)
+    np.testing.assert_allclose(got[ok & big_b], J1[ok & big_b], rtol=1e-6, atol=0)
+
+
+@pytest.mark.parametrize("D", [1, 2, 3, 4, 5, 32, 127, 128])
 def test_fused_against_per_simulation_path(config4, D):
-    """dtc_robust_kernel against dtc_small_kernel + numpy: fewer draws than waves, D not a multiple
-    of the wave count, and the benchmark's D.  Counts and statuses exact; mean and worst to 1e-9
-    (two kernels running the same bounded loop, tests/test_dtc.py _costs_agree; sums and maxima of
-    positive terms that agree to 1e-9 agree to 1e-9); the J1 sample by _costs_agree's rule."""
+    """dtc_robust_kernel against dtc_small_kernel + numpy: fewer draws than waves (D = 2 leaves two
+    waves without one), D not a multiple of the wave count, the benchmark's D, and the LDS record
+    array at its cap (D = 128; at 127 its 381 doubles are rounded up to 382).  Counts and statuses
+    exact; mean and worst to 1e-9 (two kernels running the same bounded loop, tests/test_dtc.py
+    _costs_agree; sums and maxima of positive terms that agree to 1e-9 agree to 1e-9); the J1 sample
+    by _costs_agree's rule."""
     from mpct.engine import eval_robust, robust_instance
 
     sc, refs, v = mc(D)
@@ -177,15 +195,7 @@ def test_fused_against_per_simulation_path(config4, D):
     print("D = %d: n_failed %s, per-simulation J1 bitwise equal to dtc_small_kernel's: %s" % (
         D, ref["n_failed"].tolist(), bool(np.array_equal(bits(res.J1.reshape(J1.shape)), bits(J1)))))
     compare(res, ref, 1e-9, exact_worst=False)
-    # the optional sample: 1e-9 where the loop stays bounded, 1e-6 where it grows, the same sets
-    got = res.J1.reshape(J1.shape)
-    ok = st == 0
-    np.testing.assert_array_equal(np.isfinite(got).all(axis=2), ok)
-    big_a = np.max(np.abs(np.where(np.isfinite(got), got, 0.0)), axis=2) >= 1e12
-    big_b = np.max(np.abs(np.where(np.isfinite(J1), J1, 0.0)), axis=2) >= 1e12
-    np.testing.assert_array_equal(big_a[ok], big_b[ok])
-    np.testing.assert_allclose(got[ok & ~big_b], J1[ok & ~big_b], rtol=1e-9, atol=0)
-    np.testing.assert_allclose(got[ok & big_b], J1[ok & big_b], rtol=1e-6, atol=0)
+    sample_agrees(res.J1.reshape(J1.shape), J1, st)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -239,13 +249,23 @@ def test_generic_against_per_simulation_path(gpu, make, name):
 
 
 # ---------------------------------------------------------------------------------------------
-def _device_call(sc, q, refs, v, jb, with_J1=True):
+def _device_inputs(q, refs, v):
+    """The arguments of one device-entry call as tensors on cuda:0 (keep them until the call has run)."""
+    import torch
+
+    dev = torch.device("cuda", 0)
+    t = [torch.from_numpy(np.ascontiguousarray(q[k])).to(dev) for k in ("N2", "Nu", "d", "l")]
+    return t, torch.from_numpy(refs).to(dev), None if v is None else torch.from_numpy(v).to(dev)
+
+
+def _device_enqueue(sc, inputs, jb, with_J1=True, stream=None):
+    """eval_robust_device into fresh output tensors, enqueued and not synchronised."""
     import torch
     from mpct.engine import eval_robust_device
 
     dev = torch.device("cuda", 0)
-    Cn, D, my = len(q["N2"]), refs.shape[0], sc.my
-    t = [torch.from_numpy(np.ascontiguousarray(q[k])).to(dev) for k in ("N2", "Nu", "d", "l")]
+    t, tr, tv = inputs
+    Cn, D, my = t[0].numel(), tr.shape[0], sc.my
     out = dict(mean=torch.empty((Cn, my), dtype=torch.float64, device=dev),
                worst=torch.empty((Cn, my), dtype=torch.float64, device=dev),
                n_failed=torch.empty(Cn, dtype=torch.int32, device=dev),
@@ -253,8 +273,16 @@ def _device_call(sc, q, refs, v, jb, with_J1=True):
                status=torch.empty(Cn, dtype=torch.int32, device=dev))
     if with_J1:
         out["J1"] = torch.empty((Cn * D, my), dtype=torch.float64, device=dev)
-    eval_robust_device(sc, *t, torch.from_numpy(refs).to(dev), out, v=torch.from_numpy(v).to(dev), j_bound=jb)
-    torch.cuda.synchronize(dev)
+    eval_robust_device(sc, *t, tr, out, v=tv, j_bound=jb, stream=stream)
+    return out
+
+
+def _device_call(sc, q, refs, v, jb, with_J1=True):
+    import torch
+
+    inputs = _device_inputs(q, refs, v)
+    out = _device_enqueue(sc, inputs, jb, with_J1)
+    torch.cuda.synchronize(torch.device("cuda", 0))
     return out
 
 
@@ -339,6 +367,300 @@ def test_generic_determinism_and_sentinels(gpu):
     for f in ("mean", "worst", "n_failed", "worst_draw", "status"):
         np.testing.assert_array_equal(bits(getattr(r, f)[::-1]), bits(getattr(a, f)), err_msg=f)
     _sentinels(sc, N2, Nu, d, l, refs, v, 0.0, a)
+
+
+# ---------------------------------------------------------------------------------------------
+# large batches: strided workgroups, a classifier of several passes, a dispatch order
+RECORD = ("mean", "worst", "n_failed", "worst_draw", "status")
+CLASSIFY_SLOTS = 1024   # robust_classify_kernel compacts this many slots per pass
+ORDER_MIN_C = 256       # order_candidates hands out a dispatch order from here (kOrderMinC)
+
+
+def with_invalid(N2, Nu, d, l, at):
+    """The batch with a sentinel (N2 = 0) at index at[0] and a bad horizon (Nu = 3 > N2 = 2) at at[1]
+    (indices of the result)."""
+    pos = [at[0], at[1] - 1]
+    N2, Nu = np.insert(N2, pos, [0, 2]).astype(np.int32), np.insert(Nu, pos, [1, 3]).astype(np.int32)
+    d, l = np.insert(d, pos, 1.0, axis=0), np.insert(l, pos, 1.0, axis=0)
+    assert N2[at[0]] == 0 and (N2[at[1]], Nu[at[1]]) == (2, 3)
+    return dict(N2=N2, Nu=Nu, d=d, l=l)
+
+
+def rows(q, idx):
+    return {k: np.ascontiguousarray(a[idx]) for k, a in q.items()}
+
+
+def robust(sc, q, refs, v, jb=0.0, want_J1=False):
+    from mpct.engine import eval_robust
+
+    return eval_robust(sc, q["N2"], q["Nu"], q["d"], q["l"], refs, v=v, j_bound=jb, want_J1=want_J1)
+
+
+def same_rows(a, b, idx_a, idx_b=None, J1=False):
+    """Candidates idx_a of a and idx_b of b (default: all, in order) carry the same bits."""
+    idx_b = np.arange(len(b.status)) if idx_b is None else idx_b
+    for f in RECORD:
+        np.testing.assert_array_equal(bits(getattr(a, f)[idx_a]), bits(getattr(b, f)[idx_b]), err_msg=f)
+    if J1:
+        np.testing.assert_array_equal(bits(a.J1.reshape(len(a.status), -1)[idx_a]),
+                                      bits(b.J1.reshape(len(b.status), -1)[idx_b]), err_msg="J1")
+
+
+def large_config4_batch(ncu):
+    """Candidates from the front of config4_candidates(10000) until the class with 2 Nu <= 16 has more
+    than 2 (4 ncu) members and the class above more than 2 (3 ncu), neither count a multiple of its
+    grid, C > 2048 and no multiple of 1024 (C counts the two invalid candidates added at the end).
+    Where the list runs out first (its upper class has 1,499 members: short of 2 x 768 on 256 CUs) it
+    is padded with repeats of members of the class that is short, pass p over the class with delta
+    scaled by 1.01^p and lambda by 1.01^-p, so that no candidate repeats another's controller.
+    Returns the batch with a sentinel at index 1500 and a bad horizon at 2000, and the two grids."""
+    from mpct.dtc import config4_candidates
+
+    N2a, Nua, da, la = config4_candidates(10000)
+    g16, g32 = 4 * ncu, 3 * ncu
+    upper = 2 * Nua > 16
+
+    def lo_ok(n):
+        return n > 2 * g16 and n % g16 != 0
+
+    def up_ok(n):
+        return n > 2 * g32 and n % g32 != 0
+
+    def c_ok(n):
+        return n > 2 * CLASSIFY_SLOTS and n % CLASSIFY_SLOTS != 0
+
+    n_lo, n_up, idx, power = 0, 0, [], []
+    for k in range(len(N2a)):
+        if lo_ok(n_lo) and up_ok(n_up) and c_ok(len(idx) + 2):
+            break
+        idx.append(k)
+        power.append(0)
+        n_up += int(upper[k])
+        n_lo += int(not upper[k])
+    members = {True: np.flatnonzero(upper), False: np.flatnonzero(~upper)}
+    taken = {True: 0, False: 0}
+    while not (lo_ok(n_lo) and up_ok(n_up) and c_ok(len(idx) + 2)):
+        cls = False if (up_ok(n_up) and not lo_ok(n_lo)) else True
+        m = members[cls]
+        idx.append(int(m[taken[cls] % len(m)]))
+        power.append(1 + taken[cls] // len(m))
+        taken[cls] += 1
+        n_up += int(cls)
+        n_lo += int(not cls)
+        assert len(idx) < 40 * ncu + 4 * CLASSIFY_SLOTS   # the padding ends
+    idx, f = np.array(idx), 1.01 ** np.array(power, dtype=float)[:, None]
+    q = with_invalid(N2a[idx], Nua[idx], da[idx] * f, la[idx] / f, (1500, 2000))
+    return q, g16, g32
+
+
+def median_gap_bound(J, pairs=101):
+    """Among the `pairs` adjacent pairs of the sorted finite totals centred on their median, the pair
+    with the largest ratio: (geometric midpoint, ratio)."""
+    t = np.sort(J[np.isfinite(J)])
+    m = len(t) // 2
+    lo = m - pairs // 2
+    a, b = t[lo:lo + pairs], t[lo + 1:lo + pairs + 1]
+    assert len(b) == pairs and a[0] > 0
+    k = int(np.argmax(b / a))
+    return float(np.sqrt(a[k]) * np.sqrt(b[k])), float(b[k] / a[k])
+
+
+def test_fused_large_batch_strides_and_orders(gpu):
+    """dtc_robust_kernel<16|32> where every workgroup takes at least three candidates of its class
+    list (the second iteration re-zeroes the gain pads and the per-wave state and reuses flag[0] and
+    the draw records), robust_classify_kernel over at least three passes with its carried counters,
+    and a dispatch order (C >= 256).  The batch-shape conditions are asserted on the inputs, the bound
+    conditions on the yardstick, before any comparison.
+    (a) 48 candidates -- the first and last of each class, those at positions grid - 1, grid and
+        2 grid of each class, the rest seeded -- evaluated in four 12-candidate calls (no dispatch
+        order, no second iteration) carry bitwise the large call's records and J1 rows.  The class
+        positions are taken in the caller's order: with a dispatch order the lists follow the sort's
+        keys, which the call does not return; (b) covers every candidate whatever its place.
+    (b) eval_batch on the same C x 5, reduced by reduce_np: compare() at 1e-9, the J1 sample by the
+        1e-9 / 1e-6 rule.
+    (c) the default bound and one that fails a real share of the draws, between two sorted totals
+        whose ratio is >= 1 + 1e-4 (fifty times the 1e-6 two kernels may differ by): no candidate is
+        excluded.
+    (d) repeated and reversed: the same bits per candidate.  (e) the device-pointer entry too."""
+    import time
+
+    import torch
+    from mpct.engine import robust_instance
+
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    sc, refs, v = mc(5)
+    assert robust_instance(sc) == "dtc_robust_kernel<16> + dtc_robust_kernel<32>"
+    q, g16, g32 = large_config4_batch(ncu)
+    N2, Nu = q["N2"], q["Nu"]
+    Cn, D = len(N2), 5
+    # ---- the batch's shape, on the inputs
+    valid = (N2 > 0) & (N2 <= 30) & (Nu >= 1) & (Nu <= 10) & (Nu <= N2)
+    lower, upper = np.flatnonzero(valid & (2 * Nu <= 16)), np.flatnonzero(valid & (2 * Nu > 16))
+    print("ncu %d: C = %d, %d candidates with 2 Nu <= 16 (grid %d), %d above (grid %d)" % (
+        ncu, Cn, len(lower), g16, len(upper), g32))
+    assert (g16, g32) == (4 * ncu, 3 * ncu)
+    assert len(lower) > 2 * g16 and len(upper) > 2 * g32          # every workgroup: three candidates or more
+    assert len(lower) % g16 != 0 and len(upper) % g32 != 0        # and the last round is partial
+    assert Cn > 2 * CLASSIFY_SLOTS and Cn % CLASSIFY_SLOTS != 0   # three passes or more, the last partial
+    assert Cn >= ORDER_MIN_C
+    invalid = np.flatnonzero(~valid)
+    # invalid candidates sort last (work_order.hip), so their dispatch slots are C - 2 and C - 1; their
+    # places in the caller's order are beyond the first pass too
+    assert invalid.tolist() == [1500, 2000] and N2[1500] == 0 and Nu[2000] > N2[2000] > 0
+    assert invalid.min() >= CLASSIFY_SLOTS and Cn - 2 >= CLASSIFY_SLOTS
+    # ---- the yardstick and the bound, on the yardstick
+    t0 = time.perf_counter()
+    J1, st = per_sim(sc, N2, Nu, q["d"], q["l"], refs, v)
+    t1 = time.perf_counter()
+    J = totals(J1, st)
+    jb, ratio = median_gap_bound(J[valid])
+    fail = ((st != 0) | ~np.isfinite(J) | (J > jb))[valid]
+    print("j_bound %.6g between totals of ratio 1 + %.3g; %.1f %% of the %d simulated draws fail it" % (
+        jb, ratio - 1.0, 100.0 * fail.mean(), fail.size))
+    assert ratio >= 1.0 + 1e-4
+    assert 0.05 <= fail.mean() <= 0.95
+    # ---- the 48 candidates of (a)
+    pick = []
+    for lst, g in ((lower, g16), (upper, g32)):   # 2 grid may be the last position: a set
+        pick += [int(lst[p]) for p in sorted({0, len(lst) - 1, g - 1, g, 2 * g})]
+    rest = np.setdiff1d(np.flatnonzero(valid), pick)
+    pick = np.array(sorted(pick + np.random.default_rng(48).choice(rest, 48 - len(pick), replace=False).tolist()))
+    assert len(np.unique(pick)) == 48
+    for jbound in (0.0, jb):
+        t2 = time.perf_counter()
+        res = robust(sc, q, refs, v, jbound, want_J1=True)
+        t3 = time.perf_counter()
+        same = np.array_equal(bits(res.J1.reshape(J1.shape)[valid]), bits(J1[valid]))
+        print("j_bound %g: eval_robust %.0f ms (eval_batch %.0f ms); J1 bitwise eval_batch's: %s" % (
+            jbound, 1e3 * (t3 - t2), 1e3 * (t1 - t0), bool(same)))
+        # (b), (c)
+        ref = reduce_np(J1, st, jbound if jbound else 1e100)
+        compare(res, ref, 1e-9, exact_worst=False)
+        sample_agrees(res.J1.reshape(J1.shape), J1, st)
+        assert res.status[1500] == 8 and res.status[2000] == 16
+        for k in (1500, 2000):
+            assert np.all(np.isnan(res.mean[k])) and np.all(np.isnan(res.worst[k]))
+            assert res.n_failed[k] == 0 and res.worst_draw[k] == -1 and np.all(np.isnan(res.J1.reshape(Cn, -1)[k]))
+        # (a)
+        for part in range(4):
+            sel = pick[part::4]
+            assert len(sel) == 12
+            same_rows(res, robust(sc, rows(q, sel), refs, v, jbound, want_J1=True), sel, J1=True)
+    assert (res.n_failed[valid] > 0).any() and (res.n_failed[valid] < D).any()
+    # (d)
+    same_rows(res, robust(sc, q, refs, v, jb, want_J1=True), np.arange(Cn), J1=True)
+    same_rows(res, robust(sc, rows(q, np.arange(Cn)[::-1]), refs, v, jb, want_J1=True), np.arange(Cn)[::-1], J1=True)
+    # (e)
+    dv = _device_call(sc, q, refs, v, jb)
+    for f in RECORD + ("J1",):
+        np.testing.assert_array_equal(bits(dv[f].cpu().numpy()), bits(getattr(res, f)), err_msg=f)
+
+
+def shell_large(n, at):
+    from mpct.scenarios import candidate_grid, shell3x3, vns_step_refs
+
+    sc, _, _ = shell3x3(n2_max=30, nu_max=5)
+    return sc, with_invalid(*candidate_grid(n), at), vns_step_refs(3, sc.nit)
+
+
+def test_generic_large_batch(gpu):
+    """The generic path at C >= 256: gpc_small_kernel in dispatch order (a non-null perm, its records
+    staged and gathered back) writing only J1 and status into the caller's sample or the scenario's
+    robust scratch, then robust_reduce_kernel.  Shell 3x3, 320 grid candidates and two invalid ones x 3
+    step references.  With want_J1 the sample is bitwise eval_batch's and the records are reduce_np's
+    (1e-12 on the mean, everything else exact); without it (scenario scratch) and with the batch
+    reversed the same bits per candidate."""
+    from mpct.engine import robust_instance
+
+    sc, q, refs = shell_large(320, (100, 301))
+    Cn = len(q["N2"])
+    assert Cn == 322 and Cn >= ORDER_MIN_C
+    assert robust_instance(sc) == "gpc_small_kernel + robust_reduce_kernel"
+    J1, st = per_sim(sc, q["N2"], q["Nu"], q["d"], q["l"], refs, None)
+    assert st[100].tolist() == [8] * 3 and st[301].tolist() == [16] * 3
+    # a bound inside the totals, so that draws fail: the per-simulation bits are the yardstick's own and
+    # a total of three terms differs between numpy's sum and the sequential one by a few ulp (4e-16)
+    # at the most, so a gap of 1e-9 between the two totals around the bound is ample
+    valid = (q["N2"] > 0) & (q["Nu"] <= q["N2"])
+    jb, ratio = median_gap_bound(totals(J1, st)[valid])
+    assert ratio >= 1.0 + 1e-9
+    ref = reduce_np(J1, st, jb)
+    assert 0.05 <= 1.0 - ref["surv"][valid].mean() <= 0.95   # the share of the simulated draws that fail
+    res = robust(sc, q, refs, None, jb, want_J1=True)
+    print("C = %d: j_bound %.6g (ratio 1 + %.3g), %d candidates with failed draws" % (
+        Cn, jb, ratio - 1.0, int((ref["n_failed"] > 0).sum())))
+    np.testing.assert_array_equal(bits(res.J1.reshape(J1.shape)), bits(J1))
+    compare(res, ref, 1e-12, exact_worst=True)
+    assert res.status[100] == 8 and res.status[301] == 16
+    same_bits(robust(sc, q, refs, None, jb), res)
+    same_rows(res, robust(sc, rows(q, np.arange(Cn)[::-1]), refs, None, jb, want_J1=True), np.arange(Cn)[::-1], J1=True)
+
+
+def test_more_draws_than_the_fused_kernel_holds(config4):
+    """D = 129 is one draw more than the fused kernel's LDS record array holds (kRobustMaxD = 128):
+    the call takes the generic route (dtc_small_kernel + robust_reduce_kernel), so the J1 sample is
+    bitwise eval_batch's, the records are exact against reduce_np, and the call gives the same
+    record bits with and without the sample."""
+    sc, refs, v = mc(129)
+    q = config4
+    J1, st = per_sim(sc, q["N2"], q["Nu"], q["d"], q["l"], refs, v)
+    ref = reduce_np(J1, st, q["jb"])
+    res = robust(sc, q, refs, v, q["jb"], want_J1=True)
+    print("D = 129: n_failed %s" % ref["n_failed"].tolist())
+    np.testing.assert_array_equal(bits(res.J1.reshape(J1.shape)), bits(J1))
+    compare(res, ref, 1e-12, exact_worst=True)
+    same_bits(robust(sc, q, refs, v, q["jb"]), res)
+
+
+def _two_streams(make, calls, jb):
+    """make() -> (scenario, refs, v); calls: the candidate batches A, B.  A on stream 1, B on stream 2,
+    A again on stream 1, enqueued back to back through the device-pointer entry with no host
+    synchronisation between them, each into its own output tensors, against a fresh scenario's
+    host-entry calls."""
+    import torch
+
+    dev = torch.device("cuda", 0)
+    sc, refs, v = make()
+    fresh = make()[0]
+    want = [robust(fresh, q, refs, v, jb) for q in calls]
+    fresh.close()
+    inputs = [_device_inputs(q, refs, v) for q in calls]
+    streams = [torch.cuda.Stream(dev), torch.cuda.Stream(dev)]
+    torch.cuda.synchronize(dev)   # inputs resident; from here to the end nothing waits on the host
+    outs = [_device_enqueue(sc, inputs[k], jb, with_J1=False, stream=streams[k]) for k in (0, 1, 0)]
+    torch.cuda.synchronize(dev)
+    for out, k in zip(outs, (0, 1, 0)):
+        for f in RECORD:
+            np.testing.assert_array_equal(bits(out[f].cpu().numpy()), bits(getattr(want[k], f)),
+                                          err_msg="call %d %s" % (k, f))
+    sc.close()
+
+
+def test_robust_device_calls_on_two_streams(gpu):
+    """Two device-entry calls on one scenario and two streams, and the first again (modelled on
+    tests/test_gpu_parity.py::test_two_streams_share_a_scenario).  Generic route, Shell 3x3: 64
+    candidates on stream 1; 320 on stream 2, for which the robust scratch regrows and a dispatch order
+    exists; the 64 again on stream 1, in the regrown scratch behind the second call's event.  Without
+    a J1 of the caller's the per-simulation records of all three live in that one scratch.  Fused
+    route, config 4 at D = 5: 12 candidates, then 600 (the candidate lists regrow), then the 12."""
+    from mpct.dtc import config4_candidates
+    from mpct.scenarios import candidate_grid, shell3x3, vns_step_refs
+
+    grid = dict(zip(("N2", "Nu", "d", "l"), candidate_grid(384)))
+
+    def make_shell():
+        sc = shell3x3(n2_max=30, nu_max=5)[0]
+        return sc, vns_step_refs(3, sc.nit), None
+
+    _two_streams(make_shell, [rows(grid, np.arange(64)), rows(grid, np.arange(64, 384))], 0.0)
+
+    def make_mc():
+        from mpct.dtc import woodberry_mc
+
+        return woodberry_mc(draws=5, n2_max=30, nu_max=10, nit=200)[:3]
+
+    c4 = dict(zip(("N2", "Nu", "d", "l"), config4_candidates(10000)))
+    _two_streams(make_mc, [rows(c4, np.arange(12)), rows(c4, np.arange(12, 612))], 0.0)
 
 
 # ---------------------------------------------------------------------------------------------
