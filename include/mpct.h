@@ -218,6 +218,26 @@ typedef struct mpct_nmpc_desc {
 /* Build a nonlinear MPC scenario (no device needed).  Returns MPCT_OK. */
 int32_t mpct_nmpc_scenario_create(const mpct_nmpc_desc* desc, mpct_scenario** out);
 
+/* The same scenario with a simulated plant that is not the controller's model (an addition to ABI 7:
+ * no struct, export or behaviour changes).  The reference's seam keeps the two apart: `model` is the
+ * plant handle integrated at closedloop_toolbox_nmpc.m:71 and :91, the controller predicts with
+ * nmpcobj.Model.StateFcn and is fed the measured plant state (:69): full state feedback, no estimator,
+ * so a steady-state offset under mismatch is part of the result.
+ *   nplant = 0      exactly mpct_nmpc_scenario_create; plant_params and plant_x0 must be NULL
+ *   nplant >= 1     simulation s = c*nref + k runs plant variant k % nplant (the convention of
+ *                   mpct_scenario_desc.nplant / plant_var)
+ *   plant_params    [nplant][16], each row in the order of desc->params
+ *   plant_x0        [nplant][nx] start state of each variant, or NULL: every variant starts at desc->x0
+ * The controller keeps desc->params for the prediction, its tangents, the Armijo trials and the
+ * linearised state rows.  Variant k's parameters integrate the closed-loop plant step from variant k's
+ * x0, and the plant of the open-loop leg (ys) too; the open-loop controller call starts from the
+ * variant's x0.  open_loop and want_traj stay legal.  A draw whose states leave x_min / x_max comes
+ * back with MPCT_ST_BOUNDS: a result, not an error (mpct_eval_robust counts it as a failed draw).
+ * MPCT_EINVAL: nplant < 0; nplant = 0 with a non-NULL table; nplant >= 1 with plant_params NULL; a
+ * non-finite parameter or start state; a variant with rho*cp*V = 0. */
+int32_t mpct_nmpc_scenario_create_var(const mpct_nmpc_desc* desc, int32_t nplant, const double* plant_params,
+                                      const double* plant_x0, mpct_scenario** out);
+
 /* Evaluation options. */
 typedef struct mpct_opts {
   int32_t open_loop;   /* 1: also compute the open-loop first-move prediction (uopt, ys) and

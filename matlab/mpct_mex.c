@@ -10,7 +10,9 @@
  *   v = mpct_mex('version')                          ABI version of the loaded libmpct
  *   h = mpct_mex('create', desc)                     linear scenario (mpct_scenario_create, or
  *                                                    mpct_scenario_create_est when desc.estimator ~= 0)
- *   h = mpct_mex('create_nmpc', desc)                NMPC scenario (mpct_nmpc_scenario_create)
+ *   h = mpct_mex('create_nmpc', desc)                NMPC scenario (mpct_nmpc_scenario_create;
+ *                                                    mpct_nmpc_scenario_create_var when desc.plant_params
+ *                                                    or desc.plant_x0 is given)
  *   [J1,j21,j22,Jnu,status,iters,y,u,ys,uopt] = mpct_mex('eval', h, N2, Nu, delta, lambda, r, v, opts)
  *   [...] = mpct_mex('eval_multi', h, devices, N2, Nu, delta, lambda, r, v, opts)
  *   name = mpct_mex('instance', h, opts)             kernel instance an eval launches
@@ -304,8 +306,23 @@ static void cmd_create_nmpc(mxArray* plhs[], const mxArray* d) {
   D.vns_ink = (int32_t)fscalar(d, "vns_ink", 10);
   D.sqp_max = (int32_t)fscalar(d, "sqp_max", 0);
   D.sqp_tol = fscalar(d, "sqp_tol", 0.0);
+  /* optional fields plant_params (16 x nplant, one column per simulated plant in the params order) and
+   * plant_x0 (nx x nplant start states; absent: x0 for all): the plant is not the model
+   * (mpct_nmpc_scenario_create_var); both absent is mpct_nmpc_scenario_create */
+  const mxArray* pp = field(d, "plant_params", 0);
+  const mxArray* px = field(d, "plant_x0", 0);
   mpct_scenario* s = NULL;
-  if (mpct_nmpc_scenario_create(&D, &s) != MPCT_OK) lib_error("mpct:create_nmpc");
+  if (pp || px) {
+    if (!pp) mexErrMsgIdAndTxt("mpct:desc", "plant_x0 needs plant_params");
+    const size_t np = mxGetNumberOfElements(pp) / 16;
+    if (np < 1 || np * 16 != mxGetNumberOfElements(pp))
+      mexErrMsgIdAndTxt("mpct:desc", "plant_params must be 16 x nplant");
+    const double* P = doubles(pp, (long)(np * 16), "plant_params");
+    const double* X = px ? doubles(px, (long)np * D.nx, "plant_x0") : NULL;
+    if (mpct_nmpc_scenario_create_var(&D, (int32_t)np, P, X, &s) != MPCT_OK) lib_error("mpct:create_nmpc");
+  } else if (mpct_nmpc_scenario_create(&D, &s) != MPCT_OK) {
+    lib_error("mpct:create_nmpc");
+  }
   plhs[0] = new_handle(s);
 }
 

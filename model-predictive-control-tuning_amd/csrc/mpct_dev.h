@@ -130,6 +130,9 @@ struct DevScenario {
   double ts, sqp_tol;
   const int* xc;          // [my] output states (0-based)
   const double* nm;       // [NM_NPAR][x0 3][u0 nu][u_min nu][u_max nu][x_min 3][x_max 3][s_y my][s_u nu]
+  // plant variants of the NMPC kernel (mpct_nmpc_scenario_create_var; nullptr: the plant is the model):
+  // [nvar][NM_NPAR + 3], row k % nvar = simulation k's plant parameters, then its start state
+  const double* nmv;
 };
 
 struct DevOpts {

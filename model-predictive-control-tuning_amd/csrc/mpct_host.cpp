@@ -98,6 +98,11 @@ extern "C" int32_t mpct_scenario_create_est(const mpct_scenario_desc* d, int32_t
 }
 
 extern "C" int32_t mpct_nmpc_scenario_create(const mpct_nmpc_desc* d, mpct_scenario** out) {
+  return mpct_nmpc_scenario_create_var(d, 0, nullptr, nullptr, out);
+}
+
+extern "C" int32_t mpct_nmpc_scenario_create_var(const mpct_nmpc_desc* d, int32_t nplant, const double* plant_params,
+                                                 const double* plant_x0, mpct_scenario** out) {
   if (!d || !out) return fail(MPCT_EINVAL, "null argument");
   *out = nullptr;
   BuildError err;
@@ -107,7 +112,20 @@ extern "C" int32_t mpct_nmpc_scenario_create(const mpct_nmpc_desc* d, mpct_scena
   for (int m = 1; m <= d->nu * d->nu_max; ++m)
     for (int n = 1; n <= d->n_max; ++n) lds_all = std::max(lds_all, nmpc_lds_bytes(m, n));
   if (lds_all > 64 * 1024) return fail(MPCT_ERANGE, "n_max x nu*nu_max needs more than 64 KiB of LDS per simulation");
-  return created(build_nmpc_scenario(*d, &err), err, out);
+  // the plant variants (nx = 3 holds: nmpc_dims_ok)
+  if (nplant < 0) return fail(MPCT_EINVAL, "nplant must be >= 0");
+  if (nplant == 0 && (plant_params || plant_x0))
+    return fail(MPCT_EINVAL, "nplant = 0 takes no plant_params and no plant_x0");
+  if (nplant > 0 && !plant_params) return fail(MPCT_EINVAL, "nplant >= 1 needs plant_params");
+  for (int k = 0; k < nplant; ++k) {
+    const double* q = plant_params + (size_t)k * NM_NPAR;
+    for (int i = 0; i < NM_NPAR; ++i)
+      if (!std::isfinite(q[i])) return fail(MPCT_EINVAL, "non-finite plant parameter");
+    if (q[NM_RHO] * q[NM_CP] * q[NM_V] == 0.0) return fail(MPCT_EINVAL, "plant variant with rho*cp*V = 0");
+    for (int i = 0; plant_x0 && i < d->nx; ++i)
+      if (!std::isfinite(plant_x0[(size_t)k * d->nx + i])) return fail(MPCT_EINVAL, "non-finite plant_x0");
+  }
+  return created(build_nmpc_scenario(*d, &err, nplant, plant_params, plant_x0), err, out);
 }
 
 static void ctx_release(DevCtx* c) {
@@ -773,6 +791,8 @@ static int32_t copy_name(const std::string& nm, char* buf, int32_t cap) {
 }
 
 static std::string per_simulation_instance(const mpct_scenario* s, bool ext) {
+  if (s->nmpc && !s->nmv.empty())
+    return "nmpc_closed_loop_kernel<..., plant variants> (QP-size x LDS-tier class launches)";
   if (s->nmpc) return "nmpc_closed_loop_kernel (QP-size x LDS-tier class launches)";
   if (s->mdband && s->est)
     return "mdband_closed_loop_kernel (QP-size x LDS-tier class launches) + output-bias estimator";

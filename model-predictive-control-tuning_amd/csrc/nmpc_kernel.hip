@@ -55,8 +55,14 @@ struct StateMark {
 };
 
 // one wave per SIMD (342 VGPRs): capped at 2 or 3 waves the kernel spills and config 5 ran 27 %
-// slower (profiles/r02i_nmpc_code_size.txt)
-template <int MAXM>
+// slower (profiles/r02i_nmpc_code_size.txt).
+// VAR: the simulated plant is not the controller's model (mpct_nmpc_scenario_create_var): simulation
+// (c, k) integrates the parameters of row k % nvar of sc.nmv from that row's start state, in the
+// closed-loop plant step, the open-loop leg's plant step and the plant steps of mpass's speculation;
+// the prediction, its tangents, the Armijo trials and the linearised state rows keep the model's P
+// (full state feedback, closedloop_toolbox_nmpc.m:69-71: no estimator).  VAR = false instances are
+// the code they were
+template <int MAXM, bool VAR>
 __global__ void __launch_bounds__(64, 1)
     nmpc_closed_loop_kernel(const DevScenario sc, long long C, int nref, const int* __restrict__ Nv,
                             const int* __restrict__ Nuv, const double* __restrict__ deltav,
@@ -131,8 +137,11 @@ __global__ void __launch_bounds__(64, 1)
 
   const double* tab = sc.nm;  // [params][x0 3][u0 nu][lb nu][ub nu][xmin 3][xmax 3][sy ny][su nu]
   const VdV P = vdv_load(tab);
-  const double* tx0 = tab + NM_NPAR;
-  const double* tu0 = tx0 + 3;
+  // the plant: this simulation's variant row [NM_NPAR parameters][x0 3] (wave-uniform), or the model
+  const double* ptab = VAR ? sc.nmv + (size_t)(kref % sc.nvar) * (NM_NPAR + 3) : tab;
+  const VdV Pp = VAR ? vdv_load(ptab) : P;
+  const double* tx0 = ptab + NM_NPAR;
+  const double* tu0 = tab + NM_NPAR + 3;
   const double* tlb = tu0 + nu;
   const double* tub = tlb + nu;
   const double* txmin = tub + nu;
@@ -261,7 +270,9 @@ __global__ void __launch_bounds__(64, 1)
           const double m1 = nu > 1 && j - 1 < Nu ? gv[Nu + j - 1] : 0.0;
           const double u1[2] = {ug0 + m0, nu > 1 ? ug1 + m1 : 0.0};
           double xn[3] = {xs[0], xs[1], xs[2]};
-          vdv_rk4<false>(P, h, nsub, xn, u1, nullptr, nullptr);
+          // the plant's own step (Pp): the speculated call must start from bitwise the state the
+          // closed loop reaches below
+          vdv_rk4<false>(Pp, h, nsub, xn, u1, nullptr, nullptr);
           if (j <= dg) {
             xs[0] = xn[0];
             xs[1] = xn[1];
@@ -749,7 +760,7 @@ __global__ void __launch_bounds__(64, 1)
       double un[2] = {ul[0] + sxc[0], nu > 1 ? ul[1] + sxc[Nu] : 0.0};
       lds_sync();
       PSTAMP(PROF_NM_OTHER);
-      vdv_rk4<false>(P, h, nsub, x, un, nullptr, nullptr);
+      vdv_rk4<false>(Pp, h, nsub, x, un, nullptr, nullptr);
       PSTAMP(PROF_NM_PLANT);
       ul[0] = un[0];
       ul[1] = un[1];
@@ -760,7 +771,7 @@ __global__ void __launch_bounds__(64, 1)
       if (o.open_loop) {
         const int l = t < Nu - 1 ? t : Nu - 1;
         const double uo[2] = {sUo[l], nu > 1 ? sUo[Nu + l] : 0.0};
-        vdv_rk4<false>(P, h, nsub, xo, uo, nullptr, nullptr);
+        vdv_rk4<false>(Pp, h, nsub, xo, uo, nullptr, nullptr);
       }
     }
     for (int i = 0; i < 3; ++i) inb = inb && x[i] >= txmin[i] - 1e-9 && x[i] <= txmax[i] + 1e-9;
@@ -834,7 +845,7 @@ long long nmpc_lds_bytes(int M, int N) { return (long long)nm_layout(M, N, nm_gr
 // streams of launch_fan.h so the tiers overlap; a simulation runs in the launch of its class and
 // tier, and the light tiers (short horizons) get the occupancy their own LDS allows instead of
 // the n_max-sized allocation of the heaviest candidate
-template <int MAXM>
+template <int MAXM, bool VAR>
 static int launch_nmpc_t(const DevScenario& sc, long long C, int nref, const int* N, const int* Nu, const double* delta,
                          const double* lambda, const double* r, const int* perm, const DevOpts& o,
                          const DevResult& out, FanScope& fs, int& nl, int mz_lo, bool& first, std::string* err) {
@@ -857,7 +868,7 @@ static int launch_nmpc_t(const DevScenario& sc, long long C, int nref, const int
   for (int k = ncls - 1; k >= 0; --k) {
     const hipStream_t ls = fs.stream(nl);
     if (!diag_drop_launch(nl++))
-      hipLaunchKernelGGL(nmpc_closed_loop_kernel<MAXM>, dim3((unsigned)(C * nref)), dim3(kWave), (size_t)hi[k], ls, sc,
+      hipLaunchKernelGGL((nmpc_closed_loop_kernel<MAXM, VAR>), dim3((unsigned)(C * nref)), dim3(kWave), (size_t)hi[k], ls, sc,
                          C, nref, N, Nu, delta, lambda, r, perm, o, out, mz_lo, lo[k], hi[k], first ? 1 : 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -895,8 +906,16 @@ int launch_nmpc(const DevScenario& sc, long long C, int nref, const int* N, cons
   FanScope fs(fan, stream);  // forks after the sort: every class launch waits for the permutation
   int nl = 0;
   bool first = true;  // the first launch also writes the padding / bad-horizon statuses
-  if (Mmax > 15) rc = launch_nmpc_t<32>(sc, C, nref, N, Nu, delta, lambda, r, perm, o, out, fs, nl, 15, first, err);
-  if (rc == 0) rc = launch_nmpc_t<16>(sc, C, nref, N, Nu, delta, lambda, r, perm, o, out, fs, nl, 0, first, err);
+  // plant variants (sc.nmv): the same launches of the VAR = true instances
+  if (sc.nmv) {
+    if (Mmax > 15)
+      rc = launch_nmpc_t<32, true>(sc, C, nref, N, Nu, delta, lambda, r, perm, o, out, fs, nl, 15, first, err);
+    if (rc == 0) rc = launch_nmpc_t<16, true>(sc, C, nref, N, Nu, delta, lambda, r, perm, o, out, fs, nl, 0, first, err);
+  } else {
+    if (Mmax > 15)
+      rc = launch_nmpc_t<32, false>(sc, C, nref, N, Nu, delta, lambda, r, perm, o, out, fs, nl, 15, first, err);
+    if (rc == 0) rc = launch_nmpc_t<16, false>(sc, C, nref, N, Nu, delta, lambda, r, perm, o, out, fs, nl, 0, first, err);
+  }
   fs.join();
   if (perm) order_mark_used(*wo, stream);  // after the join: every class launch has read it
   return rc;

@@ -71,6 +71,7 @@ struct mpct_scenario {
   double ts = 0.0, sqp_tol = 1e-8;
   std::vector<int> xc;      // [ny] 0-based output states
   std::vector<double> nm;   // see DevScenario::nm
+  std::vector<double> nmv;  // plant variants [nvar][NM_NPAR + 3] (DevScenario::nmv); empty: plant = model
   // device state, one context per device ordinal (created on first use, kept until destroy):
   // a scenario can be evaluated on several GPUs of one process (mpct_eval_batch_multi)
   std::vector<DevCtx*> ctx;
@@ -558,7 +559,12 @@ inline bool nmpc_dims_ok(const mpct_nmpc_desc& d, BuildError* err) {
   return true;
 }
 
-inline std::unique_ptr<mpct_scenario> build_nmpc_scenario(const mpct_nmpc_desc& d, BuildError* err) {
+// nplant plant variants (mpct_nmpc_scenario_create_var, which validates them: finite values,
+// rho*cp*V != 0, no table with nplant = 0): plant_params [nplant][NM_NPAR] in the params order,
+// plant_x0 [nplant][nx] or NULL (every variant starts at d.x0).  nplant = 0: the plant is the model
+inline std::unique_ptr<mpct_scenario> build_nmpc_scenario(const mpct_nmpc_desc& d, BuildError* err, int nplant = 0,
+                                                          const double* plant_params = nullptr,
+                                                          const double* plant_x0 = nullptr) {
   if (!nmpc_dims_ok(d, err)) return nullptr;
   if (!(d.ts > 0.0) || d.nsub < 1) return reject(err, MPCT_EINVAL, "ts must be > 0 and nsub >= 1");
   if (!d.xc || !d.x0 || !d.u0 || !d.u_min || !d.u_max || !d.x_min || !d.x_max || !d.y_scale || !d.u_scale || !d.yref)
@@ -588,7 +594,8 @@ inline std::unique_ptr<mpct_scenario> build_nmpc_scenario(const mpct_nmpc_desc& 
   for (int j = 0; j < d.ny; ++j) s->xc.push_back(d.xc[j] - 1);
   const double* p = d.params ? d.params : kVdvParams;
   s->nm.assign(p, p + NM_NPAR);
-  auto app = [&](const double* a, int n) { s->nm.insert(s->nm.end(), a, a + n); };
+  auto app_to = [](std::vector<double>& t, const double* a, int n) { t.insert(t.end(), a, a + n); };
+  auto app = [&](const double* a, int n) { app_to(s->nm, a, n); };
   app(d.x0, 3);
   app(d.u0, d.nu);
   app(d.u_min, d.nu);
@@ -598,6 +605,13 @@ inline std::unique_ptr<mpct_scenario> build_nmpc_scenario(const mpct_nmpc_desc& 
   app(d.y_scale, d.ny);
   app(d.u_scale, d.nu);
   s->yref.assign(d.yref, d.yref + (size_t)d.ny * d.nit);
+  if (nplant > 0 && plant_params) {
+    s->nvar = nplant;
+    for (int k = 0; k < nplant; ++k) {
+      app_to(s->nmv, plant_params + (size_t)k * NM_NPAR, NM_NPAR);
+      app_to(s->nmv, plant_x0 ? plant_x0 + (size_t)k * d.nx : d.x0, 3);
+    }
+  }
   return s;
 }
 
@@ -891,6 +905,8 @@ inline PackedTables pack_tables(const mpct_scenario* s) {
   putd(&DevScenario::wscale, s->wscale);
   puti(&DevScenario::xc, s->xc);
   putd(&DevScenario::nm, s->nm);
+  putd(&DevScenario::nmv, s->nmv);
+  if (s->nmv.empty()) p.dslots.pop_back();  // plant = model: the pointer stays null
   putd(&DevScenario::gram, gram);
   if (gram.empty()) p.dslots.pop_back();  // not built: the pointer stays null (its padding stays in the blob)
   putd(&DevScenario::sm_coef, smt.coef);

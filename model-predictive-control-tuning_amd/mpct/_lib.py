@@ -91,7 +91,7 @@ EXPORTS = [
     "mpct_scenario_table", "mpct_eval_batch", "mpct_eval_batch_device", "mpct_lds_bytes", "mpct_lds_bytes_opts",
     "mpct_nmpc_scenario_create", "mpct_eval_batch_multi", "mpct_shard_candidates", "mpct_kernel_instance",
     "mpct_rank_device", "mpct_eval_robust", "mpct_eval_robust_device", "mpct_robust_instance",
-    "mpct_scenario_create_est",
+    "mpct_scenario_create_est", "mpct_nmpc_scenario_create_var",
 ]
 
 ABI_VERSION = 7
@@ -136,6 +136,9 @@ def load():
     lib.mpct_scenario_create_est.restype = C.c_int32
     lib.mpct_nmpc_scenario_create.argtypes = [C.POINTER(MpctNmpcDesc), C.POINTER(C.c_void_p)]
     lib.mpct_nmpc_scenario_create.restype = C.c_int32
+    lib.mpct_nmpc_scenario_create_var.argtypes = [C.POINTER(MpctNmpcDesc), C.c_int32, c_double_p, c_double_p,
+                                                  C.POINTER(C.c_void_p)]
+    lib.mpct_nmpc_scenario_create_var.restype = C.c_int32
     lib.mpct_scenario_destroy.argtypes = [C.c_void_p]
     lib.mpct_scenario_destroy.restype = None
     lib.mpct_scenario_table.argtypes = [C.c_void_p, C.c_int32, c_double_p, C.c_int64]

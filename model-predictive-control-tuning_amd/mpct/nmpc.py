@@ -1,9 +1,10 @@
 """Nonlinear MPC host mirror (config 5): the Van de Vusse reactor of ``VanDeVusse_NMPC.m`` over the
-libmpct C ABI (``mpct_nmpc_scenario_create``, include/mpct.h).
+libmpct C ABI (``mpct_nmpc_scenario_create``, ``mpct_nmpc_scenario_create_var``, include/mpct.h).
 
   NmpcScenario              the candidate-independent part of ``closedloop_toolbox_nmpc``'s
                             arguments (nmpcobj constraints / scales, model, init, Yref)
   vandevusse()              the driver's scenario (``VanDeVusse_NMPC.m:35-185``)
+  vandevusse_mc()           the same controller on plant-parameter draws (model error case, :29)
   closedloop_toolbox_nmpc   drop-in for ``closedloop_toolbox_nmpc.m:1`` (one candidate)
 
 Evaluate batches with ``mpct.engine.eval_batch`` / ``eval_batch_device`` exactly as for the
@@ -87,7 +88,10 @@ class NmpcScenario:
 
     def __init__(self, x0, u0, u_min, u_max, x_min, x_max, yref, n_max, nu_max, ts=VDV_TS, nsub=10,
                  xc=VDV_XC, params=VDV_PARAMS, y_scale=None, u_scale=None, vns_ink=10, sqp_max=100,
-                 sqp_tol=1e-8):
+                 sqp_tol=1e-8, plant_params=None, plant_x0=None):
+        """plant_params [nplant][16]: the simulated plants (reference set k runs row k % nplant) when
+        they are not the controller's model ``params``; plant_x0 [nplant][3]: their start states
+        (None: x0 for all).  Both None: the plant is the model (``mpct_nmpc_scenario_create``)."""
         self.lib = _lib.load()
         self.yref = np.ascontiguousarray(np.asarray(yref, dtype=float).reshape(len(xc), -1))
         self.my, self.nu, self.nd, self.nq = len(xc), 2, 0, 0
@@ -118,9 +122,25 @@ class NmpcScenario:
         d.yref = self.yref.ctypes.data_as(_lib.c_double_p)
         d.vns_ink, d.sqp_max, d.sqp_tol = int(vns_ink), int(sqp_max), float(sqp_tol)
         h = C.c_void_p()
-        rc = self.lib.mpct_nmpc_scenario_create(C.byref(d), C.byref(h))
+        self.nplant = 0
+        if plant_params is None and plant_x0 is None:
+            rc = self.lib.mpct_nmpc_scenario_create(C.byref(d), C.byref(h))
+        else:
+            pp = px = None
+            if plant_params is not None:
+                pp = self._keep["plant_params"] = np.ascontiguousarray(
+                    np.asarray(plant_params, dtype=float).reshape(-1, VDV_PARAMS.size))
+                self.nplant = pp.shape[0]
+            if plant_x0 is not None:
+                px = self._keep["plant_x0"] = np.ascontiguousarray(np.asarray(plant_x0, dtype=float).reshape(-1, 3))
+                if pp is not None and px.shape[0] != pp.shape[0]:
+                    raise ValueError("plant_x0 needs one row per plant variant")
+            rc = self.lib.mpct_nmpc_scenario_create_var(
+                C.byref(d), self.nplant, pp.ctypes.data_as(_lib.c_double_p) if pp is not None else None,
+                px.ctypes.data_as(_lib.c_double_p) if px is not None else None, C.byref(h))
         if rc != 0:
-            raise MpctError("mpct_nmpc_scenario_create failed (%d): %s" % (rc, _lib.last_error()))
+            raise MpctError("mpct_nmpc_scenario_create%s failed (%d): %s"
+                            % ("" if plant_params is None and plant_x0 is None else "_var", rc, _lib.last_error()))
         self._h = h
         self.x0 = self._keep["x0"]
         self.u0 = self._keep["u0"]
@@ -149,6 +169,47 @@ def vandevusse(n_max=31, nu_max=15, nit=VDV_NIT, nsub=10):
     x0 = steady_state()
     r, yref = vandevusse_signals(x0, nit)
     sc = NmpcScenario(x0, VDV_U0, VDV_UMIN, VDV_UMAX, VDV_XMIN, VDV_XMAX, yref, n_max, nu_max, nsub=nsub)
+    return sc, r, yref
+
+
+VDV_MC_EK, VDV_MC_EH = 0.05, 0.05   # vandevusse_mc defaults (ours, not the reference's: see there)
+
+
+def vandevusse_mc_params(D, e_k=VDV_MC_EK, e_h=VDV_MC_EH, seed=20250311, params=VDV_PARAMS):
+    """[D][16] plant parameters: row 0 the model, rows k >= 1 with k10, k20, k30 each times
+    1 + U(-e_k, e_k) and dHab, dHbc, dHad each times 1 + U(-e_h, e_h) (six independent factors a
+    draw, fixed seed; the draws do not depend on D)."""
+    rng = np.random.default_rng(seed)
+    P = np.tile(np.asarray(params, dtype=float), (int(D), 1))
+    for k in range(1, int(D)):
+        f = rng.uniform(-1.0, 1.0, size=6)
+        P[k, 0:3] *= 1.0 + e_k * f[:3]
+        P[k, 6:9] *= 1.0 + e_h * f[3:]
+    return P
+
+
+def vandevusse_mc(D, e_k=VDV_MC_EK, e_h=VDV_MC_EH, seed=20250311, n_max=31, nu_max=15, nit=VDV_NIT, nsub=10):
+    """The VanDeVusse_NMPC.m controller on D plants (``nominal = false``, the model error case the
+    driver declares at :29 and never uses): returns (sc, r[D], yref) for ``eval_robust`` /
+    ``eval_batch``, reference set k running plant k.
+
+    Draw 0 is the model itself; draws k >= 1 are ``vandevusse_mc_params``.  Each plant starts at its
+    OWN steady state at u0 (``steady_state(params=p_k)``: :78 applied to the plant), and r[k] is
+    ``vandevusse_signals`` of that state, so before the setpoint steps each loop is asked to hold the
+    plant where it rests.  Yref is the nominal scenario's: J1 therefore includes the shift of the
+    operating point (the squared distance between the plant's and the model's resting outputs over
+    the first samples), not only the transient's mismatch.
+
+    The default half-widths e_k = e_h = 0.05 are ours, not the reference's: the first value tried,
+    kept because on the CPU reference loop (tests/nmpc_mismatch_ref.py) the committed tuning
+    (VDV_TUNED) keeps every state inside x_min / x_max on all of 8 draws; nothing had to shrink."""
+    P = vandevusse_mc_params(D, e_k, e_h, seed)
+    X0 = np.array([steady_state(params=p) for p in P])
+    x0 = steady_state()
+    _, yref = vandevusse_signals(x0, nit)
+    r = np.array([vandevusse_signals(xk, nit)[0] for xk in X0])
+    sc = NmpcScenario(x0, VDV_U0, VDV_UMIN, VDV_UMAX, VDV_XMIN, VDV_XMAX, yref, n_max, nu_max, nsub=nsub,
+                      plant_params=P, plant_x0=X0)
     return sc, r, yref
 
 

@@ -22,9 +22,16 @@ the same size, which fills the GPU alike) and with an estimator scenario whose 8
 the model (the nominal loops bit for bit, so its time over the equal-size nominal launch is what the
 second plant copy and the two-copy LDS tiers cost; the mismatched draws solve other QPs).
 
+--workload vandevusse: the Van de Vusse NMPC on plant-parameter draws (mpct.nmpc.vandevusse_mc): the
+4,096-candidate config-5 grid x 8 draws through eval_robust_device, interleaved with the nominal scenario
+on the same 8 signal rows (a launch of the same size) and with a variant scenario whose 8 plants all
+equal the model from the model's x0 (the nominal loops bit for bit: its time over the nominal launch is
+what the VAR = true instances cost; the mismatched draws solve other problems).
+
 python tools/robust_bench.py [--candidates C] [--draws D] [--reps N] [--out profiles/r07_robust_bench.json]
 python tools/robust_bench.py --workload shell3x3 [--baseline-lib PATH] [--out profiles/r08_robust_shell3x3.json]
-python tools/robust_bench.py --workload shell7x5 [--out profiles/r09_robust_shell7x5.json]"""
+python tools/robust_bench.py --workload shell7x5 [--out profiles/r09_robust_shell7x5.json]
+python tools/robust_bench.py --workload vandevusse [--out profiles/r010_robust_vandevusse.json]"""
 import argparse
 import json
 import os
@@ -38,7 +45,7 @@ from mpct.dtc import config4_candidates, woodberry_mc
 from mpct.engine import eval_batch_device, eval_robust_device, kernel_instance, robust_instance
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--workload", choices=("config4", "shell3x3", "shell7x5"), default="config4")
+ap.add_argument("--workload", choices=("config4", "shell3x3", "shell7x5", "vandevusse"), default="config4")
 ap.add_argument("--baseline-lib", default=None, help="shell3x3: another build's libmpct.so to time against")
 ap.add_argument("--candidates", type=int, default=None)
 ap.add_argument("--draws", type=int, default=None)
@@ -213,6 +220,79 @@ def shell7x5_workload():
                       "n_failed_counts": res["robust"]["n_failed_counts"], "instance": res["robust"]["instance"]}))
 
 
+def vandevusse_workload():
+    """The config-5 grid x 8 plant-parameter draws of the Van de Vusse reactor through eval_robust_device
+    (NMPC kernel, VAR = true instances), against the nominal scenario on the same signal rows."""
+    from mpct.nmpc import NmpcScenario, VDV_PARAMS, nmpc_candidate_grid, vandevusse, vandevusse_mc
+
+    D, my = a.draws or 8, 2
+    dev = torch.device("cuda", 0)
+    Cn = a.candidates or 4096
+    N, Nu, dl, lm = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in nmpc_candidate_grid(Cn))
+    scv, r, yref = vandevusse_mc(D)
+    scn, _, _ = vandevusse()
+    k = scn._keep
+    sc0 = NmpcScenario(k["x0"], k["u0"], k["u_min"], k["u_max"], k["x_min"], k["x_max"], yref, scn.n2_max, scn.nu_max,
+                       plant_params=np.tile(VDV_PARAMS, (D, 1)), plant_x0=np.tile(k["x0"], (D, 1)))
+    rd = torch.from_numpy(r).to(dev)
+    rob = dict(mean=torch.empty((Cn, my), dtype=torch.float64, device=dev),
+               worst=torch.empty((Cn, my), dtype=torch.float64, device=dev),
+               n_failed=torch.empty(Cn, dtype=torch.int32, device=dev),
+               worst_draw=torch.empty(Cn, dtype=torch.int32, device=dev),
+               status=torch.empty(Cn, dtype=torch.int32, device=dev),
+               J1=torch.empty((Cn * D, my), dtype=torch.float64, device=dev))
+    pern, per0 = (dict(J1=torch.empty((Cn * D, my), dtype=torch.float64, device=dev),
+                       status=torch.empty(Cn * D, dtype=torch.int32, device=dev)) for _ in range(2))
+    pers = dict(status=torch.empty(Cn * D, dtype=torch.int32, device=dev))
+    run = {"robust": lambda: eval_robust_device(scv, N, Nu, dl, lm, rd, rob),
+           "nominal_all_rows": lambda: eval_batch_device(scn, N, Nu, dl, lm, rd, pern),
+           "variant_nominal_plants": lambda: eval_batch_device(sc0, N, Nu, dl, lm, rd, per0)}
+    for _ in range(a.warmup):
+        for fn in run.values():
+            fn()
+    torch.cuda.synchronize()
+    t = {name: [] for name in run}
+    for _ in range(a.reps):
+        for name, fn in run.items():
+            t[name].append(timed(fn))
+    eval_batch_device(scv, N, Nu, dl, lm, rd, pers)   # the draws' own statuses (the record holds their OR)
+    torch.cuda.synchronize()
+    o = {k_: x.cpu().numpy() for k_, x in rob.items()}
+    st, cnt = np.unique(o["status"], return_counts=True)
+    nf, ncnt = np.unique(o["n_failed"], return_counts=True)
+    sst, scnt = np.unique(pers["status"].cpu().numpy(), return_counts=True)
+    same = bool(np.array_equal(pern["J1"].cpu().numpy().view(np.int64), per0["J1"].cpu().numpy().view(np.int64)) and
+                np.array_equal(pern["status"].cpu().numpy(), per0["status"].cpu().numpy()))
+    mr, mn, m0 = (float(np.median(t[k_])) for k_ in ("robust", "nominal_all_rows", "variant_nominal_plants"))
+    res = {"tool": "tools/robust_bench.py --workload vandevusse",
+           "workload": "Van de Vusse NMPC plant-parameter draws (vandevusse_mc): config-5 grid x plant draws, nit = 60",
+           "device": torch.cuda.get_device_name(0), "candidates": Cn, "draws": D, "nit": 60, "warmup": a.warmup,
+           "reps": a.reps, "timing": "HIP events around each call, the routes interleaved", "j_bound": JB,
+           "robust": dict(stats(t["robust"]), instance=robust_instance(scv), per_simulation_instance=kernel_instance(scv),
+                          sims_per_s=float(Cn * D / (mr * 1e-3)),
+                          status_counts={str(int(k_)): int(x) for k_, x in zip(st, cnt)},
+                          simulation_status_counts={str(int(k_)): int(x) for k_, x in zip(sst, scnt)},
+                          simulations_with_nonzero_status=int(np.count_nonzero(pers["status"].cpu().numpy())),
+                          n_failed_counts={str(int(k_)): int(x) for k_, x in zip(nf, ncnt)},
+                          candidates_with_failed_draw=int(np.count_nonzero(o["n_failed"] > 0)),
+                          candidates_without_failed_draw=int(np.count_nonzero(o["n_failed"] == 0))),
+           "nominal_all_rows": dict(stats(t["nominal_all_rows"]), instance=kernel_instance(scn),
+                                    sims_per_s=float(Cn * D / (mn * 1e-3))),
+           "variant_nominal_plants": dict(stats(t["variant_nominal_plants"]), instance=kernel_instance(sc0),
+                                          sims_per_s=float(Cn * D / (m0 * 1e-3)), bitwise_equal_to_nominal=same),
+           "var_overhead_ratio": m0 / mn,
+           "per_simulation_ratio_robust_over_nominal_all_rows": mr / mn}
+    write(res, "r010_robust_vandevusse.json")
+    print(json.dumps({"robust_median_ms": mr, "nominal_all_rows_median_ms": mn, "variant_nominal_plants_median_ms": m0,
+                      "var_overhead_ratio": res["var_overhead_ratio"], "bitwise_equal_to_nominal": same,
+                      "n_failed_counts": res["robust"]["n_failed_counts"],
+                      "simulation_status_counts": res["robust"]["simulation_status_counts"],
+                      "instance": res["robust"]["instance"]}))
+
+
+if a.workload == "vandevusse":
+    vandevusse_workload()
+    sys.exit(0)
 if a.workload == "shell3x3":
     shell3x3_workload()
     sys.exit(0)
