@@ -255,7 +255,13 @@ typedef struct mpct_opts {
  *   J1[i]  = sum_t (y_i - yref_i)^2                       GAM_fun.m:110-111
  *   j21[i] = sum_{t>=inK} (y_i - ys_i)^2                   VNS2.m:172,176
  *   j22[i] = sum_{t>=inK} (y_i - yref_i)^2                 VNS2.m:173,177
- *   Jnu[n] = sum_t (|uopt_n(1)| / |diff(uopt_n)|)^2, inf/NaN -> 0   VNS2.m:183-191           */
+ *   Jnu[n] = sum_t (|uopt_n(1)| / |diff(uopt_n)|)^2, inf/NaN -> 0   VNS2.m:183-191
+ * Only the requested arrays are written, and only their S rows.  In a call without open_loop, j21 and
+ * Jnu (when requested) come back NaN.  All ten pointers NULL is legal: the batch is checked and
+ * simulated, nothing is written, and the call returns MPCT_OK (the robust entries reject an `out`
+ * without a pointer instead; they have nothing else to deliver).  A simulation whose status carries
+ * MPCT_ST_SKIPPED or MPCT_ST_BADHORIZON is not run: like its costs, its rows of the trajectories the
+ * call writes (y, u; ys, uopt with open_loop) come back NaN, through every entry.                   */
 typedef struct mpct_result {
   double* J1;
   double* j21;

@@ -286,7 +286,12 @@ static int launch_batch(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* 
   dr.prof = dprof;
 #endif
   std::string err;
-  int rc;
+  int rc = 0;
+  // no class launch writes the trajectories of a skipped or bad-horizon simulation: NaN, like its costs
+  if (dop.want_traj)
+    rc = fill_unrun_trajectories(dr, C, nref, N2, Nu, cx->ds.n2max, cx->ds.numax, s->my, s->nu, s->nit,
+                                 dop.open_loop != 0, stream, &err);
+  if (rc) return fail(rc, err);
   if (s->nmpc)
     rc = launch_nmpc(cx->ds, C, nref, N2, Nu, delta, lambda, r, dop, dr, stream, &cx->fan, &cx->order, &err);
   else if (s->mdband)

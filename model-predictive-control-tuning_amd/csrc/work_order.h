@@ -46,6 +46,12 @@ int unpermute_results(const WorkOrder& wo, long long C, int nref, int my, int nu
 // MPCT_ST_NOT_RUN, 0 iterations; enqueue before the class launches, which overwrite the records
 // of the slots they simulate, so a slot that no launch claims cannot pass for a result
 int prefill_results(const DevResult& out, long long S, int my, int nu, hipStream_t stream, std::string* err);
+// trajectory calls: the y / u (open_loop: ys / uopt) rows of every skipped or bad-horizon simulation
+// <- NaN.  No class launch simulates such a slot, so its trajectory rows would keep what the buffer
+// held (the host entries' scratch: another call's trajectories); its cost record is NaN already.
+// One wave per simulation; a valid simulation's wave leaves at once.  Enqueue before the class launches
+int fill_unrun_trajectories(const DevResult& out, long long C, int nref, const int* N2, const int* Nu, int n2max,
+                            int numax, int my, int nu, int nit, bool open_loop, hipStream_t stream, std::string* err);
 // diagnostic build only (-DMPCT_DIAG, csrc/libmpct_diag.so): with MPCT_DIAG_DROP_LAUNCH=k in the
 // environment the k-th class launch of every batch is not issued (tests plant the dispatch fault
 // that the prefill must expose).  The release library has no fault hook: always false

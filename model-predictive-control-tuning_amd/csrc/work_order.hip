@@ -619,6 +619,42 @@ int prefill_results(const DevResult& out, long long S, int my, int nu, hipStream
   return 0;
 }
 
+// wave = simulation (caller's order): the horizon test of the closed-loop kernels' exit path
+__global__ void __launch_bounds__(256) unrun_traj_kernel(DevResult out, long long S, int nref,
+                                                         const int* __restrict__ N2v, const int* __restrict__ Nuv,
+                                                         int n2max, int numax, int my, int nu, int nit, int open_loop) {
+  const long long s = (long long)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
+  if (s >= S) return;
+  const long long c = s / nref;
+  const int n2 = N2v[c], nuc = Nuv[c];
+  if (n2 > 0 && n2 <= n2max && nuc >= 1 && nuc <= numax && nuc <= n2) return;  // a class launch simulates it
+  const int lane = threadIdx.x % kWave;
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const long long ny = (long long)my * nit, nuu = (long long)nu * nit;
+  for (long long e = lane; e < ny; e += kWave) {
+    if (out.y) out.y[s * ny + e] = nan;
+    if (open_loop && out.ys) out.ys[s * ny + e] = nan;
+  }
+  for (long long e = lane; e < nuu; e += kWave) {
+    if (out.u) out.u[s * nuu + e] = nan;
+    if (open_loop && out.uopt) out.uopt[s * nuu + e] = nan;
+  }
+}
+
+int fill_unrun_trajectories(const DevResult& out, long long C, int nref, const int* N2, const int* Nu, int n2max,
+                            int numax, int my, int nu, int nit, bool open_loop, hipStream_t stream, std::string* err) {
+  const long long S = C * nref;
+  if (S <= 0 || !(out.y || out.u || (open_loop && (out.ys || out.uopt)))) return 0;
+  constexpr int kPer = 256 / kWave;  // simulations per workgroup
+  hipLaunchKernelGGL(unrun_traj_kernel, dim3((unsigned)((S + kPer - 1) / kPer)), dim3(256), 0, stream, out, S, nref, N2,
+                     Nu, n2max, numax, my, nu, nit, open_loop ? 1 : 0);
+  if (hipGetLastError() != hipSuccess) {
+    *err = "trajectory fill launch failed";
+    return -3;
+  }
+  return 0;
+}
+
 int unpermute_results(const WorkOrder& wo, long long C, int nref, int my, int nu, const StageRow& R,
                       const DevResult& out, hipStream_t stream, std::string* err) {
   const long long S = C * nref;

@@ -17,7 +17,7 @@ static int g_bad = 0;
     }                                                              \
   } while (0)
 
-static std::unique_ptr<mpct_scenario> build(const mpct_scenario_desc& d, int est = 0) {
+[[maybe_unused]] static std::unique_ptr<mpct_scenario> build(const mpct_scenario_desc& d, int est = 0) {
   BuildError err;
   auto s = build_scenario(d, &err, est);
   if (!s) {
