@@ -214,12 +214,14 @@ __device__ __forceinline__ int gi_qp(const QPBufs& Q, int M, int Nu, const RowCo
       }
       gi_drop<MAXM>(S, sJT, sRA, M, kdrop, BoxMark{});
       PSTAMP(PROF_QDROP);
-      if (it >= maxit) {
+      if (it >= maxit) {  // flagged here; the outer loop then passes through its check once more and ends there
         *st |= MPCT_ST_QP_MAXITER_;
         break;
       }
     }
-    if (it >= maxit || infeas) break;
+    // an add that lands on the cap goes back to the check above: the QP may be solved, and if it
+    // is not the check sets MPCT_ST_QP_MAXITER (leaving here returned a violated x with status 0)
+    if (infeas) break;
   }
   if (row) sxc[lane] = xm;
   lds_sync();

@@ -596,12 +596,14 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
 #endif
       gi16_drop(S, F, sRA, M, kdrop, mark);
       PSTAMP(PROF_QDROP);
-      if (it >= maxit) {
+      if (it >= maxit) {  // flagged here; the outer loop then passes through its check once more and ends there
         *st |= MPCT_ST_QP_MAXITER_;
         break;
       }
     }
-    if (it >= maxit || infeas) break;
+    // an add that lands on the cap goes back to the check above: the QP may be solved, and if it
+    // is not the check sets MPCT_ST_QP_MAXITER (leaving here returned a violated x with status 0)
+    if (infeas) break;
   }
   xout = xm;
   return it;

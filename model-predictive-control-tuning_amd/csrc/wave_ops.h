@@ -24,7 +24,9 @@ __device__ __forceinline__ void lds_sync() {
 }
 
 // 1/x: v_rcp_f64 and two Newton steps (about 1 ulp, not correctly rounded): five dependent
-// operations instead of the division's scale / rcp / refine / fixup sequence
+// operations instead of the division's scale / rcp / refine / fixup sequence.  Measured 0.5 ulp
+// (rsq_nr below: 1.34 ulp, 2.5 by derivation; tests/test_qp_units_gpu.py).  No denormal handling:
+// a denormal x gives NaN (1 / x overflows to INF and the Newton step forms 0 * INF)
 __device__ __forceinline__ double rcp_nr(double x) {
   double r = __builtin_amdgcn_rcp(x);
   r = fma(r, fma(-x, r, 1.0), r);
