@@ -23,7 +23,8 @@
  *     host-pointer entries synchronise that stream only, never the whole device.
  *   - robust scoring (mpct_robust_result, mpct_eval_robust, mpct_eval_robust_device,
  *     mpct_robust_instance) is part of ABI 7: new exports and one new struct, added without a
- *     version change because no existing struct, export or behaviour changes.
+ *     version change because no existing struct, export or behaviour changes.  The tail statistics
+ *     (mpct_robust_tail, mpct_eval_robust_tail, mpct_eval_robust_tail_device) were added the same way.
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -441,6 +442,66 @@ int32_t mpct_eval_robust_device(mpct_scenario* s, int64_t C, const int32_t* N2, 
  * e.g. "dtc_robust_kernel<16> + dtc_robust_kernel<32>" or "gpc_small_kernel + robust_reduce_kernel".
  * Same buffer contract as mpct_kernel_instance; no device needed. */
 int32_t mpct_robust_instance(const mpct_scenario* s, const mpct_opts* opts, char* buf, int32_t cap);
+
+/* ---------------------------------------------------------------------------------------------
+ * Tail statistics over the draws: per candidate, empirical quantiles of the total cost J and the mean
+ * of the tail above each (CVaR), reduced on the device from the J1 sample of the same launch
+ * (robust_tail_kernel, one wave per candidate).  `worst` is the sample maximum (it grows with D and one
+ * draw decides it) and `mean` hides the tail; a quantile and its tail mean are what a robust tuner
+ * ranks by.
+ *
+ * For candidate c the draws k = 0 .. D-1 are classified exactly as above: J(k) = sum_i J1_i(k), summed
+ * over i = 0 .. my-1 in that order; a draw SURVIVES when its status is 0, J is finite and J <= j_bound
+ * (0 means 1e100).  n is the number of survivors; a candidate carrying MPCT_ST_SKIPPED or
+ * MPCT_ST_BADHORIZON has n = 0.
+ *
+ * The survivors are ordered by J ascending and, among equal J, by draw index DESCENDING:
+ * J_(1) <= .. <= J_(n).  -0.0 and +0.0 compare equal.  For each level a_j, j = 0 .. nlev-1:
+ *   m_j = ceil(a_j * (double)n), evaluated in double arithmetic exactly as written, clamped to [1, n]
+ *   quantile[c*nlev+j] = J_(m_j)           the type-1 empirical quantile, no interpolation
+ *   q_draw[c*nlev+j]   = the draw index of J_(m_j)
+ *   cvar[c*nlev+j]     = (J_(m_j) + J_(m_j+1) + .. + J_(n)) / (n - m_j + 1): one accumulator that starts
+ *                        at 0.0 and adds in ascending rank order
+ *   n = 0: NaN, NaN, -1.
+ *
+ * Hence: at level 1.0 quantile = cvar = the largest surviving J and q_draw = worst_draw (the
+ * descending tie-break exists for this identity); duplicate levels give identical columns and the
+ * levels need not be sorted; a repeated call is bitwise identical and a record does not depend on the
+ * candidate's place in the batch.  With a finite bound nothing overflows while D * j_bound < 1.8e308;
+ * with j_bound = +INFINITY a tail sum may round to +INFINITY, never NaN.
+ *
+ * `levels` is a HOST pointer in both entries: a call parameter like j_bound, its values travel to the
+ * kernel by value.  `out` may be NULL, or all its pointers NULL, as long as `tail` carries a pointer;
+ * the base record written through `out` is bitwise what mpct_eval_robust writes for the same call,
+ * and out->J1 is still the optional sample of the same launch (without it the sample lives in the
+ * scenario's robust scratch).  The route is mpct_eval_robust's, fused or generic, followed by
+ * robust_tail_kernel on the same stream.
+ *
+ * MPCT_EINVAL, in this order and before any device is touched: nlev < 1 or nlev >
+ * MPCT_TAIL_MAX_LEVELS; levels NULL; a level that is NaN, <= 0 or > 1; no result pointer at all in
+ * `out` and `tail`; everything mpct_eval_robust rejects.  Then MPCT_ERANGE for nref >
+ * MPCT_TAIL_MAX_DRAWS (the kernel stages 12 B of LDS per draw). */
+#define MPCT_TAIL_MAX_LEVELS 8
+#define MPCT_TAIL_MAX_DRAWS 4096
+typedef struct mpct_robust_tail {
+  double* quantile; /* [C*nlev] */
+  double* cvar;     /* [C*nlev] */
+  int32_t* q_draw;  /* [C*nlev]; any of the three may be NULL */
+} mpct_robust_tail;
+
+/* Host pointers: mpct_eval_robust plus the tail record. */
+int32_t mpct_eval_robust_tail(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
+                              const double* lambda, int32_t nref, const double* r, const double* v, double j_bound,
+                              const mpct_opts* opts, int32_t nlev, const double* levels, mpct_robust_result* out,
+                              mpct_robust_tail* tail);
+
+/* Device pointers (levels excepted), enqueued on `stream` and not synchronised: the contract of
+ * mpct_eval_robust_device, its stream-ordering rule of the scenario's robust scratch included. */
+int32_t mpct_eval_robust_tail_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                     const double* delta, const double* lambda, int32_t nref, const double* r,
+                                     const double* v, double j_bound, const mpct_opts* opts, int32_t nlev,
+                                     const double* levels, mpct_robust_result* out, mpct_robust_tail* tail,
+                                     void* stream);
 
 #ifdef __cplusplus
 }

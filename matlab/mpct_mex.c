@@ -22,6 +22,12 @@
  *                                                    n_failed, worst_draw, status (C x 1; worst_draw is the
  *                                                    library's 0-based draw, -1: none) and J1 (S x my);
  *                                                    j_bound optional (0: 1e100)
+ *   R = mpct_mex('eval_robust_tail', h, N2, Nu, delta, lambda, r, v, j_bound, levels)
+ *                                                    the same record plus the tail statistics of the total
+ *                                                    cost at the 1 .. 8 levels in (0, 1] (mpct_eval_robust_tail):
+ *                                                    fields levels (1 x nlev), quantile, cvar and q_draw
+ *                                                    (C x nlev; q_draw is the library's 0-based draw, -1: none);
+ *                                                    v and j_bound may be []
  *   mpct_mex('destroy', h)
  *
  * MATLAB layouts (column-major, what the callers already hold):
@@ -456,9 +462,21 @@ static void cmd_eval(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[],
   }
 }
 
-/* R = mpct_mex('eval_robust', h, N2, Nu, delta, lambda, r [, v, j_bound]) */
-static void cmd_eval_robust(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
-  if (nrhs < 7) mexErrMsgIdAndTxt("mpct:arg", "usage: R = mpct_mex('eval_robust', h, N2, Nu, delta, lambda, r [, v, j_bound])");
+/* R = mpct_mex('eval_robust', h, N2, Nu, delta, lambda, r [, v, j_bound])
+ * R = mpct_mex('eval_robust_tail', h, N2, Nu, delta, lambda, r, v, j_bound, levels)   (tail != 0) */
+static void cmd_eval_robust(mxArray* plhs[], int nrhs, const mxArray* prhs[], int tail) {
+  if (!tail && nrhs < 7)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: R = mpct_mex('eval_robust', h, N2, Nu, delta, lambda, r [, v, j_bound])");
+  if (tail && nrhs != 10)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: R = mpct_mex('eval_robust_tail', h, N2, Nu, delta, lambda, r, v, j_bound, levels)");
+  long nlev = 0;
+  double* levels = NULL;
+  if (tail) { /* the count is checked before anything is sized by it; the values are the library's to judge */
+    levels = doubles(prhs[9], -1, "levels");
+    nlev = (long)mxGetNumberOfElements(prhs[9]);
+    if (nlev < 1 || nlev > MPCT_TAIL_MAX_LEVELS)
+      mexErrMsgIdAndTxt("mpct:arg", "'levels' must hold 1 .. %d values (has %ld)", MPCT_TAIL_MAX_LEVELS, nlev);
+  }
   const batch_args b = read_batch(nrhs, prhs, 2);
   const int my = b.my;
   const double j_bound = (nrhs > 8 && !mxIsEmpty(prhs[8])) ? scalar(prhs[8], "j_bound") : 0.0;
@@ -471,9 +489,19 @@ static void cmd_eval_robust(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   res.status = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
   res.J1 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
   mpct_opts o = read_opts(NULL);
-  if (mpct_eval_robust(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, &res) != MPCT_OK) lib_error("mpct:eval_robust");
-  const char* names[6] = {"mean", "worst", "n_failed", "worst_draw", "status", "J1"};
-  mxArray* R = mxCreateStructMatrix(1, 1, 6, names);
+  mpct_robust_tail tl = {NULL, NULL, NULL};
+  if (tail) {
+    tl.quantile = (double*)mxCalloc((size_t)(C * nlev + 1), sizeof(double));
+    tl.cvar = (double*)mxCalloc((size_t)(C * nlev + 1), sizeof(double));
+    tl.q_draw = (int32_t*)mxCalloc((size_t)(C * nlev + 1), sizeof(int32_t));
+    if (mpct_eval_robust_tail(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, (int32_t)nlev, levels,
+                              &res, &tl) != MPCT_OK)
+      lib_error("mpct:eval_robust_tail");
+  } else if (mpct_eval_robust(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, &res) != MPCT_OK) {
+    lib_error("mpct:eval_robust");
+  }
+  const char* names[10] = {"mean", "worst", "n_failed", "worst_draw", "status", "J1", "levels", "quantile", "cvar", "q_draw"};
+  mxArray* R = mxCreateStructMatrix(1, 1, tail ? 10 : 6, names);
   mxSetField(R, 0, "mean", out_rows(res.mean, C, my));
   mxSetField(R, 0, "worst", out_rows(res.worst, C, my));
   const int32_t* iv[3] = {res.n_failed, res.worst_draw, res.status};
@@ -483,6 +511,15 @@ static void cmd_eval_robust(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     mxSetField(R, 0, names[2 + f], a);
   }
   mxSetField(R, 0, "J1", out_rows(res.J1, S, my));
+  if (tail) {
+    mxSetField(R, 0, "levels", out_rows(levels, 1, (int)nlev));
+    mxSetField(R, 0, "quantile", out_rows(tl.quantile, C, (int)nlev));
+    mxSetField(R, 0, "cvar", out_rows(tl.cvar, C, (int)nlev));
+    mxArray* a = mxCreateDoubleMatrix((mwSize)C, (mwSize)nlev, mxREAL);
+    for (long k = 0; k < C; ++k)
+      for (long j = 0; j < nlev; ++j) mxGetPr(a)[(size_t)j * C + k] = tl.q_draw[k * nlev + j];
+    mxSetField(R, 0, "q_draw", a);
+  }
   plhs[0] = R;
 }
 
@@ -507,7 +544,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   } else if (!strcmp(cmd, "eval_multi")) {
     cmd_eval(nlhs, plhs, nrhs, prhs, 1);
   } else if (!strcmp(cmd, "eval_robust")) {
-    cmd_eval_robust(plhs, nrhs, prhs);
+    cmd_eval_robust(plhs, nrhs, prhs, 0);
+  } else if (!strcmp(cmd, "eval_robust_tail")) {
+    cmd_eval_robust(plhs, nrhs, prhs, 1);
   } else if (!strcmp(cmd, "instance")) {
     if (nrhs < 2) mexErrMsgIdAndTxt("mpct:arg", "usage: name = mpct_mex('instance', h [, opts])");
     mpct_scenario* s = handle(prhs[1]);

@@ -1,5 +1,5 @@
 // dtc_robust.h — constants and host-side launch interface of dtc_robust.hip (robust scoring over
-// plant draws: the fused small_dtc kernel, the generic reduction).
+// plant draws: the fused small_dtc kernel, the generic reduction, the tail statistics).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +7,7 @@
 
 #include "mpct_dev.h"
 #include "robust_reduce.h"
+#include "robust_tail.h"
 
 namespace mpct {
 
@@ -23,6 +24,8 @@ inline bool dtc_robust_eligible(const DevScenario& sc, int D) {
 
 int launch_robust_reduce(long long C, int D, int my, double j_bound, const double* J1, const int* status,
                          const RobustOut& out, hipStream_t stream, std::string* err);
+int launch_robust_tail(long long C, int D, int my, double j_bound, const double* J1, const int* status, int nlev,
+                       const double* levels, const TailOut& out, hipStream_t stream, std::string* err);
 long long dtc_robust_lds_bytes(const DevScenario& sc, int M, int D);
 int launch_dtc_robust(const DevScenario& sc, long long C, int D, const int* N2, const int* Nu, const double* delta,
                       const double* lambda, const double* r, const double* v, const int* perm, int* lists,

@@ -13,6 +13,9 @@
 //   * robust_classify_kernel: the per-class candidate lists of the fused path, in dispatch order.
 //     The workgroups of a class launch stride over their class's list, so none is started for a
 //     candidate of the other class; skipped / bad-horizon candidates get their records here.
+//   * robust_tail_kernel: quantiles and tail means of the total cost over the draws
+//     (mpct_eval_robust_tail, robust_tail.h), on the J1 sample either path has left in global memory;
+//     one single-wave workgroup per candidate.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -21,6 +24,7 @@
 #include "gpc_prologue.h"
 #include "dtc_step.h"
 #include "robust_reduce.h"
+#include "robust_tail.h"
 #include "dtc_robust.h"
 
 namespace mpct {
@@ -39,6 +43,28 @@ __global__ void __launch_bounds__(kWave* kReduceWaves)
   robust_reduce(
       lane, D, my, j_bound, [&](int k, int i) __attribute__((always_inline)) { return j[k * my + i]; },
       [&](int k) __attribute__((always_inline)) { return s[k]; }, out, c);
+}
+
+// ------------------------------------------------------------------------------------------
+// tail statistics: J1 [C*D][my], status [C*D] or null (read as 0: the fused path keeps none, and its
+// failed draws carry a non-finite J1) -> quantile, cvar, q_draw [C][nlev].  The workgroup is ONE wave
+// and the whole dynamic LDS (12 B per draw) is its candidate's slice, so the hand-offs inside
+// robust_tail need lds_sync() only; with more waves per workgroup each would need a slice of its own
+// (the hazard dtc_robust_kernel's barrier comment states).  The workgroups stride over the candidates
+__global__ void __launch_bounds__(kWave)
+    robust_tail_kernel(long long C, int D, int my, double j_bound, const double* __restrict__ J1,
+                       const int* __restrict__ status, int nlev, const TailLevels lv, const TailOut out) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x;
+  double* Js = lds;
+  int* idx = reinterpret_cast<int*>(lds + D);
+  for (long long c = blockIdx.x; c < C; c += gridDim.x) {
+    const double* j = J1 + c * D * my;
+    const int* s = status ? status + c * D : nullptr;
+    robust_tail(
+        lane, D, my, j_bound, [&](int k, int i) __attribute__((always_inline)) { return j[k * my + i]; },
+        [&](int k) __attribute__((always_inline)) { return s ? s[k] : 0; }, nlev, lv, out, c, Js, idx);
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -220,6 +246,19 @@ int launch_robust_reduce(long long C, int D, int my, double j_bound, const doubl
   const unsigned grid = (unsigned)((C + kReduceWaves - 1) / kReduceWaves);
   hipLaunchKernelGGL(robust_reduce_kernel, dim3(grid), dim3(kWave * kReduceWaves), 0, stream, C, D, my, j_bound, J1,
                      status, out);
+  return launched(err);
+}
+
+// D <= kTailMaxDraws, 1 <= nlev <= kTailMaxLevels (the callers check); status may be null
+int launch_robust_tail(long long C, int D, int my, double j_bound, const double* J1, const int* status, int nlev,
+                       const double* levels, const TailOut& out, hipStream_t stream, std::string* err) {
+  if (C == 0) return 0;
+  TailLevels lv;
+  for (int q = 0; q < kTailMaxLevels; ++q) lv.a[q] = q < nlev ? levels[q] : 1.0;
+  const long long cap = 1 << 20;  // beyond it the workgroups stride
+  const unsigned grid = (unsigned)(C < cap ? C : cap);
+  hipLaunchKernelGGL(robust_tail_kernel, dim3(grid), dim3(kWave), robust_tail_lds_bytes(D), stream, C, D, my, j_bound,
+                     J1, status, nlev, lv, out);
   return launched(err);
 }
 

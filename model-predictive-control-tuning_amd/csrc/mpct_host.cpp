@@ -651,15 +651,17 @@ extern "C" int32_t mpct_eval_batch_multi(mpct_scenario* s, int32_t ndev, const i
 // the argument checks of the robust entries, on top of check_args
 static int check_robust(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* N2, const int32_t* Nu,
                         const double* delta, const double* lambda, const double* r, const double* v, double j_bound,
-                        const mpct_opts* opts, const mpct_robust_result* out) {
+                        const mpct_opts* opts, const mpct_robust_result* out, bool need_out = true) {
   if (!s) return fail(MPCT_EINVAL, "null scenario");
   if (opts && (opts->open_loop || opts->want_traj))
     return fail(MPCT_EINVAL, "robust scoring is cost-only: open_loop and want_traj must be 0");
   if (nref < 1) return fail(MPCT_EINVAL, "nref < 1: robust scoring needs at least one draw");
   if (!(j_bound >= 0.0)) return fail(MPCT_EINVAL, "j_bound must be >= 0 (0 = 1e100, +inf allowed), not negative or NaN");
-  if (!out) return fail(MPCT_EINVAL, "null result");
-  if (!out->mean && !out->worst && !out->n_failed && !out->worst_draw && !out->status && !out->J1)
-    return fail(MPCT_EINVAL, "every output pointer of the robust result is NULL");
+  if (need_out) {
+    if (!out) return fail(MPCT_EINVAL, "null result");
+    if (!out->mean && !out->worst && !out->n_failed && !out->worst_draw && !out->status && !out->J1)
+      return fail(MPCT_EINVAL, "every output pointer of the robust result is NULL");
+  }
   const mpct_result any{};
   return check_args(s, C, nref, N2, Nu, delta, lambda, r, v, opts, &any);
 }
@@ -684,10 +686,39 @@ static int robust_scratch(DevCtx* cx, size_t bytes, hipStream_t stream, char** o
   return MPCT_OK;
 }
 
-// enqueue one robust batch with device pointers on `stream` (ctx's device is current)
+// the tail statistics a robust call adds (mpct_eval_robust_tail): the levels on the host, the
+// outputs on the device
+struct TailReq {
+  int nlev;
+  const double* levels;
+  TailOut out;
+};
+
+// the argument checks the tail entries add, in the header's order; then check_robust's, then the
+// draw cap.  Nothing here touches a device
+static int check_tail(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* N2, const int32_t* Nu,
+                      const double* delta, const double* lambda, const double* r, const double* v, double j_bound,
+                      const mpct_opts* opts, int32_t nlev, const double* levels, const mpct_robust_result* out,
+                      const mpct_robust_tail* tail) {
+  if (nlev < 1 || nlev > MPCT_TAIL_MAX_LEVELS) return fail(MPCT_EINVAL, "nlev must be 1 .. MPCT_TAIL_MAX_LEVELS (8)");
+  if (!levels) return fail(MPCT_EINVAL, "null levels");
+  for (int j = 0; j < nlev; ++j)
+    if (!(levels[j] > 0.0 && levels[j] <= 1.0)) return fail(MPCT_EINVAL, "every level must lie in (0, 1], not NaN");
+  const bool any_tail = tail && (tail->quantile || tail->cvar || tail->q_draw);
+  const bool any_out = out && (out->mean || out->worst || out->n_failed || out->worst_draw || out->status || out->J1);
+  if (!any_tail && !any_out) return fail(MPCT_EINVAL, "every output pointer of the robust result and of the tail is NULL");
+  const int rc = check_robust(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, out, false);
+  if (rc) return rc;
+  if (nref > MPCT_TAIL_MAX_DRAWS) return fail(MPCT_ERANGE, "nref > MPCT_TAIL_MAX_DRAWS (4096): the tail kernel's LDS holds no more draws");
+  return MPCT_OK;
+}
+
+// enqueue one robust batch with device pointers on `stream` (ctx's device is current); with `tail`,
+// robust_tail_kernel follows on the same stream, on the J1 sample of the same launch
 static int launch_robust(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2, const int32_t* Nu,
                          const double* delta, const double* lambda, int32_t nref, const double* r, const double* v,
-                         double j_bound, const mpct_opts* opts, const mpct_robust_result* out, hipStream_t stream) {
+                         double j_bound, const mpct_opts* opts, const mpct_robust_result* out, hipStream_t stream,
+                         const TailReq* tail = nullptr) {
   if (C == 0) return MPCT_OK;
   const double bound = j_bound == 0.0 ? kRobustDefaultBound : j_bound;
   const RobustOut ro{out->mean, out->worst, out->n_failed, out->worst_draw, out->status};
@@ -699,15 +730,23 @@ static int launch_robust(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t*
     if (cx->ncu == 0 &&
         (hipDeviceGetAttribute(&cx->ncu, hipDeviceAttributeMultiprocessorCount, cx->dev) != hipSuccess || cx->ncu < 1))
       return fail(MPCT_EDEVICE, "hipDeviceGetAttribute(MultiprocessorCount) failed");
-    rc = robust_scratch(cx, sizeof(int) * (size_t)(2 * C + 2), stream, &scr);
+    // the candidate lists, and the J1 sample where a tail is asked for and the caller keeps none
+    const size_t lb = (sizeof(int) * (size_t)(2 * C + 2) + 255) & ~(size_t)255;
+    const bool own_j1 = tail && !out->J1;
+    rc = robust_scratch(cx, own_j1 ? lb + (size_t)S * s->my * 8 : sizeof(int) * (size_t)(2 * C + 2), stream, &scr);
     if (rc) return rc;
+    double* j1 = own_j1 ? reinterpret_cast<double*>(scr + lb) : out->J1;
     const int* perm = nullptr;
     rc = order_candidates(kOrderGpc, s->my, s->nu, C, N2, Nu, delta, lambda, cx->order, &perm, stream, &err, &cx->ds,
                           nref, r);
     if (rc == 0)
       rc = launch_dtc_robust(cx->ds, C, nref, N2, Nu, delta, lambda, r, v, perm, reinterpret_cast<int*>(scr), bound, ro,
-                             out->J1, cx->ncu, &cx->fan, stream, &err);
+                             j1, cx->ncu, &cx->fan, stream, &err);
     if (perm) order_mark_used(cx->order, stream);
+    // the fused kernel keeps no per-simulation status: a failed draw of it has a non-finite J1, and a
+    // candidate that was never simulated an all-NaN sample (robust_classify_kernel)
+    if (rc == 0 && tail)
+      rc = launch_robust_tail(C, nref, s->my, bound, j1, nullptr, tail->nlev, tail->levels, tail->out, stream, &err);
     if (rc) return fail(rc, err);
   } else {
     // the per-simulation instance, unchanged, into the caller's J1 or the scenario's scratch
@@ -720,6 +759,9 @@ static int launch_robust(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t*
     rc = launch_batch(s, cx, C, N2, Nu, delta, lambda, nref, r, v, opts, &per, stream);
     if (rc) return rc;
     rc = launch_robust_reduce(C, nref, s->my, bound, per.J1, per.status, ro, stream, &err);
+    if (rc == 0 && tail)
+      rc = launch_robust_tail(C, nref, s->my, bound, per.J1, per.status, tail->nlev, tail->levels, tail->out, stream,
+                              &err);
     if (rc) return fail(rc, err);
   }
   cx->robust_pending = hipEventRecord(cx->robust_used, stream) == hipSuccess;
@@ -738,6 +780,39 @@ extern "C" int32_t mpct_eval_robust_device(mpct_scenario* s, int64_t C, const in
   return launch_robust(s, cx, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, out, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int32_t mpct_eval_robust_tail_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                const double* delta, const double* lambda, int32_t nref,
+                                                const double* r, const double* v, double j_bound,
+                                                const mpct_opts* opts, int32_t nlev, const double* levels,
+                                                mpct_robust_result* out, mpct_robust_tail* tail, void* stream) {
+  int rc = check_tail(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, nlev, levels, out, tail);
+  if (rc) return rc;
+  DevCtx* cx = nullptr;
+  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  if (rc) return rc;
+  const mpct_robust_result base = out ? *out : mpct_robust_result{};
+  const TailReq tq{nlev, levels, tail ? TailOut{tail->quantile, tail->cvar, tail->q_draw} : TailOut{}};
+  return launch_robust(s, cx, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, &base, static_cast<hipStream_t>(stream),
+                       &tq);
+}
+
+// Test hook, deliberately not declared in include/mpct.h: robust_tail_kernel alone, on per-simulation
+// records the caller supplies (device pointers, status may be NULL and is then read as 0; levels on
+// the host; enqueued on `stream`).
+extern "C" int32_t mpct_internal_robust_tail(int64_t C, int32_t D, int32_t my, double j_bound, const double* J1,
+                                             const int32_t* status, int32_t nlev, const double* levels,
+                                             double* quantile, double* cvar, int32_t* q_draw, void* stream) {
+  if (C < 0 || D < 1 || my < 1 || !J1 || !(j_bound >= 0.0) || nlev < 1 || nlev > kTailMaxLevels || !levels)
+    return fail(MPCT_EINVAL, "bad argument");
+  for (int j = 0; j < nlev; ++j)
+    if (!(levels[j] > 0.0 && levels[j] <= 1.0)) return fail(MPCT_EINVAL, "every level must lie in (0, 1], not NaN");
+  if (D > kTailMaxDraws) return fail(MPCT_ERANGE, "D > MPCT_TAIL_MAX_DRAWS");
+  std::string err;
+  const int rc = launch_robust_tail(C, D, my, j_bound == 0.0 ? kRobustDefaultBound : j_bound, J1, status, nlev, levels,
+                                    TailOut{quantile, cvar, q_draw}, static_cast<hipStream_t>(stream), &err);
+  return rc ? fail(rc, err) : MPCT_OK;
+}
+
 // Test hook, deliberately not declared in include/mpct.h: the generic path's reduction alone, on
 // per-simulation records the caller supplies (device pointers, enqueued on `stream`).  The tests
 // reduce the fused kernel's own J1 sample with it to pin that both paths share one robust_reduce.
@@ -751,13 +826,13 @@ extern "C" int32_t mpct_internal_robust_reduce(int64_t C, int32_t D, int32_t my,
   return rc ? fail(rc, err) : MPCT_OK;
 }
 
-extern "C" int32_t mpct_eval_robust(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
-                                    const double* delta, const double* lambda, int32_t nref, const double* r,
-                                    const double* v, double j_bound, const mpct_opts* opts, mpct_robust_result* out) {
-  int rc = check_robust(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, out);
-  if (rc) return rc;
+// the host-pointer robust entries after their argument checks; nlev = 0: no tail
+static int eval_robust_host(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
+                            const double* lambda, int32_t nref, const double* r, const double* v, double j_bound,
+                            const mpct_opts* opts, const mpct_robust_result* out, int32_t nlev, const double* levels,
+                            const mpct_robust_tail* tail) {
   DevCtx* cx = nullptr;
-  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  int rc = device_ctx(s, opts ? opts->device : -1, &cx);
   if (rc) return rc;
   if (C == 0) return MPCT_OK;
   // host buffers in, host buffers out on the context's own stream, staged as eval_host does
@@ -766,6 +841,8 @@ extern "C" int32_t mpct_eval_robust(mpct_scenario* s, int64_t C, const int32_t* 
   HostStage hs(s, cx, C);
   const size_t o_mean = hs.slot(C * my * 8), o_worst = hs.slot(C * my * 8), o_nf = hs.slot(C * 4), o_wd = hs.slot(C * 4);
   const size_t o_st = hs.slot(C * 4), o_J1 = out->J1 ? hs.slot(S * my * 8) : 0;
+  const size_t o_q = nlev ? hs.slot(C * nlev * 8) : 0, o_cv = nlev ? hs.slot(C * nlev * 8) : 0;
+  const size_t o_qd = nlev ? hs.slot(C * nlev * 4) : 0;
   rc = hs.upload(s, N2, Nu, delta, lambda, nref, r, v);
   if (rc) return rc;
   mpct_robust_result dres{};
@@ -775,7 +852,9 @@ extern "C" int32_t mpct_eval_robust(mpct_scenario* s, int64_t C, const int32_t* 
   dres.worst_draw = hs.at<int32_t>(o_wd);
   dres.status = hs.at<int32_t>(o_st);
   dres.J1 = out->J1 ? hs.at<double>(o_J1) : nullptr;
-  rc = launch_robust(s, cx, C, hs.N2(), hs.Nu(), hs.delta(), hs.lambda(), nref, hs.r, hs.v, j_bound, opts, &dres, hs.st);
+  const TailReq tq{nlev, levels, nlev ? TailOut{hs.at<double>(o_q), hs.at<double>(o_cv), hs.at<int32_t>(o_qd)} : TailOut{}};
+  rc = launch_robust(s, cx, C, hs.N2(), hs.Nu(), hs.delta(), hs.lambda(), nref, hs.r, hs.v, j_bound, opts, &dres, hs.st,
+                     nlev ? &tq : nullptr);
   if (rc) return hs.abandon(rc);
   hs.fetch(out->mean, o_mean, C * my * 8);
   hs.fetch(out->worst, o_worst, C * my * 8);
@@ -783,7 +862,30 @@ extern "C" int32_t mpct_eval_robust(mpct_scenario* s, int64_t C, const int32_t* 
   hs.fetch(out->worst_draw, o_wd, C * 4);
   hs.fetch(out->status, o_st, C * 4);
   hs.fetch(out->J1, o_J1, S * my * 8);
+  if (nlev && tail) {
+    hs.fetch(tail->quantile, o_q, C * nlev * 8);
+    hs.fetch(tail->cvar, o_cv, C * nlev * 8);
+    hs.fetch(tail->q_draw, o_qd, C * nlev * 4);
+  }
   return hs.finish();
+}
+
+extern "C" int32_t mpct_eval_robust(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                    const double* delta, const double* lambda, int32_t nref, const double* r,
+                                    const double* v, double j_bound, const mpct_opts* opts, mpct_robust_result* out) {
+  const int rc = check_robust(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, out);
+  if (rc) return rc;
+  return eval_robust_host(s, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, out, 0, nullptr, nullptr);
+}
+
+extern "C" int32_t mpct_eval_robust_tail(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                         const double* delta, const double* lambda, int32_t nref, const double* r,
+                                         const double* v, double j_bound, const mpct_opts* opts, int32_t nlev,
+                                         const double* levels, mpct_robust_result* out, mpct_robust_tail* tail) {
+  const int rc = check_tail(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, nlev, levels, out, tail);
+  if (rc) return rc;
+  const mpct_robust_result base = out ? *out : mpct_robust_result{};
+  return eval_robust_host(s, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, &base, nlev, levels, tail);
 }
 
 static int32_t copy_name(const std::string& nm, char* buf, int32_t cap) {

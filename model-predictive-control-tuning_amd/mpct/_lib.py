@@ -86,15 +86,21 @@ class MpctRobustResult(C.Structure):
                 ("status", c_int32_p), ("J1", c_double_p)]
 
 
+class MpctRobustTail(C.Structure):
+    _fields_ = [("quantile", c_double_p), ("cvar", c_double_p), ("q_draw", c_int32_p)]
+
+
 EXPORTS = [
     "mpct_abi_version", "mpct_last_error", "mpct_scenario_create", "mpct_scenario_destroy",
     "mpct_scenario_table", "mpct_eval_batch", "mpct_eval_batch_device", "mpct_lds_bytes", "mpct_lds_bytes_opts",
     "mpct_nmpc_scenario_create", "mpct_eval_batch_multi", "mpct_shard_candidates", "mpct_kernel_instance",
     "mpct_rank_device", "mpct_eval_robust", "mpct_eval_robust_device", "mpct_robust_instance",
-    "mpct_scenario_create_est", "mpct_nmpc_scenario_create_var",
+    "mpct_scenario_create_est", "mpct_nmpc_scenario_create_var", "mpct_eval_robust_tail",
+    "mpct_eval_robust_tail_device",
 ]
 
 ABI_VERSION = 7
+TAIL_MAX_LEVELS, TAIL_MAX_DRAWS = 8, 4096
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
 ST_SQP_MAXITER, ST_BOUNDS, ST_NOT_RUN = 32, 64, 128
 NMPC_VANDEVUSSE = 1
@@ -168,10 +174,19 @@ def load():
     lib.mpct_eval_robust_device.restype = C.c_int32
     lib.mpct_robust_instance.argtypes = [C.c_void_p, C.POINTER(MpctOpts), C.c_char_p, C.c_int32]
     lib.mpct_robust_instance.restype = C.c_int32
+    tail_args = robust_args[:11] + [C.c_int32, c_double_p, C.POINTER(MpctRobustResult), C.POINTER(MpctRobustTail)]
+    lib.mpct_eval_robust_tail.argtypes = tail_args
+    lib.mpct_eval_robust_tail.restype = C.c_int32
+    lib.mpct_eval_robust_tail_device.argtypes = tail_args + [C.c_void_p]
+    lib.mpct_eval_robust_tail_device.restype = C.c_int32
     # the reduction of the generic robust path alone: a test hook, not part of include/mpct.h
     lib.mpct_internal_robust_reduce.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                                 C.POINTER(MpctRobustResult), C.c_void_p]
     lib.mpct_internal_robust_reduce.restype = C.c_int32
+    # robust_tail_kernel alone (levels on the host, status may be NULL): a test hook as well
+    lib.mpct_internal_robust_tail.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                              C.c_int32, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.mpct_internal_robust_tail.restype = C.c_int32
     if lib.mpct_abi_version() != ABI_VERSION:
         raise ImportError("libmpct ABI version mismatch")
     _lib = lib

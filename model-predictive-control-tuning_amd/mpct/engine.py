@@ -378,6 +378,11 @@ class RobustResult:
     status: np.ndarray        # (C,) OR of the draws' status bits
     draws: int = 1
     J1: np.ndarray | None = None   # (C * draws, my) per-simulation costs of the same launch (want_J1)
+    # tail statistics of the total cost J over the surviving draws (eval_robust(levels=...); include/mpct.h)
+    levels: np.ndarray | None = None     # (nlev,) the levels asked for, each in (0, 1]
+    quantile: np.ndarray | None = None   # (C, nlev) type-1 empirical quantile J_(ceil(a n)); NaN if none survives
+    cvar: np.ndarray | None = None       # (C, nlev) mean of the survivors from that rank upwards
+    q_draw: np.ndarray | None = None     # (C, nlev) the draw whose J is the quantile; -1 if none survives
 
     def scores(self, max_failed: int = 0, stat: str = "worst") -> np.ndarray:
         """(C, my) costs for ranking: the chosen statistic ('worst' or 'mean'), NaN for every
@@ -390,11 +395,21 @@ class RobustResult:
         return s
 
 
+def _levels(levels):
+    """The levels of a tail call as the contiguous float64 vector the library reads (a host pointer)."""
+    lv = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.float64)
+    if lv.ndim != 1:
+        raise ValueError("levels must be a vector")
+    return lv
+
+
 def eval_robust(sc: Scenario, N2, Nu, delta, lam, refs, v=None, j_bound=0.0, device=-1, want_J1=False,
-                max_qp_iter=0, feas_tol=0.0) -> RobustResult:
+                max_qp_iter=0, feas_tol=0.0, levels=None) -> RobustResult:
     """Score C candidates over the D = len(refs) draws (reference set k, plant variant k % nplant)
     and reduce on the device to per-candidate statistics (host arrays in and out).  ``j_bound``:
-    a draw whose total cost exceeds it fails (0 = 1e100, inf allowed)."""
+    a draw whose total cost exceeds it fails (0 = 1e100, inf allowed).  ``levels`` (up to 8 values in
+    (0, 1]) adds the tail record of the total cost from the same launch (mpct_eval_robust_tail):
+    quantile, cvar and q_draw, each of shape (C, nlev)."""
     N2, Nu, delta, lam, refs, Cn, D, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
     res = RobustResult(mean=np.zeros((Cn, sc.my)), worst=np.zeros((Cn, sc.my)), n_failed=np.zeros(Cn, dtype=np.int32),
                        worst_draw=np.zeros(Cn, dtype=np.int32), status=np.zeros(Cn, dtype=np.int32), draws=D,
@@ -405,6 +420,19 @@ def eval_robust(sc: Scenario, N2, Nu, delta, lam, refs, v=None, j_bound=0.0, dev
     if want_J1:
         r.J1 = _dp(res.J1)
     o = _opts(False, False, device, max_qp_iter, feas_tol)
+    if levels is not None:
+        lv = _levels(levels)
+        res.levels = lv
+        res.quantile, res.cvar = np.zeros((Cn, lv.size)), np.zeros((Cn, lv.size))
+        res.q_draw = np.zeros((Cn, lv.size), dtype=np.int32)
+        t = _lib.MpctRobustTail(_dp(res.quantile), _dp(res.cvar), _ip(res.q_draw))
+        rc = sc.lib.mpct_eval_robust_tail(sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data,
+                                          lam.ctypes.data, D, refs.ctypes.data,
+                                          vv.ctypes.data if vv is not None else None, float(j_bound), C.byref(o),
+                                          lv.size, _dp(lv), C.byref(r), C.byref(t))
+        if rc != 0:
+            raise MpctError("mpct_eval_robust_tail failed (%d): %s" % (rc, _lib.last_error()))
+        return res
     rc = sc.lib.mpct_eval_robust(sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data, lam.ctypes.data,
                                  D, refs.ctypes.data, vv.ctypes.data if vv is not None else None, float(j_bound),
                                  C.byref(o), C.byref(r))
@@ -422,17 +450,31 @@ def _robust_struct(out: dict):
 
 
 def eval_robust_device(sc: Scenario, N2, Nu, delta, lam, refs, out: dict, v=None, j_bound=0.0, device=-1,
-                       stream=None):
+                       stream=None, levels=None):
     """Device-pointer entry of eval_robust: every argument is a CUDA (HIP) torch tensor; the records
     are written into the tensors of ``out`` (keys mean, worst: float64 [C, my]; n_failed, worst_draw,
     status: int32 [C]; J1: float64 [C * D, my]; any may be absent).  Enqueued on ``stream`` (torch
-    stream; default: current) and not synchronised."""
+    stream; default: current) and not synchronised.  ``levels`` (a HOST sequence, up to 8 values in
+    (0, 1]) adds the tail record through mpct_eval_robust_tail_device: ``out`` keys quantile, cvar
+    (float64 [C, nlev]) and q_draw (int32 [C, nlev]), any may be absent."""
     import torch
 
     if stream is None:
         stream = torch.cuda.current_stream()
     r = _robust_struct(out)
     o = _opts(False, False, device)
+    if levels is not None:
+        lv = _levels(levels)
+        t = _lib.MpctRobustTail(_tptr(out.get("quantile"), _lib.c_double_p), _tptr(out.get("cvar"), _lib.c_double_p),
+                                _tptr(out.get("q_draw"), _lib.c_int32_p))
+        rc = sc.lib.mpct_eval_robust_tail_device(
+            sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+            C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+            C.c_void_p(v.data_ptr()) if v is not None else None, float(j_bound), C.byref(o), lv.size, _dp(lv),
+            C.byref(r), C.byref(t), C.c_void_p(stream.cuda_stream))
+        if rc != 0:
+            raise MpctError("mpct_eval_robust_tail_device failed (%d): %s" % (rc, _lib.last_error()))
+        return
     rc = sc.lib.mpct_eval_robust_device(
         sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
         C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),

@@ -28,7 +28,13 @@ on the same 8 signal rows (a launch of the same size) and with a variant scenari
 equal the model from the model's x0 (the nominal loops bit for bit: its time over the nominal launch is
 what the VAR = true instances cost; the mismatched draws solve other problems).
 
+--levels A,B,..: the tail statistics on the config-4 workload: eval_robust_tail_device (quantiles and
+tail means at those levels, robust_tail_kernel behind the same launches) timed beside eval_robust_device of
+this build and, with --baseline-lib, of that library too (the code both run is unchanged, so this build's
+median should lie inside the baseline's own min-max range); the tail kernel's share is the difference.
+
 python tools/robust_bench.py [--candidates C] [--draws D] [--reps N] [--out profiles/r07_robust_bench.json]
+python tools/robust_bench.py --levels 0.5,0.9,1.0 [--baseline-lib PATH] [--out profiles/r011_robust_tail.json]
 python tools/robust_bench.py --workload shell3x3 [--baseline-lib PATH] [--out profiles/r08_robust_shell3x3.json]
 python tools/robust_bench.py --workload shell7x5 [--out profiles/r09_robust_shell7x5.json]
 python tools/robust_bench.py --workload vandevusse [--out profiles/r010_robust_vandevusse.json]"""
@@ -46,7 +52,8 @@ from mpct.engine import eval_batch_device, eval_robust_device, kernel_instance, 
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--workload", choices=("config4", "shell3x3", "shell7x5", "vandevusse"), default="config4")
-ap.add_argument("--baseline-lib", default=None, help="shell3x3: another build's libmpct.so to time against")
+ap.add_argument("--baseline-lib", default=None, help="shell3x3, --levels: another build's libmpct.so to time against")
+ap.add_argument("--levels", default=None, help="config4: comma-separated levels; times eval_robust_tail_device too")
 ap.add_argument("--candidates", type=int, default=None)
 ap.add_argument("--draws", type=int, default=None)
 ap.add_argument("--warmup", type=int, default=3)
@@ -79,6 +86,117 @@ def write(res, default_name):
         f.write("\n")
 
 
+def load_baseline(path):
+    """Make the next Scenario load and keep the library at `path` (scenarios made before keep theirs).
+    A build from before the tail entries lacks their symbols; the loader only sets their argtypes, so
+    for such a library those names resolve to placeholders that are never called."""
+    import ctypes
+    import types
+    from mpct import _lib
+
+    new = ("mpct_eval_robust_tail", "mpct_eval_robust_tail_device", "mpct_internal_robust_tail")
+
+    class Baseline(ctypes.CDLL):
+        def __getattr__(self, name):
+            try:
+                return super().__getattr__(name)
+            except AttributeError:
+                if name in new:
+                    return types.SimpleNamespace()
+                raise
+
+    os.environ["MPCT_LIB"] = os.path.abspath(path)
+    _lib._lib = None
+    cdll, _lib.C.CDLL = _lib.C.CDLL, Baseline
+    try:
+        _lib.load()
+    finally:
+        _lib.C.CDLL = cdll
+
+
+def config4_tail_workload(levels):
+    """Config 4, candidates x draws: eval_robust_device of the baseline library (with --baseline-lib)
+    and of this build, and this build's eval_robust_tail_device at `levels`, interleaved."""
+    from mpct import _lib
+    from mpct.engine import robust_instance
+
+    Cn, D, my, nlev = a.candidates or 10000, a.draws or 32, 2, len(levels)
+    dev = torch.device("cuda", 0)
+    made = woodberry_mc(draws=D, n2_max=30, nu_max=10)
+    builds = {"this_build": made[0]}
+    refs, v = made[1], made[2]
+    if a.baseline_lib:
+        load_baseline(a.baseline_lib)
+        builds = {"baseline": woodberry_mc(draws=D, n2_max=30, nu_max=10)[0], "this_build": made[0]}
+        assert builds["baseline"].lib is not builds["this_build"].lib
+    N2, Nu, dl, lm = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in config4_candidates(Cn))
+    refs_d, v_d = torch.from_numpy(refs).to(dev), torch.from_numpy(v).to(dev)
+
+    def record():
+        return dict(mean=torch.empty((Cn, my), dtype=torch.float64, device=dev),
+                    worst=torch.empty((Cn, my), dtype=torch.float64, device=dev),
+                    n_failed=torch.empty(Cn, dtype=torch.int32, device=dev),
+                    worst_draw=torch.empty(Cn, dtype=torch.int32, device=dev),
+                    status=torch.empty(Cn, dtype=torch.int32, device=dev))
+
+    outs = {name: record() for name in builds}
+    outs["this_build_tail"] = dict(record(), quantile=torch.empty((Cn, nlev), dtype=torch.float64, device=dev),
+                                   cvar=torch.empty((Cn, nlev), dtype=torch.float64, device=dev),
+                                   q_draw=torch.empty((Cn, nlev), dtype=torch.int32, device=dev))
+    run = {name: (lambda sc=sc, out=outs[name]: eval_robust_device(sc, N2, Nu, dl, lm, refs_d, out, v=v_d))
+           for name, sc in builds.items()}
+    run["this_build_tail"] = lambda: eval_robust_device(builds["this_build"], N2, Nu, dl, lm, refs_d,
+                                                        outs["this_build_tail"], v=v_d, levels=levels)
+    for _ in range(a.warmup):
+        for fn in run.values():
+            fn()
+    torch.cuda.synchronize()
+    t = {name: [] for name in run}
+    for _ in range(a.reps):
+        for name, fn in run.items():
+            t[name].append(timed(fn))
+    torch.cuda.synchronize()
+    host = {name: {k: x.cpu().numpy() for k, x in o.items()} for name, o in outs.items()}
+    base = ("mean", "worst", "n_failed", "worst_draw", "status")
+
+    def same(x, y):
+        return bool(all(np.array_equal(x[f].view(np.int64 if x[f].dtype == np.float64 else np.int32),
+                                       y[f].view(np.int64 if y[f].dtype == np.float64 else np.int32)) for f in base))
+
+    tl = host["this_build_tail"]
+    m_this, m_tail = float(np.median(t["this_build"])), float(np.median(t["this_build_tail"]))
+    rec_bytes = Cn * (2 * my * 8 + 3 * 4)
+    res = {"tool": "tools/robust_bench.py --levels " + ",".join(repr(x) for x in levels),
+           "workload": "config 4: DTC-GPC WoodBerry, plant-mismatch draws", "device": torch.cuda.get_device_name(0),
+           "candidates": Cn, "draws": D, "nit": 200, "levels": list(levels), "warmup": a.warmup, "reps": a.reps,
+           "timing": "HIP events around each call, the routes interleaved", "j_bound": JB,
+           "this_build": dict(stats(t["this_build"]), entry="eval_robust_device", instance=robust_instance(builds["this_build"]),
+                              bytes_written=rec_bytes),
+           "this_build_tail": dict(stats(t["this_build_tail"]), entry="eval_robust_tail_device",
+                                   instance=robust_instance(builds["this_build"]) + " + robust_tail_kernel",
+                                   bytes_written=rec_bytes + Cn * nlev * 20, scratch_J1_bytes=Cn * D * my * 8),
+           "tail_extra_ms_median": m_tail - m_this, "tail_share_of_tail_call": (m_tail - m_this) / m_tail,
+           "base_record_of_tail_call_bitwise_equal": same(tl, host["this_build"]),
+           "level_one_q_draw_equals_worst_draw": (bool(np.array_equal(tl["q_draw"][:, list(levels).index(1.0)], tl["worst_draw"]))
+                                                  if 1.0 in levels else None),
+           "candidates_without_failed_draw": int(np.count_nonzero(tl["n_failed"] == 0)),
+           "candidates_all_draws_failed": int(np.count_nonzero(tl["n_failed"] == D))}
+    line = {"this_build_median_ms": m_this, "tail_median_ms": m_tail, "tail_share": res["tail_share_of_tail_call"],
+            "base_record_bitwise_equal": res["base_record_of_tail_call_bitwise_equal"]}
+    if a.baseline_lib:
+        tb = t["baseline"]
+        res["baseline"] = dict(stats(tb), entry="eval_robust_device", instance=robust_instance(builds["baseline"]))
+        res["this_build_median_inside_baseline_range"] = bool(min(tb) <= m_this <= max(tb))
+        res["ratio_this_over_baseline_median"] = m_this / float(np.median(tb))
+        res["records_bitwise_equal_to_baseline"] = same(host["this_build"], host["baseline"])
+        line |= {"baseline_median_ms": res["baseline"]["median_ms"], "baseline_min_ms": res["baseline"]["min_ms"],
+                 "baseline_max_ms": res["baseline"]["max_ms"],
+                 "inside_baseline_range": res["this_build_median_inside_baseline_range"],
+                 "records_bitwise_equal_to_baseline": res["records_bitwise_equal_to_baseline"]}
+    write(res, "r011_robust_tail.json")
+    print(json.dumps(line))
+
+
 def shell3x3_workload():
     """4,096 metric candidates x 8 model-error draws of Shell 3x3, eval_robust_device on this build
     and, with --baseline-lib, on that library too (its scenario is created through that library)."""
@@ -89,8 +207,7 @@ def shell3x3_workload():
     dev = torch.device("cuda", 0)
     builds = {"this_build": shell3x3_mc(draws=D)}
     if a.baseline_lib:
-        os.environ["MPCT_LIB"] = os.path.abspath(a.baseline_lib)
-        _lib._lib = None  # the next Scenario loads and keeps the baseline library; the first keeps its own
+        load_baseline(a.baseline_lib)  # the next Scenario keeps the baseline library; the first keeps its own
         builds["baseline"] = shell3x3_mc(draws=D)
     N2, Nu, dl, lm = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in candidate_grid(Cn))
     run, outs = {}, {}
@@ -298,6 +415,9 @@ if a.workload == "shell3x3":
     sys.exit(0)
 if a.workload == "shell7x5":
     shell7x5_workload()
+    sys.exit(0)
+if a.levels:
+    config4_tail_workload([float(x) for x in a.levels.split(",")])
     sys.exit(0)
 
 Cn, D, my = a.candidates or 10000, a.draws or 32, 2
