@@ -24,7 +24,8 @@
  *   - robust scoring (mpct_robust_result, mpct_eval_robust, mpct_eval_robust_device,
  *     mpct_robust_instance) is part of ABI 7: new exports and one new struct, added without a
  *     version change because no existing struct, export or behaviour changes.  The tail statistics
- *     (mpct_robust_tail, mpct_eval_robust_tail, mpct_eval_robust_tail_device) were added the same way.
+ *     (mpct_robust_tail, mpct_eval_robust_tail, mpct_eval_robust_tail_device) were added the same way,
+ *     and so was the Pareto analysis of a scored grid (mpct_pareto_result, mpct_pareto_device, mpct_pareto).
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -502,6 +503,68 @@ int32_t mpct_eval_robust_tail_device(mpct_scenario* s, int64_t C, const int32_t*
                                      const double* v, double j_bound, const mpct_opts* opts, int32_t nlev,
                                      const double* levels, mpct_robust_result* out, mpct_robust_tail* tail,
                                      void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Pareto front, domination counts and non-dominated-sorting layers of a scored grid, on the device
+ * (pareto.hip).  mpct_rank_device orders the candidates by one weighted sum, which
+ * collapses the objectives and can never return a candidate on a non-convex part of the front; this is
+ * its multi-objective counterpart, O(C^2 k) pair tests with exact integer results.
+ *
+ * costs is [C][k] row-major, the layout mpct_rank_device takes: the J1 per output of mpct_eval_batch, or
+ * the mean / worst / quantile / cvar columns of the robust entries.  1 <= k <= MPCT_PARETO_MAX_OBJ,
+ * 0 <= C <= MPCT_PARETO_MAX_C.
+ *
+ * Candidate c is VALID when none of its k costs is NaN.  +-INFINITY are ordinary values (a robust mean
+ * may be +INFINITY); -0.0 and +0.0 compare equal.  An invalid candidate dominates nobody and is dominated
+ * by nobody: its dom_count and layer are -1 and it is never in front (mpct_rank_device sorts NaN last,
+ * RobustResult.scores masks with NaN).
+ *
+ * a DOMINATES b when both are valid, a_j <= b_j for every j and a_j < b_j for at least one j.  Equal
+ * vectors do not dominate each other, so the duplicates of a front point are all on the front.
+ *
+ *   dom_count[c]   number of valid candidates that dominate c (the Fonseca-Fleming rank; 0 = on the front)
+ *   front[0 .. n_front)  the valid candidates with dom_count 0, in ascending candidate index;
+ *                  front[n_front .. C) = -1, so the caller's buffer of C entries is fully defined
+ *   n_front[0]     the size of the front
+ *   layer[c]       the non-dominated-sorting layer: 0 on the front, else 1 + the largest layer among c's
+ *                  dominators (peeling the front off repeatedly), computed for max_layers = L layers,
+ *                  1 <= L <= MPCT_PARETO_MAX_LAYERS: a valid candidate deeper than layer L - 1 gets exactly L
+ *                  ("beyond")
+ * Any of the four pointers may be NULL, not all of them; n_front alone is fine.  A repeated call is bitwise
+ * identical; permuting the candidates permutes dom_count and layer and maps the front's set of indices.
+ *
+ * Argument errors, in this order and before any device is touched:
+ *   MPCT_EINVAL  k < 1 or k > MPCT_PARETO_MAX_OBJ
+ *   MPCT_EINVAL  C < 0
+ *   MPCT_ERANGE  C > MPCT_PARETO_MAX_C
+ *   MPCT_EINVAL  costs NULL (with C > 0)
+ *   MPCT_EINVAL  out NULL, or all four of its pointers NULL
+ *   MPCT_EINVAL  front without n_front
+ *   MPCT_EINVAL  max_layers < 0 or > MPCT_PARETO_MAX_LAYERS, or layer non-NULL with max_layers = 0
+ * C = 0 writes n_front[0] = 0 and returns MPCT_OK. */
+#define MPCT_PARETO_MAX_OBJ 16
+#define MPCT_PARETO_MAX_C 1048576
+#define MPCT_PARETO_MAX_LAYERS 64
+typedef struct mpct_pareto_result {
+  int32_t* dom_count; /* [C] */
+  int32_t* layer;     /* [C] */
+  int32_t* front;     /* [C] */
+  int32_t* n_front;   /* [1] */
+} mpct_pareto_result;
+
+/* All pointers DEVICE pointers, n_front included; enqueued on `stream` (NULL = default stream) and NOT
+ * synchronised.  Scratch comes from hipMallocAsync / hipFreeAsync on that stream, as in mpct_rank_device,
+ * so calls on different streams are independent.  The work is bounded by C, k and max_layers alone:
+ * exactly max_layers counting passes are enqueued with no host synchronisation; a pass with no
+ * candidate left leaves at once. */
+int32_t mpct_pareto_device(const double* costs, int64_t C, int32_t k, int32_t max_layers,
+                           const mpct_pareto_result* out, void* stream);
+
+/* Host pointers (MATLAB and C callers); needs no scenario.  device: HIP ordinal, -1 = the current device
+ * (an ordinal out of range is MPCT_EINVAL).  Stages on a stream of its own and waits for that stream only;
+ * the calling thread's current device is unchanged on return.  Without a device: MPCT_EDEVICE with a message. */
+int32_t mpct_pareto(const double* costs, int64_t C, int32_t k, int32_t max_layers, int32_t device,
+                    const mpct_pareto_result* out);
 
 #ifdef __cplusplus
 }

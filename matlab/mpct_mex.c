@@ -28,6 +28,15 @@
  *                                                    fields levels (1 x nlev), quantile, cvar and q_draw
  *                                                    (C x nlev; q_draw is the library's 0-based draw, -1: none);
  *                                                    v and j_bound may be []
+ *   P = mpct_mex('pareto', costs, max_layers, device)
+ *                                                    Pareto front, domination counts and layers of the
+ *                                                    C x k cost table (mpct_pareto; no scenario needed): struct
+ *                                                    with front (n_front x 1, 1-BASED candidate indices,
+ *                                                    ascending, ready to index MATLAB arrays), dom_count and
+ *                                                    layer (C x 1, 0-BASED counts / layers as the library
+ *                                                    defines them, -1: a candidate with a NaN cost); layer is
+ *                                                    [] with max_layers = 0; max_layers and device optional
+ *                                                    (0: no layers; -1: the current device)
  *   mpct_mex('destroy', h)
  *
  * MATLAB layouts (column-major, what the callers already hold):
@@ -523,6 +532,44 @@ static void cmd_eval_robust(mxArray* plhs[], int nrhs, const mxArray* prhs[], in
   plhs[0] = R;
 }
 
+/* P = mpct_mex('pareto', costs [, max_layers, device]): costs is C x k column-major, transposed here into
+ * the library's [C][k] rows; the objective count is the library's to judge (its message is surfaced) */
+static void cmd_pareto(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 2 || nrhs > 4) mexErrMsgIdAndTxt("mpct:arg", "usage: P = mpct_mex('pareto', costs [, max_layers, device])");
+  const mxArray* a = prhs[1];
+  if (!a || !mxIsNumeric(a) || mxIsComplex(a) || mxIsSparse(a) || mxGetNumberOfDimensions(a) != 2)
+    mexErrMsgIdAndTxt("mpct:arg", "'costs' must be a real full C x k matrix");
+  const long C = (long)mxGetM(a), k = (long)mxGetN(a);
+  const double ml = (nrhs > 2 && !mxIsEmpty(prhs[2])) ? scalar(prhs[2], "max_layers") : 0.0;
+  const double dv = (nrhs > 3 && !mxIsEmpty(prhs[3])) ? scalar(prhs[3], "device") : -1.0;
+  if (ml != floor(ml) || fabs(ml) > 1e6) mexErrMsgIdAndTxt("mpct:arg", "'max_layers' must be an integer");
+  if (dv != floor(dv) || fabs(dv) > 1e6) mexErrMsgIdAndTxt("mpct:arg", "'device' must be an integer");
+  if (k > 1000000) mexErrMsgIdAndTxt("mpct:arg", "'costs' has too many columns");
+  double* cm = doubles(a, C * k, "costs");
+  double* rows = (double*)mxMalloc((size_t)(C * k + 1) * sizeof(double));
+  for (long c = 0; c < C; ++c)
+    for (long j = 0; j < k; ++j) rows[c * k + j] = cm[(size_t)j * C + c];
+  mpct_pareto_result r;
+  r.dom_count = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  r.layer = ml != 0.0 ? (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t)) : NULL;
+  r.front = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  int32_t nf = 0;
+  r.n_front = &nf;
+  if (mpct_pareto(rows, C, (int32_t)k, (int32_t)ml, (int32_t)dv, &r) != MPCT_OK) lib_error("mpct:pareto");
+  const char* names[3] = {"front", "dom_count", "layer"};
+  mxArray* P = mxCreateStructMatrix(1, 1, 3, names);
+  mxArray* f = mxCreateDoubleMatrix((mwSize)nf, 1, mxREAL);
+  for (long i = 0; i < nf; ++i) mxGetPr(f)[i] = (double)r.front[i] + 1.0; /* 1-based */
+  mxSetField(P, 0, "front", f);
+  mxArray* d = mxCreateDoubleMatrix((mwSize)C, 1, mxREAL);
+  for (long c = 0; c < C; ++c) mxGetPr(d)[c] = r.dom_count[c];
+  mxSetField(P, 0, "dom_count", d);
+  mxArray* l = mxCreateDoubleMatrix(r.layer ? (mwSize)C : 0, r.layer ? 1 : 0, mxREAL);
+  for (long c = 0; r.layer && c < C; ++c) mxGetPr(l)[c] = r.layer[c];
+  mxSetField(P, 0, "layer", l);
+  plhs[0] = P;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (!g_atexit) {
     mexAtExit(destroy_all);
@@ -547,6 +594,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_eval_robust(plhs, nrhs, prhs, 0);
   } else if (!strcmp(cmd, "eval_robust_tail")) {
     cmd_eval_robust(plhs, nrhs, prhs, 1);
+  } else if (!strcmp(cmd, "pareto")) {
+    cmd_pareto(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "instance")) {
     if (nrhs < 2) mexErrMsgIdAndTxt("mpct:arg", "usage: name = mpct_mex('instance', h [, opts])");
     mpct_scenario* s = handle(prhs[1]);

@@ -14,6 +14,7 @@
 #include "launch_fan.h"
 #include "work_order.h"
 #include "dtc_robust.h"
+#include "pareto.h"
 
 namespace mpct {
 // defined in gpc_kernel_launch.hip
@@ -376,6 +377,113 @@ extern "C" int32_t mpct_rank_device(const double* costs, int64_t C, int32_t k, c
   const int rc = rank_device(costs, C, k, w, perm, static_cast<hipStream_t>(stream), &err);
   if (rc) return fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err);
   return MPCT_OK;
+}
+
+// ---- Pareto front, domination counts and layers (pareto.hip).  The argument checks of both entries,
+// in the order include/mpct.h states, before any device is touched
+static int pareto_check(const double* costs, int64_t C, int32_t k, int32_t max_layers, const mpct_pareto_result* out) {
+  if (k < 1 || k > MPCT_PARETO_MAX_OBJ) return fail(MPCT_EINVAL, "k must be 1 .. MPCT_PARETO_MAX_OBJ");
+  if (C < 0) return fail(MPCT_EINVAL, "C < 0");
+  if (C > MPCT_PARETO_MAX_C) return fail(MPCT_ERANGE, "C exceeds MPCT_PARETO_MAX_C");
+  if (C > 0 && !costs) return fail(MPCT_EINVAL, "costs is NULL");
+  if (!out || !(out->dom_count || out->layer || out->front || out->n_front))
+    return fail(MPCT_EINVAL, "no output pointer in mpct_pareto_result");
+  if (out->front && !out->n_front) return fail(MPCT_EINVAL, "front needs n_front");
+  if (max_layers < 0 || max_layers > MPCT_PARETO_MAX_LAYERS || (out->layer && max_layers < 1))
+    return fail(MPCT_EINVAL, "max_layers must be 1 .. MPCT_PARETO_MAX_LAYERS when layer is asked for (0 without)");
+  return MPCT_OK;
+}
+
+static int32_t pareto_launch(const double* costs, int64_t C, int32_t k, int32_t max_layers, const mpct_pareto_result* out,
+                             hipStream_t stream, int tile, int split) {
+  std::string err;
+  const ParetoOut po{out->dom_count, out->layer, out->front, out->n_front};
+  const int rc = pareto_device(costs, C, k, max_layers, po, stream, &err, tile, split);
+  if (rc) return fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err);
+  return MPCT_OK;
+}
+
+extern "C" int32_t mpct_pareto_device(const double* costs, int64_t C, int32_t k, int32_t max_layers,
+                                      const mpct_pareto_result* out, void* stream) {
+  const int rc = pareto_check(costs, C, k, max_layers, out);
+  if (rc) return rc;
+  return pareto_launch(costs, C, k, max_layers, out, static_cast<hipStream_t>(stream), 0, 0);
+}
+
+// the device entry with the tile length (128 or 256) and the number of a-chunks forced: the A/B of
+// tools/pareto_bench.py and the empty-chunk test; a hook, not part of include/mpct.h
+extern "C" int32_t mpct_internal_pareto_tuned(const double* costs, int64_t C, int32_t k, int32_t max_layers,
+                                              const mpct_pareto_result* out, void* stream, int32_t tile, int32_t split) {
+  const int rc = pareto_check(costs, C, k, max_layers, out);
+  if (rc) return rc;
+  if (split < 0 || split > 1024) return fail(MPCT_EINVAL, "split must be 0 .. 1024");
+  return pareto_launch(costs, C, k, max_layers, out, static_cast<hipStream_t>(stream), tile, split);
+}
+
+// the grid the device entry launches for C candidates: {tile, chunks along a, competitors per chunk}
+extern "C" int32_t mpct_internal_pareto_grid(int64_t C, int32_t* tile_split_chunk) {
+  if (C < 0 || C > MPCT_PARETO_MAX_C || !tile_split_chunk) return fail(MPCT_EINVAL, "bad argument");
+  int split = 1, chunk = kParetoTile;
+  pareto_grid(C, kParetoTile, 0, &split, &chunk);
+  tile_split_chunk[0] = kParetoTile;
+  tile_split_chunk[1] = split;
+  tile_split_chunk[2] = chunk;
+  return MPCT_OK;
+}
+
+extern "C" int32_t mpct_pareto(const double* costs, int64_t C, int32_t k, int32_t max_layers, int32_t device,
+                               const mpct_pareto_result* out) {
+  int rc = pareto_check(costs, C, k, max_layers, out);
+  if (rc) return rc;
+  if (C == 0) {  // nothing to stage
+    if (out->n_front) out->n_front[0] = 0;
+    return MPCT_OK;
+  }
+  int cur = -1, cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
+    return fail(MPCT_EDEVICE, "no HIP device (mpct_pareto needs a GPU)");
+  const int dev = device < 0 ? cur : device;
+  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
+  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
+  // one blob: costs | dom_count | layer | front | n_front, each 256-B aligned; a stream of this call's own
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t nc = al((size_t)C * k * sizeof(double)), ni = al((size_t)C * sizeof(int32_t));
+  hipStream_t st = nullptr;
+  char* blob = nullptr;
+  rc = MPCT_OK;
+  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
+  } else if (hipMalloc(reinterpret_cast<void**>(&blob), nc + 3 * ni + 256) != hipSuccess) {
+    rc = fail(MPCT_ENOMEM, "hipMalloc failed (Pareto staging)");
+  } else {
+    mpct_pareto_result d{};
+    d.dom_count = out->dom_count ? reinterpret_cast<int32_t*>(blob + nc) : nullptr;
+    d.layer = out->layer ? reinterpret_cast<int32_t*>(blob + nc + ni) : nullptr;
+    d.front = out->front ? reinterpret_cast<int32_t*>(blob + nc + 2 * ni) : nullptr;
+    d.n_front = out->n_front ? reinterpret_cast<int32_t*>(blob + nc + 3 * ni) : nullptr;
+    bool ok = hipMemcpyAsync(blob, costs, (size_t)C * k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (costs)");
+    if (ok) {
+      rc = pareto_launch(reinterpret_cast<const double*>(blob), C, k, max_layers, &d, st, 0, 0);
+      ok = rc == MPCT_OK;
+    }
+    if (ok) {
+      const size_t bi = (size_t)C * sizeof(int32_t);
+      ok = (!d.dom_count || hipMemcpyAsync(out->dom_count, d.dom_count, bi, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.layer || hipMemcpyAsync(out->layer, d.layer, bi, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.front || hipMemcpyAsync(out->front, d.front, bi, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.n_front || hipMemcpyAsync(out->n_front, d.n_front, sizeof(int32_t), hipMemcpyDeviceToHost, st) == hipSuccess);
+      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (Pareto results)");
+    }
+    // this call's stream only, also after an error: the blob is freed below
+    const hipError_t se = hipStreamSynchronize(st);
+    if (rc == MPCT_OK && se != hipSuccess)
+      rc = fail(MPCT_EDEVICE, std::string("mpct_pareto failed on the device: ") + hipGetErrorString(se));
+  }
+  if (blob) (void)hipFree(blob);
+  if (st) (void)hipStreamDestroy(st);
+  if (dev != cur) (void)hipSetDevice(cur);
+  return rc;
 }
 
 // Host-pointer staging of one call on the context's own stream, shared by eval_host and

@@ -35,6 +35,11 @@ int order_candidates(int kind, int my, int nu, long long C, const int* N2, const
 int rank_device(const double* costs, long long C, int k, const double* w, int* perm, hipStream_t stream,
                 std::string* err);
 
+// exclusive prefix sum of n ints (hipCUB DeviceScan; deterministic), on `stream`: the ordered compaction
+// of the Pareto front (pareto.hip).  scan_exclusive_bytes sizes the temporary storage the scan needs
+int scan_exclusive_bytes(int n, size_t* bytes, std::string* err);
+int scan_exclusive(const int* in, int* out, int n, void* temp, size_t temp_bytes, hipStream_t stream, std::string* err);
+
 // staging rows for the cost records of an ordered launch of S simulations (DevResult::stage), and
 // the gather of those rows back into the caller's order (one thread per simulation, contiguous
 // writes); enqueue the gather after every launch of the batch

@@ -730,6 +730,23 @@ int rank_device(const double* costs, long long C, int k, const double* w, int* p
   return rc;
 }
 
+int scan_exclusive_bytes(int n, size_t* bytes, std::string* err) {
+  *bytes = 0;
+  if (hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (const int*)nullptr, (int*)nullptr, n) != hipSuccess) {
+    *err = "hipcub::DeviceScan::ExclusiveSum (size query) failed";
+    return -3;
+  }
+  return 0;
+}
+
+int scan_exclusive(const int* in, int* out, int n, void* temp, size_t temp_bytes, hipStream_t stream, std::string* err) {
+  if (hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, in, out, n, stream) != hipSuccess) {
+    *err = "hipcub::DeviceScan::ExclusiveSum failed";
+    return -3;
+  }
+  return 0;
+}
+
 void order_release(WorkOrder& wo) {
   if (wo.buf) (void)hipFree(wo.buf);
   if (wo.stage) (void)hipFree(wo.stage);

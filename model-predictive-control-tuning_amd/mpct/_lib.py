@@ -86,6 +86,10 @@ class MpctRobustResult(C.Structure):
                 ("status", c_int32_p), ("J1", c_double_p)]
 
 
+class MpctParetoResult(C.Structure):
+    _fields_ = [("dom_count", c_int32_p), ("layer", c_int32_p), ("front", c_int32_p), ("n_front", c_int32_p)]
+
+
 class MpctRobustTail(C.Structure):
     _fields_ = [("quantile", c_double_p), ("cvar", c_double_p), ("q_draw", c_int32_p)]
 
@@ -96,11 +100,12 @@ EXPORTS = [
     "mpct_nmpc_scenario_create", "mpct_eval_batch_multi", "mpct_shard_candidates", "mpct_kernel_instance",
     "mpct_rank_device", "mpct_eval_robust", "mpct_eval_robust_device", "mpct_robust_instance",
     "mpct_scenario_create_est", "mpct_nmpc_scenario_create_var", "mpct_eval_robust_tail",
-    "mpct_eval_robust_tail_device",
+    "mpct_eval_robust_tail_device", "mpct_pareto_device", "mpct_pareto",
 ]
 
 ABI_VERSION = 7
 TAIL_MAX_LEVELS, TAIL_MAX_DRAWS = 8, 4096
+PARETO_MAX_OBJ, PARETO_MAX_C, PARETO_MAX_LAYERS = 16, 1048576, 64
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
 ST_SQP_MAXITER, ST_BOUNDS, ST_NOT_RUN = 32, 64, 128
 NMPC_VANDEVUSSE = 1
@@ -187,6 +192,16 @@ def load():
     lib.mpct_internal_robust_tail.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                               C.c_int32, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mpct_internal_robust_tail.restype = C.c_int32
+    lib.mpct_pareto_device.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(MpctParetoResult),
+                                       C.c_void_p]
+    lib.mpct_pareto_device.restype = C.c_int32
+    lib.mpct_pareto.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MpctParetoResult)]
+    lib.mpct_pareto.restype = C.c_int32
+    # the device entry with the tile length and the a-split forced, and the default grid: test / bench hooks
+    lib.mpct_internal_pareto_tuned.argtypes = lib.mpct_pareto_device.argtypes + [C.c_int32, C.c_int32]
+    lib.mpct_internal_pareto_tuned.restype = C.c_int32
+    lib.mpct_internal_pareto_grid.argtypes = [C.c_int64, c_int32_p]
+    lib.mpct_internal_pareto_grid.restype = C.c_int32
     if lib.mpct_abi_version() != ABI_VERSION:
         raise ImportError("libmpct ABI version mismatch")
     _lib = lib

@@ -119,6 +119,85 @@ def rank_candidates(costs: torch.Tensor, weights: torch.Tensor, C: int | None = 
     return torch.argsort(s, stable=True)
 
 
+def _pareto_torch(costs: torch.Tensor, max_layers: int, chunk: int = 1024):
+    """The contract of mpct_pareto_device (include/mpct.h) as chunked torch expressions, on the tensor's
+    device: the CPU path of pareto_candidates, and what tools/pareto_bench.py times the kernel against."""
+    Cn, k = costs.shape
+    dev = costs.device
+    valid = ~torch.isnan(costs).any(dim=1)
+
+    def count(alive, todo):
+        """dominators among `alive` of every candidate in `todo` (index tensor)"""
+        out = torch.zeros(todo.numel(), dtype=torch.int64, device=dev)
+        a_idx = torch.nonzero(alive).flatten()
+        for b0 in range(0, todo.numel(), chunk):
+            b = costs[todo[b0:b0 + chunk]]
+            acc = torch.zeros(b.shape[0], dtype=torch.int64, device=dev)
+            for a0 in range(0, a_idx.numel(), chunk):
+                a = costs[a_idx[a0:a0 + chunk]]
+                le = (a[:, None, :] <= b[None, :, :]).all(dim=2)
+                lt = (a[:, None, :] < b[None, :, :]).any(dim=2)
+                acc += (le & lt).sum(dim=0)
+            out[b0:b0 + chunk] = acc
+        return out
+
+    dom = torch.full((Cn,), -1, dtype=torch.int32, device=dev)
+    vi = torch.nonzero(valid).flatten()
+    dom[vi] = count(valid, vi).to(torch.int32)
+    members = torch.nonzero(valid & (dom == 0)).flatten()
+    front = torch.full((Cn,), -1, dtype=torch.int32, device=dev)
+    front[:members.numel()] = members.to(torch.int32)
+    layer = None
+    if max_layers > 0:
+        layer = torch.where(valid, max_layers, -1).to(torch.int32)
+        alive = valid.clone()
+        for p in range(max_layers):
+            todo = torch.nonzero(alive).flatten()
+            if todo.numel() == 0:
+                break
+            top = todo[(dom[todo] == 0) if p == 0 else (count(alive, todo) == 0)]
+            layer[top] = p
+            alive[top] = False
+    return dom, layer, front, int(members.numel())
+
+
+def pareto_candidates(costs: torch.Tensor, C: int | None = None, max_layers: int = 0) -> dict:
+    """Pareto front, domination counts and layers of the gathered cost records (the multi-objective
+    counterpart of rank_candidates; contract: mpct_pareto_device in include/mpct.h).  Returns a dict of
+    tensors on the costs' device: dom_count [C] int32 (-1: a NaN record), front [n_front] int64 ascending,
+    and layer [C] int32 with max_layers in 1 .. 64.  Identical on every rank, because every rank analyses
+    the same gathered tensor and all results are integers.  GPU tensors go through mpct_pareto_device on
+    the current stream; CPU tensors (the gloo tests) through chunked torch expressions."""
+    if C is not None:
+        costs = costs[:C]
+    if costs.dim() == 1:
+        costs = costs[:, None]
+    if not 0 <= int(max_layers) <= 64:
+        raise ValueError("max_layers must be 0 .. 64")
+    c = costs.to(torch.float64).contiguous()
+    n = c.shape[0]
+    if c.is_cuda:
+        from . import engine
+
+        out = dict(dom_count=torch.empty(n, dtype=torch.int32, device=c.device),
+                   front=torch.empty(n, dtype=torch.int32, device=c.device),
+                   n_front=torch.empty(1, dtype=torch.int32, device=c.device))
+        if max_layers:
+            out["layer"] = torch.empty(n, dtype=torch.int32, device=c.device)
+        engine.pareto_device(c, out, max_layers=max_layers)
+        res = dict(dom_count=out["dom_count"], front=out["front"][:int(out["n_front"].item())].to(torch.int64))
+        if max_layers:
+            res["layer"] = out["layer"]
+        return res
+    if not 1 <= c.shape[1] <= 16:
+        raise ValueError("k must be 1 .. 16")
+    dom, layer, front, nf = _pareto_torch(c, int(max_layers))
+    res = dict(dom_count=dom, front=front[:nf].to(torch.int64))
+    if max_layers:
+        res["layer"] = layer
+    return res
+
+
 # measured one-GPU time of every config-3 cell alone (tools/shard_balance.py --cells): the (N2, Nu)
 # cells of mpct.scenarios.config3_grid with 1024 lambda draws each, whole and in two halves
 CELL_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "config3_cells.json")

@@ -4,6 +4,8 @@
   eval_batch          mpct_eval_batch (host arrays): C candidates x nref reference sets
   eval_batch_device   mpct_eval_batch_device (torch CUDA tensors, enqueued on a stream)
   closedloop_toolbox  drop-in for closedloop_toolbox.m:1 (one candidate, full trajectories)
+  pareto              mpct_pareto: front, domination counts and layers of a [C, k] cost table
+  pareto_device       mpct_pareto_device (torch CUDA tensors, enqueued on the current stream)
 
 No CPU fallback: every numerical result comes from the HIP kernel.
 """
@@ -394,6 +396,23 @@ class RobustResult:
         s[np.asarray(self.n_failed) > int(max_failed)] = np.nan
         return s
 
+    def pareto(self, stat: str = "worst", max_failed: int = 0, max_layers: int = 0, columns=(), device: int = -1):
+        """Pareto analysis (``pareto``) of the (C, my) statistic ``scores`` returns, so a candidate with more
+        than ``max_failed`` failed draws is invalid: dom_count and layer -1, never on the front.
+        ``columns`` adds tail columns of an eval_robust(levels=...) result as further objectives: pairs
+        (name, j) with name 'quantile' or 'cvar' and j the level's index."""
+        cols = [self.scores(max_failed, stat)]
+        for name, j in columns:
+            if name not in ("quantile", "cvar"):
+                raise ValueError("columns take 'quantile' or 'cvar'")
+            tab = getattr(self, name)
+            if tab is None:
+                raise ValueError("this result has no %s: call eval_robust with levels=" % name)
+            cols.append(np.asarray(tab, dtype=float)[:, int(j)].reshape(-1, 1))
+        costs = np.hstack(cols)
+        costs[np.isnan(cols[0]).any(axis=1)] = np.nan   # the masking of scores covers the added columns too
+        return pareto(costs, max_layers=max_layers, device=device)
+
 
 def _levels(levels):
     """The levels of a tail call as the contiguous float64 vector the library reads (a host pointer)."""
@@ -491,3 +510,55 @@ def robust_instance(sc: Scenario) -> str:
     if n < 0:
         raise MpctError(_lib.last_error())
     return buf.value.decode()
+
+
+# --------------------------------------------------------------------------------------------
+# Pareto front, domination counts and layers of a scored grid (mpct_pareto, include/mpct.h)
+@dataclass
+class ParetoResult:
+    """a dominates b when both are valid (no NaN cost), a <= b in every objective and a < b in one."""
+    dom_count: np.ndarray           # (C,) valid candidates that dominate c; 0 = on the front; -1 = invalid
+    layer: np.ndarray | None        # (C,) non-dominated-sorting layer, max_layers = deeper; -1 = invalid; None without max_layers
+    front: np.ndarray               # (n_front,) the candidates with dom_count 0, ascending
+
+
+def _pareto_costs(costs):
+    a = np.ascontiguousarray(costs, dtype=np.float64)
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)
+    if a.ndim != 2:
+        raise ValueError("costs must be (C, k)")
+    return a
+
+
+def pareto(costs, max_layers: int = 0, device: int = -1) -> ParetoResult:
+    """mpct_pareto: Pareto front, domination counts and (with ``max_layers`` = 1 .. 64) the
+    non-dominated-sorting layers of the (C, k) cost table, computed on the GPU (host arrays in and out)."""
+    a = _pareto_costs(costs)
+    Cn, k = a.shape
+    dom = np.zeros(Cn, dtype=np.int32)
+    lay = np.zeros(Cn, dtype=np.int32) if max_layers else None
+    front = np.zeros(Cn, dtype=np.int32)
+    nf = np.zeros(1, dtype=np.int32)
+    r = _lib.MpctParetoResult(_ip(dom), _ip(lay) if lay is not None else None, _ip(front), _ip(nf))
+    rc = _lib.load().mpct_pareto(a.ctypes.data, Cn, k, int(max_layers), int(device), C.byref(r))
+    if rc != 0:
+        raise MpctError("mpct_pareto failed (%d): %s" % (rc, _lib.last_error()))
+    return ParetoResult(dom_count=dom, layer=lay, front=front[:int(nf[0])].copy())
+
+
+def pareto_device(costs, out: dict, max_layers: int = 0):
+    """mpct_pareto_device: ``costs`` is a float64 CUDA (HIP) tensor [C, k]; the results are written into the
+    int32 tensors of ``out`` (keys dom_count, layer, front: [C]; n_front: [1]; any may be absent, front
+    needs n_front).  Enqueued on the current torch stream of the tensor's device and not synchronised."""
+    import torch
+
+    if costs.dtype != torch.float64 or costs.dim() != 2 or not costs.is_contiguous():
+        raise ValueError("costs must be a contiguous float64 tensor [C, k]")
+    r = _lib.MpctParetoResult(*[_tptr(out.get(f), _lib.c_int32_p) for f in ("dom_count", "layer", "front", "n_front")])
+    stream = torch.cuda.current_stream(costs.device).cuda_stream
+    with torch.cuda.device(costs.device):
+        rc = _lib.load().mpct_pareto_device(C.c_void_p(costs.data_ptr()), costs.shape[0], costs.shape[1],
+                                            int(max_layers), C.byref(r), C.c_void_p(stream))
+    if rc != 0:
+        raise MpctError("mpct_pareto_device failed (%d): %s" % (rc, _lib.last_error()))

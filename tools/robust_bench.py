@@ -94,7 +94,8 @@ def load_baseline(path):
     import types
     from mpct import _lib
 
-    new = ("mpct_eval_robust_tail", "mpct_eval_robust_tail_device", "mpct_internal_robust_tail")
+    new = ("mpct_eval_robust_tail", "mpct_eval_robust_tail_device", "mpct_internal_robust_tail", "mpct_pareto_device",
+           "mpct_pareto", "mpct_internal_pareto_tuned", "mpct_internal_pareto_grid")
 
     class Baseline(ctypes.CDLL):
         def __getattr__(self, name):
