@@ -56,8 +56,14 @@ static DevScenario check_valid(const char* name, std::unique_ptr<mpct_scenario> 
   if (lanes)
     for (const auto& t : pk.islots)
       if (t.field == &DevScenario::sm_hoff) *lanes = t.bytes / 4;
-  std::printf("valid %s: %zu tables, %zu blob bytes, small %d small_dtc %d regpath %d\n", name, tables, pk.blob.size(),
-              ds.small, ds.small_dtc, ds.regpath);
+  // the dispatch key's Gram tables: none for NMPC, band and my > 4 scenarios, and then no pointer either
+  std::vector<double> gram;
+  gram_tables(s.get(), gram);
+  CHECK(gram.empty() == (s->nmpc || s->mdband || s->my > 4));
+  CHECK((ds.gram != nullptr) == !gram.empty());
+  CHECK(gram.empty() || std::memcmp(ds.gram, gram.data(), gram.size() * 8) == 0);
+  std::printf("valid %s: %zu tables, %zu blob bytes, small %d small_dtc %d regpath %d, gram %zu doubles\n", name, tables,
+              pk.blob.size(), ds.small, ds.small_dtc, ds.regpath, gram.size());
   return ds;
 }
 

@@ -14,6 +14,10 @@ def test_host_tables_under_sanitizers(tmp_path):
     stdout = host_program.run(host_program.build("host_tables_check", tmp_path))
     for name in ("shell3x3", "dtc 2x2:", "dtc 2x2, bounded", "mdband", "van de vusse nmpc"):
         assert "valid " + name in stdout, name
+    # the dispatch key's Gram tables (gram_tables): built for the GPC and DTC scenarios, none for band and NMPC
+    gram = {m.group(1): int(m.group(2)) for m in re.finditer(r"valid ([^:]+):.*gram (\d+) doubles", stdout)}
+    assert gram["shell3x3 (derived CARIMA)"] == 30 * 5 * 3 * 272 and gram["dtc 2x2"] == 10 * 4 * 2 * 272, gram
+    assert gram["mdband 2x(1+1)"] == 0 and gram["van de vusse nmpc"] == 0, gram
 
     header = open(os.path.join(host_program.CSRC, "scenario_tables.h")).read()
     checks = REJECT.findall(header)
