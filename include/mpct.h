@@ -25,7 +25,9 @@
  *     mpct_robust_instance) is part of ABI 7: new exports and one new struct, added without a
  *     version change because no existing struct, export or behaviour changes.  The tail statistics
  *     (mpct_robust_tail, mpct_eval_robust_tail, mpct_eval_robust_tail_device) were added the same way,
- *     and so was the Pareto analysis of a scored grid (mpct_pareto_result, mpct_pareto_device, mpct_pareto).
+ *     and so was the Pareto analysis of a scored grid (mpct_pareto_result, mpct_pareto_device, mpct_pareto),
+ *     and the closed-loop performance indices (mpct_index_params, mpct_index_result, mpct_indices_device,
+ *     mpct_indices, mpct_eval_indices, mpct_eval_indices_device).
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -565,6 +567,123 @@ int32_t mpct_pareto_device(const double* costs, int64_t C, int32_t k, int32_t ma
  * the calling thread's current device is unchanged on return.  Without a device: MPCT_EDEVICE with a message. */
 int32_t mpct_pareto(const double* costs, int64_t C, int32_t k, int32_t max_layers, int32_t device,
                     const mpct_pareto_result* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Closed-loop performance indices per simulation, reduced on the device from the trajectories
+ * (traj_indices.hip): what a control engineer reads off the plots of the reference's drivers
+ * -- integrated errors, overshoot, settling time, valve travel, peak move -- as columns for mpct_pareto or
+ * mpct_rank_device, without the trajectories leaving the device.
+ *
+ * Trajectories in mpct_result's layout: y[S][my][nit], u[S][nu][nit], r[nref][my][nit]; simulation s reads
+ * reference set s % nref (S is a multiple of nref).  The indices cover the samples t = t0 .. nit-1.
+ *
+ * Output row (s, i), with e(t) = y(t) - r(t), r_f = r(nit-1), d = r_f - y(t0), sigma = sign(d) (0 for d = 0):
+ *   iae      sum_t |e(t)|
+ *   ise      sum_t e(t)*e(t)
+ *   itae     sum_t (double)(t - t0) * |e(t)|
+ *   emax     max_t |e(t)|;  t_emax  the first t that attains it
+ *   over     sigma != 0: the excursion past the reference in the step's direction, max_t sigma*e(t) where that
+ *            is > 0, else +0.0.  sigma = 0 (a regulated or interaction channel): emax
+ *   e_final  e(nit-1), signed
+ *   settle   the smallest T in [t0, nit] with |y(t) - r_f| <= band for every t >= T, where
+ *            band = band_rel*|d| + band_abs: the last violating sample + 1, t0 when there is none, and
+ *            nit = "not settled at the last sample"
+ * Input row (s, n), with du(t) = u(t) - u(t-1) for t = t0+1 .. nit-1:
+ *   tv       sum |du|         du2    sum du*du        dumax  max |du|; the three are 0.0 over an empty range
+ *   u_lo, u_hi  min and max of u(t), t >= t0; a zero extreme is +0.0 whatever the signs of the row's zeros
+ *
+ * Row validity.  A row is VALID when every sample it reads in [t0, nit) is finite: y and r for an output
+ * row, u for an input row.  An invalid row gives NaN in every double field and -1 in every integer field;
+ * other rows are not affected.  This covers the NaN trajectories of MPCT_ST_SKIPPED, MPCT_ST_BADHORIZON and
+ * MPCT_ST_NOT_RUN slots; samples before t0 are never read.
+ *
+ * No contraction.  Every product above is rounded to double before it is added (e*e, (t-t0)*|e|, du*du and
+ * band_rel*|d|): no fused multiply-add anywhere, so a host restatement in plain IEEE double arithmetic gives
+ * the same bits -- one fused operation in `band` could move `settle` by a sample.
+ *
+ * Summation order (fixed).  Lane l = (t - t0) mod 64 accumulates its samples in ascending t, starting from
+ * 0.0; a lane without a sample keeps 0.0.  The 64 partials p0 .. p63 are then combined as a pairwise tree in
+ * lane order: (p0 + p1), (p2 + p3), ..; then ((p0 + p1) + (p2 + p3)), ..; up to (p0..p31) + (p32..p63).
+ * A repeated call is bitwise identical and a record does not depend on the simulation's place in the
+ * batch.  Maxima, minima, t_emax and settle are exact whatever the order.
+ *
+ * Any result pointer may be NULL, but not all of them.  y and r may be NULL when no output-row field is
+ * requested, u when no input-row field is.  Only the requested arrays are written, and only their S rows.
+ *
+ * Argument errors, in this order and before any device is touched:
+ *   MPCT_EINVAL  params NULL; S < 0, my < 0, nu < 0 or nit < 1
+ *   MPCT_EINVAL  nref < 1
+ *   MPCT_EINVAL  S not a multiple of nref
+ *   MPCT_EINVAL  t0 < 0 or t0 >= nit
+ *   MPCT_EINVAL  band_rel or band_abs negative, infinite or NaN
+ *   MPCT_EINVAL  out NULL, or all thirteen of its pointers NULL
+ *   MPCT_EINVAL  an output-row field with my < 1, or (S > 0) with y or r NULL; an input-row field with
+ *                nu < 1, or (S > 0) with u NULL
+ *   MPCT_ERANGE  S*my or S*nu > MPCT_INDEX_MAX_ROWS (one wave per row, four rows per workgroup)
+ * S = 0 is MPCT_OK and writes nothing. */
+#define MPCT_INDEX_MAX_ROWS 2147483647
+typedef struct mpct_index_params {
+  int32_t t0;      /* first sample of the indices, 0 <= t0 < nit */
+  double band_rel; /* settling band relative to the step size |d| (0.02 = the 2 % band) */
+  double band_abs; /* plus an absolute band; both finite and >= 0 */
+} mpct_index_params;
+
+typedef struct mpct_index_result {
+  double* iae;      /* [S*my] */
+  double* ise;      /* [S*my] */
+  double* itae;     /* [S*my] */
+  double* emax;     /* [S*my] */
+  int32_t* t_emax;  /* [S*my] */
+  double* over;     /* [S*my] */
+  double* e_final;  /* [S*my] */
+  int32_t* settle;  /* [S*my] */
+  double* tv;       /* [S*nu] */
+  double* du2;      /* [S*nu] */
+  double* dumax;    /* [S*nu] */
+  double* u_lo;     /* [S*nu] */
+  double* u_hi;     /* [S*nu] */
+} mpct_index_result;
+
+/* All pointers DEVICE pointers; enqueued on `stream` (NULL = default stream) and NOT synchronised.  Needs no
+ * scenario and no scratch: one kernel launch. */
+int32_t mpct_indices_device(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my,
+                            int32_t nu, int32_t nit, const mpct_index_params* params, const mpct_index_result* out,
+                            void* stream);
+
+/* Host pointers (MATLAB and C callers), for trajectories from any source, MATLAB's own sim included.
+ * device: HIP ordinal, -1 = the current device (an ordinal out of range is MPCT_EINVAL).  Stages on a stream
+ * of its own and waits for that stream only; the calling thread's current device is unchanged on return.
+ * Without a device: MPCT_EDEVICE with a message. */
+int32_t mpct_indices(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my, int32_t nu,
+                     int32_t nit, const mpct_index_params* params, int32_t device, const mpct_index_result* out);
+
+/* Score a batch and return only the index records (host pointers; arguments as mpct_eval_batch).  The
+ * closed loops run with their trajectories written to device scratch that belongs to the scenario's context,
+ * traj_indices_kernel reduces them there on the same stream, and only the records travel back: S = C*nref
+ * simulations, output rows [S*my], input rows [S*nu]; the reference sets of the indices are the call's r.
+ *   res   optional: J1, j21, j22, Jnu, status and qp_iters of the same launch (j21 and Jnu come back NaN: the
+ *         call is closed-loop only).  Its trajectory pointers y, u, ys, uopt must be NULL.
+ *   opts  open_loop = 1 is MPCT_EINVAL; want_traj is ignored (the call sets it).
+ * Chunking.  The trajectory scratch is bounded by MPCT_INDEX_SCRATCH_BYTES (or one candidate's trajectories,
+ * nref*(my+nu)*nit*8 bytes, where that is more): the batch is walked in chunks of whole candidates, each
+ * chunk's launch followed by the index kernel on the same stream.  Every record is bitwise independent of
+ * the chunk size.
+ * MPCT_EINVAL, in this order and before any device is touched: s NULL; params NULL; open_loop set; a
+ * trajectory pointer in res; then everything mpct_eval_batch rejects; then the checks of mpct_indices_device
+ * from t0 on.  C = 0 is MPCT_OK and writes nothing.  Without a device: MPCT_EDEVICE with a message. */
+#define MPCT_INDEX_SCRATCH_BYTES 268435456 /* 256 MiB */
+int32_t mpct_eval_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
+                          const double* lambda, int32_t nref, const double* r, const double* v, const mpct_opts* opts,
+                          const mpct_index_params* params, mpct_result* res, const mpct_index_result* out);
+
+/* Same, all pointers DEVICE pointers (res's and out's included), enqueued on `stream` (NULL = default
+ * stream) and NOT synchronised: the contract of mpct_eval_batch_device.  The trajectory scratch belongs to
+ * the scenario; a later call on another stream waits for the one before it, and a regrow waits for the work
+ * on the old buffer before freeing it. */
+int32_t mpct_eval_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
+                                 const double* lambda, int32_t nref, const double* r, const double* v,
+                                 const mpct_opts* opts, const mpct_index_params* params, mpct_result* res,
+                                 const mpct_index_result* out, void* stream);
 
 #ifdef __cplusplus
 }

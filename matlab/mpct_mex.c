@@ -37,6 +37,15 @@
  *                                                    defines them, -1: a candidate with a NaN cost); layer is
  *                                                    [] with max_layers = 0; max_layers and device optional
  *                                                    (0: no layers; -1: the current device)
+ *   I = mpct_mex('indices', y, u, r, params)         performance indices of stored trajectories (mpct_indices;
+ *                                                    no scenario needed): y my x nit x S, u nu x nit x S,
+ *                                                    r my x nit x nref; struct with iae, ise, itae, emax, t_emax,
+ *                                                    over, e_final, settle (S x my) and tv, du2, dumax, u_lo,
+ *                                                    u_hi (S x nu); params optional (t0, band_rel, band_abs,
+ *                                                    device); t0, t_emax, settle are 0-BASED samples, -1: invalid
+ *   I = mpct_mex('eval_indices', h, N2, Nu, delta, lambda, r, v, params)
+ *                                                    score the batch and return only its index records
+ *                                                    (mpct_eval_indices), plus J1, j22, status, iters
  *   mpct_mex('destroy', h)
  *
  * MATLAB layouts (column-major, what the callers already hold):
@@ -570,6 +579,157 @@ static void cmd_pareto(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = P;
 }
 
+/* ---- closed-loop performance indices (mpct_indices, mpct_eval_indices; include/mpct.h) */
+static const char* const kIndexNames[13] = {"iae", "ise", "itae", "emax", "t_emax", "over", "e_final", "settle",
+                                            "tv", "du2", "dumax", "u_lo", "u_hi"};
+
+/* params struct (all fields optional): t0 (0-based first sample, default 0), band_rel (0.02), band_abs (0) */
+static mpct_index_params read_index_params(const mxArray* o, double* device) {
+  mpct_index_params p = {0, 0.02, 0.0};
+  *device = -1.0;
+  if (!o || mxIsEmpty(o)) return p;
+  if (!mxIsStruct(o)) mexErrMsgIdAndTxt("mpct:arg", "params must be a struct (t0, band_rel, band_abs, device)");
+  const double t0 = fscalar(o, "t0", 0.0);
+  *device = fscalar(o, "device", -1.0);
+  if (t0 != floor(t0) || fabs(t0) > 2147483647.0) mexErrMsgIdAndTxt("mpct:arg", "'t0' must be an integer");
+  if (*device != floor(*device) || fabs(*device) > 1e6) mexErrMsgIdAndTxt("mpct:arg", "'device' must be an integer");
+  p.t0 = (int32_t)t0;
+  p.band_rel = fscalar(o, "band_rel", 0.02);
+  p.band_abs = fscalar(o, "band_abs", 0.0);
+  return p;
+}
+
+/* the buffers of the record: output-row fields [S*my] when with_y, input-row fields [S*nu] when with_u */
+static mpct_index_result index_buffers(long S, int my, int nu, int with_y, int with_u) {
+  mpct_index_result r;
+  memset(&r, 0, sizeof r);
+  const size_t ny = (size_t)(S * my + 1), nn = (size_t)(S * nu + 1);
+  if (with_y) {
+    r.iae = (double*)mxCalloc(ny, sizeof(double));
+    r.ise = (double*)mxCalloc(ny, sizeof(double));
+    r.itae = (double*)mxCalloc(ny, sizeof(double));
+    r.emax = (double*)mxCalloc(ny, sizeof(double));
+    r.t_emax = (int32_t*)mxCalloc(ny, sizeof(int32_t));
+    r.over = (double*)mxCalloc(ny, sizeof(double));
+    r.e_final = (double*)mxCalloc(ny, sizeof(double));
+    r.settle = (int32_t*)mxCalloc(ny, sizeof(int32_t));
+  }
+  if (with_u) {
+    r.tv = (double*)mxCalloc(nn, sizeof(double));
+    r.du2 = (double*)mxCalloc(nn, sizeof(double));
+    r.dumax = (double*)mxCalloc(nn, sizeof(double));
+    r.u_lo = (double*)mxCalloc(nn, sizeof(double));
+    r.u_hi = (double*)mxCalloc(nn, sizeof(double));
+  }
+  return r;
+}
+
+static mxArray* out_int_rows(const int32_t* p, long S, int w) {
+  mxArray* a = mxCreateDoubleMatrix((mwSize)S, (mwSize)w, mxREAL);
+  for (long s = 0; s < S; ++s)
+    for (int i = 0; i < w; ++i) mxGetPr(a)[(size_t)i * S + s] = p[s * w + i];
+  return a;
+}
+
+/* the thirteen fields into struct R: S x my / S x nu, [] for a group that was not computed */
+static void set_index_fields(mxArray* R, const mpct_index_result* r, long S, int my, int nu) {
+  const double* dv[13] = {r->iae, r->ise, r->itae, r->emax, NULL, r->over, r->e_final, NULL,
+                          r->tv,  r->du2, r->dumax, r->u_lo, r->u_hi};
+  for (int k = 0; k < 13; ++k) {
+    const int w = k < 8 ? my : nu;
+    const int32_t* iv = k == 4 ? r->t_emax : (k == 7 ? r->settle : NULL);
+    mxArray* a;
+    if (iv) a = out_int_rows(iv, S, w);
+    else if (dv[k]) a = out_rows(dv[k], S, w);
+    else a = mxCreateDoubleMatrix(0, 0, mxREAL);
+    mxSetField(R, 0, kIndexNames[k], a);
+  }
+}
+
+/* the rows, columns and pages of a rows x nit x pages signal array ([] gives 0, 0, 0) */
+static void signal_dims(const mxArray* a, const char* what, int* rows, int* nit, long* pages) {
+  *rows = *nit = 0;
+  *pages = 0;
+  if (!a || mxIsEmpty(a)) return;
+  if (!mxIsDouble(a) || mxIsComplex(a) || mxIsSparse(a) || mxGetNumberOfDimensions(a) > 3)
+    mexErrMsgIdAndTxt("mpct:arg", "'%s' must be a real double rows x nit x pages array", what);
+  const mwSize* d = mxGetDimensions(a);
+  *rows = (int)d[0];
+  *nit = (int)d[1];
+  *pages = mxGetNumberOfDimensions(a) >= 3 ? (long)d[2] : 1;
+}
+
+/* I = mpct_mex('indices', y, u, r [, params]): y my x nit x S, u nu x nit x S, r my x nit x nref (the layouts
+ * 'eval' returns and takes); y and r, or u, may be [] (their fields then come back []).  t0, t_emax and
+ * settle are the library's 0-based sample indices: sample t is column t + 1 */
+static void cmd_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 4 || nrhs > 5) mexErrMsgIdAndTxt("mpct:arg", "usage: I = mpct_mex('indices', y, u, r [, params])");
+  int my, nity, nu, nitu, myr, nitr;
+  long Sy, Su, nref;
+  signal_dims(prhs[1], "y", &my, &nity, &Sy);
+  signal_dims(prhs[2], "u", &nu, &nitu, &Su);
+  signal_dims(prhs[3], "r", &myr, &nitr, &nref);
+  const int with_y = Sy > 0, with_u = Su > 0;
+  if (!with_y && !with_u) mexErrMsgIdAndTxt("mpct:arg", "'y' and 'u' are both empty");
+  if (with_y && (nref < 1 || myr != my || nitr != nity)) mexErrMsgIdAndTxt("mpct:arg", "'r' must be my x nit x nref like 'y'");
+  if (with_y && with_u && (Sy != Su || nity != nitu)) mexErrMsgIdAndTxt("mpct:arg", "'y' and 'u' must agree on nit and S");
+  const long S = with_y ? Sy : Su;
+  const int nit = with_y ? nity : nitu;
+  if (!with_y) nref = 1;
+  if (S > 2147483647L || nref > 2147483647L) mexErrMsgIdAndTxt("mpct:arg", "too many pages");
+  double device;
+  const mpct_index_params p = read_index_params(nrhs > 4 ? prhs[4] : NULL, &device);
+  int pg = 0;
+  double* y = with_y ? signals(prhs[1], my, nit, &pg, "y") : NULL;
+  pg = 0;
+  double* u = with_u ? signals(prhs[2], nu, nit, &pg, "u") : NULL;
+  pg = 0;
+  double* r = with_y ? signals(prhs[3], my, nit, &pg, "r") : NULL;
+  const mpct_index_result res = index_buffers(S, my, nu, with_y, with_u);
+  if (mpct_indices(y, u, r, S, (int32_t)nref, my, nu, nit, &p, (int32_t)device, &res) != MPCT_OK) lib_error("mpct:indices");
+  mxArray* R = mxCreateStructMatrix(1, 1, 13, (const char**)kIndexNames);
+  set_index_fields(R, &res, S, my, nu);
+  plhs[0] = R;
+}
+
+/* I = mpct_mex('eval_indices', h, N2, Nu, delta, lambda, r [, v, params]): the thirteen fields (S x my, S x nu,
+ * simulation s = (c-1)*nref + k) plus J1, j22 (S x my), status and iters (S x 1) of the same launch */
+static void cmd_eval_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 7 || nrhs > 9)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: I = mpct_mex('eval_indices', h, N2, Nu, delta, lambda, r [, v, params])");
+  const batch_args b = read_batch(nrhs, prhs, 2);
+  double device;
+  const mpct_index_params p = read_index_params(nrhs > 8 ? prhs[8] : NULL, &device);
+  mpct_opts o = read_opts(NULL);
+  o.device = (int32_t)device;
+  const long C = b.C, S = C * b.nref;
+  const int my = b.my, nu = b.nu;
+  const mpct_index_result res = index_buffers(S, my, nu, 1, 1);
+  mpct_result br;
+  memset(&br, 0, sizeof br);
+  br.J1 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
+  br.j22 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
+  br.status = (int32_t*)mxCalloc((size_t)(S + 1), sizeof(int32_t));
+  br.qp_iters = (int64_t*)mxCalloc((size_t)(S + 1), sizeof(int64_t));
+  if (mpct_eval_indices(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, &o, &p, &br, &res) != MPCT_OK)
+    lib_error("mpct:eval_indices");
+  const char* names[17];
+  for (int k = 0; k < 13; ++k) names[k] = kIndexNames[k];
+  names[13] = "J1";
+  names[14] = "j22";
+  names[15] = "status";
+  names[16] = "iters";
+  mxArray* R = mxCreateStructMatrix(1, 1, 17, names);
+  set_index_fields(R, &res, S, my, nu);
+  mxSetField(R, 0, "J1", out_rows(br.J1, S, my));
+  mxSetField(R, 0, "j22", out_rows(br.j22, S, my));
+  mxSetField(R, 0, "status", out_int_rows(br.status, S, 1));
+  mxArray* it = mxCreateDoubleMatrix((mwSize)S, 1, mxREAL);
+  for (long k = 0; k < S; ++k) mxGetPr(it)[k] = (double)br.qp_iters[k];
+  mxSetField(R, 0, "iters", it);
+  plhs[0] = R;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (!g_atexit) {
     mexAtExit(destroy_all);
@@ -596,6 +756,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_eval_robust(plhs, nrhs, prhs, 1);
   } else if (!strcmp(cmd, "pareto")) {
     cmd_pareto(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "indices")) {
+    cmd_indices(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "eval_indices")) {
+    cmd_eval_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "instance")) {
     if (nrhs < 2) mexErrMsgIdAndTxt("mpct:arg", "usage: name = mpct_mex('instance', h [, opts])");
     mpct_scenario* s = handle(prhs[1]);

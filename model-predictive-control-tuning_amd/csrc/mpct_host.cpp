@@ -15,6 +15,7 @@
 #include "work_order.h"
 #include "dtc_robust.h"
 #include "pareto.h"
+#include "traj_indices.h"
 
 namespace mpct {
 // defined in gpc_kernel_launch.hip
@@ -64,6 +65,13 @@ struct DevCtx {
   hipEvent_t robust_used = nullptr;
   bool robust_pending = false;
   int ncu = 0;  // compute units (grid of the fused robust kernel)
+  // mpct_eval_indices(_device): the trajectories y | u of one chunk of candidates (grow only, at most
+  // MPCT_INDEX_SCRATCH_BYTES or one candidate's).  index_used is recorded after the last kernel that
+  // reads the buffer; the next call's stream waits for it before rewriting
+  void* dindex = nullptr;
+  size_t dindex_bytes = 0;
+  hipEvent_t index_used = nullptr;
+  bool index_pending = false;
 };
 
 static thread_local std::string g_err;
@@ -138,6 +146,9 @@ static void ctx_release(DevCtx* c) {
   if (c->robust_pending) (void)hipEventSynchronize(c->robust_used);
   if (c->drobust) (void)hipFree(c->drobust);
   if (c->robust_used) (void)hipEventDestroy(c->robust_used);
+  if (c->index_pending) (void)hipEventSynchronize(c->index_used);
+  if (c->dindex) (void)hipFree(c->dindex);
+  if (c->index_used) (void)hipEventDestroy(c->index_used);
   order_release(c->order);
   c->fan.release();
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -994,6 +1005,282 @@ extern "C" int32_t mpct_eval_robust_tail(mpct_scenario* s, int64_t C, const int3
   if (rc) return rc;
   const mpct_robust_result base = out ? *out : mpct_robust_result{};
   return eval_robust_host(s, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, &base, nlev, levels, tail);
+}
+
+// ------------------------------------------------------------------------------------------
+// closed-loop performance indices per simulation (traj_indices.hip; include/mpct.h)
+
+static IndexOut index_out(const mpct_index_result* o) {
+  return IndexOut{o->iae, o->ise, o->itae, o->emax, o->t_emax, o->over, o->e_final, o->settle,
+                  o->tv,  o->du2, o->dumax, o->u_lo, o->u_hi};
+}
+
+// the checks on the parameters and the record from t0 on, in the header's order (shared by the four
+// entries; have_y / have_u: the trajectories behind the fields exist)
+static int index_check_tail(int64_t S, int32_t my, int32_t nu, int32_t nit, const mpct_index_params* p,
+                            const mpct_index_result* out, bool have_y, bool have_u) {
+  if (p->t0 < 0 || p->t0 >= nit) return fail(MPCT_EINVAL, "t0 must be 0 .. nit-1");
+  if (!(p->band_rel >= 0.0 && p->band_rel <= 1.7976931348623157e308 && p->band_abs >= 0.0 &&
+        p->band_abs <= 1.7976931348623157e308))
+    return fail(MPCT_EINVAL, "band_rel and band_abs must be finite and >= 0, not NaN");
+  if (!out) return fail(MPCT_EINVAL, "no output pointer in mpct_index_result");
+  const IndexOut io = index_out(out);
+  if (!io.any_y() && !io.any_u()) return fail(MPCT_EINVAL, "no output pointer in mpct_index_result");
+  if (io.any_y() && (my < 1 || (S > 0 && !have_y)))
+    return fail(MPCT_EINVAL, "an output-row field needs my >= 1 and the trajectories y and r");
+  if (io.any_u() && (nu < 1 || (S > 0 && !have_u)))
+    return fail(MPCT_EINVAL, "an input-row field needs nu >= 1 and the trajectory u");
+  if (S * (int64_t)my > kIndexMaxRows || S * (int64_t)nu > kIndexMaxRows)
+    return fail(MPCT_ERANGE, "S*my or S*nu exceeds MPCT_INDEX_MAX_ROWS");
+  return MPCT_OK;
+}
+
+static int index_check(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my, int32_t nu,
+                       int32_t nit, const mpct_index_params* p, const mpct_index_result* out) {
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (S < 0 || my < 0 || nu < 0 || nit < 1) return fail(MPCT_EINVAL, "bad shape: S < 0, my < 0, nu < 0 or nit < 1");
+  if (nref < 1) return fail(MPCT_EINVAL, "nref < 1");
+  if (S % nref != 0) return fail(MPCT_EINVAL, "S must be a multiple of nref");
+  return index_check_tail(S, my, nu, nit, p, out, y && r, u != nullptr);
+}
+
+static int32_t index_launch(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my,
+                            int32_t nu, int32_t nit, const mpct_index_params* p, const IndexOut& io, hipStream_t stream) {
+  if (S == 0) return MPCT_OK;
+  std::string err;
+  const int rc = launch_traj_indices(y, u, r, S, nref, my, nu, nit, IndexParams{p->t0, p->band_rel, p->band_abs}, io,
+                                     stream, &err);
+  return rc ? fail(MPCT_EDEVICE, err) : MPCT_OK;
+}
+
+extern "C" int32_t mpct_indices_device(const double* y, const double* u, const double* r, int64_t S, int32_t nref,
+                                       int32_t my, int32_t nu, int32_t nit, const mpct_index_params* params,
+                                       const mpct_index_result* out, void* stream) {
+  const int rc = index_check(y, u, r, S, nref, my, nu, nit, params, out);
+  if (rc) return rc;
+  return index_launch(y, u, r, S, nref, my, nu, nit, params, index_out(out), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_indices(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my,
+                                int32_t nu, int32_t nit, const mpct_index_params* params, int32_t device,
+                                const mpct_index_result* out) {
+  int rc = index_check(y, u, r, S, nref, my, nu, nit, params, out);
+  if (rc) return rc;
+  if (S == 0) return MPCT_OK;  // nothing to stage
+  int cur = -1, cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
+    return fail(MPCT_EDEVICE, "no HIP device (mpct_indices needs a GPU)");
+  const int dev = device < 0 ? cur : device;
+  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
+  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
+  // one blob: y | u | r | the thirteen fields, each 256-B aligned; a stream of this call's own
+  const IndexOut ho = index_out(out);
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t yb = ho.any_y() ? (size_t)S * my * nit * 8 : 0, rb = ho.any_y() ? (size_t)nref * my * nit * 8 : 0;
+  const size_t ub = ho.any_u() ? (size_t)S * nu * nit * 8 : 0;
+  const size_t fy = al((size_t)S * my * 8), fu = al((size_t)S * nu * 8);
+  const size_t o_u = al(yb), o_r = o_u + al(ub), o_f = o_r + al(rb);
+  hipStream_t st = nullptr;
+  char* blob = nullptr;
+  rc = MPCT_OK;
+  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
+  } else if (hipMalloc(reinterpret_cast<void**>(&blob), o_f + 8 * fy + 5 * fu + 256) != hipSuccess) {
+    rc = fail(MPCT_ENOMEM, "hipMalloc failed (index staging)");
+  } else {
+    // the device slot of field k (0..7 output rows, 8..12 input rows), null where the caller asks for none
+    auto slot = [&](const void* want, int k) -> char* {
+      return want ? blob + o_f + (k < 8 ? k * fy : 8 * fy + (k - 8) * fu) : nullptr;
+    };
+    const IndexOut dv{(double*)slot(ho.iae, 0),   (double*)slot(ho.ise, 1),     (double*)slot(ho.itae, 2),
+                      (double*)slot(ho.emax, 3),  (int*)slot(ho.t_emax, 4),     (double*)slot(ho.over, 5),
+                      (double*)slot(ho.e_final, 6), (int*)slot(ho.settle, 7),   (double*)slot(ho.tv, 8),
+                      (double*)slot(ho.du2, 9),   (double*)slot(ho.dumax, 10),  (double*)slot(ho.u_lo, 11),
+                      (double*)slot(ho.u_hi, 12)};
+    auto h2d = [&](size_t o, const void* p, size_t b) {
+      return b == 0 || hipMemcpyAsync(blob + o, p, b, hipMemcpyHostToDevice, st) == hipSuccess;
+    };
+    bool ok = h2d(0, y, yb) && h2d(o_u, u, ub) && h2d(o_r, r, rb);
+    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (trajectories)");
+    if (ok) {
+      rc = index_launch(yb ? reinterpret_cast<const double*>(blob) : nullptr,
+                        ub ? reinterpret_cast<const double*>(blob + o_u) : nullptr,
+                        rb ? reinterpret_cast<const double*>(blob + o_r) : nullptr, S, nref, my, nu, nit, params, dv, st);
+      ok = rc == MPCT_OK;
+    }
+    if (ok) {
+      auto d2h = [&](void* dst, const void* src, size_t b) {
+        return !dst || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, st) == hipSuccess;
+      };
+      const size_t dy = (size_t)S * my * 8, iy = (size_t)S * my * 4, du = (size_t)S * nu * 8;
+      ok = d2h(ho.iae, dv.iae, dy) && d2h(ho.ise, dv.ise, dy) && d2h(ho.itae, dv.itae, dy) && d2h(ho.emax, dv.emax, dy) &&
+           d2h(ho.t_emax, dv.t_emax, iy) && d2h(ho.over, dv.over, dy) && d2h(ho.e_final, dv.e_final, dy) &&
+           d2h(ho.settle, dv.settle, iy) && d2h(ho.tv, dv.tv, du) && d2h(ho.du2, dv.du2, du) &&
+           d2h(ho.dumax, dv.dumax, du) && d2h(ho.u_lo, dv.u_lo, du) && d2h(ho.u_hi, dv.u_hi, du);
+      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (index records)");
+    }
+    // this call's stream only, also after an error: the blob is freed below
+    const hipError_t se = hipStreamSynchronize(st);
+    if (rc == MPCT_OK && se != hipSuccess)
+      rc = fail(MPCT_EDEVICE, std::string("mpct_indices failed on the device: ") + hipGetErrorString(se));
+  }
+  if (blob) (void)hipFree(blob);
+  if (st) (void)hipStreamDestroy(st);
+  if (dev != cur) (void)hipSetDevice(cur);
+  return rc;
+}
+
+// the chunk budget of mpct_eval_indices(_device) in bytes of trajectory scratch; 0: MPCT_INDEX_SCRATCH_BYTES.
+// A test / bench hook, not part of include/mpct.h: the tests force ragged chunks at small sizes with it
+static int64_t g_index_budget = 0;
+extern "C" int32_t mpct_internal_index_budget(int64_t bytes) {
+  if (bytes < 0) return fail(MPCT_EINVAL, "budget < 0");
+  g_index_budget = bytes;
+  return MPCT_OK;
+}
+
+// the argument checks of the two scoring entries, in the header's order; nothing here touches a device
+static int check_eval_indices(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* N2, const int32_t* Nu,
+                              const double* delta, const double* lambda, const double* r, const double* v,
+                              const mpct_opts* opts, const mpct_index_params* p, const mpct_result* res,
+                              const mpct_index_result* out) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the index entries are closed-loop only: open_loop must be 0");
+  if (res && (res->y || res->u || res->ys || res->uopt))
+    return fail(MPCT_EINVAL, "the trajectory pointers of res must be NULL: the trajectories stay on the device");
+  const mpct_result any{};
+  const int rc = check_args(s, C, nref, N2, Nu, delta, lambda, r, v, opts, &any);
+  if (rc) return rc;
+  return index_check_tail(C * nref, s->my, s->nu, s->nit, p, out, true, true);
+}
+
+// the context's trajectory scratch, at least `bytes`; orders `stream` after the last index call that
+// used it.  A regrow waits for that work before the old buffer is freed (HostStage::ensure's rule)
+static int index_scratch(DevCtx* cx, size_t bytes, hipStream_t stream, char** out) {
+  if (!cx->index_used && hipEventCreateWithFlags(&cx->index_used, hipEventDisableTiming) != hipSuccess)
+    return fail(MPCT_EDEVICE, "hipEventCreate failed");
+  if (bytes > cx->dindex_bytes) {
+    if (cx->index_pending) (void)hipEventSynchronize(cx->index_used);
+    cx->index_pending = false;
+    if (cx->dindex) {
+      (void)hipStreamSynchronize(stream);
+      (void)hipFree(cx->dindex);
+    }
+    cx->dindex = nullptr;
+    cx->dindex_bytes = 0;
+    if (hipMalloc(&cx->dindex, bytes) != hipSuccess) return fail(MPCT_ENOMEM, "hipMalloc(trajectory scratch) failed");
+    cx->dindex_bytes = bytes;
+  }
+  if (cx->index_pending && hipStreamWaitEvent(stream, cx->index_used, 0) != hipSuccess)
+    return fail(MPCT_EDEVICE, "hipStreamWaitEvent failed");
+  *out = static_cast<char*>(cx->dindex);
+  return MPCT_OK;
+}
+
+// enqueue one batch with device pointers on `stream` (ctx's device is current): chunks of whole
+// candidates through launch_batch into the trajectory scratch, each followed by the index kernel
+static int launch_indices(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2, const int32_t* Nu,
+                          const double* delta, const double* lambda, int32_t nref, const double* r, const double* v,
+                          const mpct_opts* opts, const mpct_index_params* p, const mpct_result* res,
+                          const mpct_index_result* out, hipStream_t stream) {
+  if (C == 0) return MPCT_OK;
+  const int my = s->my, nu = s->nu, nit = s->nit;
+  const size_t per = (size_t)nref * (my + nu) * nit * 8;  // one candidate's trajectories
+  const size_t budget = g_index_budget > 0 ? (size_t)g_index_budget : (size_t)MPCT_INDEX_SCRATCH_BYTES;
+  const int64_t cc = std::min<int64_t>(C, std::max<int64_t>(1, (int64_t)(budget / per)));
+  char* scr = nullptr;
+  int rc = index_scratch(cx, (size_t)cc * per, stream, &scr);
+  if (rc) return rc;
+  mpct_opts o = opts ? *opts : mpct_opts{0, 0, 0, -1, 0.0};
+  o.open_loop = 0;
+  o.want_traj = 1;
+  const IndexOut io = index_out(out);
+  const mpct_result none{};
+  const mpct_result& base = res ? *res : none;
+  for (int64_t c0 = 0; c0 < C && rc == MPCT_OK; c0 += cc) {
+    const int64_t n = std::min(cc, C - c0), s0 = c0 * nref;
+    mpct_result per_chunk{};
+    per_chunk.J1 = base.J1 ? base.J1 + s0 * my : nullptr;
+    per_chunk.j21 = base.j21 ? base.j21 + s0 * my : nullptr;
+    per_chunk.j22 = base.j22 ? base.j22 + s0 * my : nullptr;
+    per_chunk.Jnu = base.Jnu ? base.Jnu + s0 * nu : nullptr;
+    per_chunk.status = base.status ? base.status + s0 : nullptr;
+    per_chunk.qp_iters = base.qp_iters ? base.qp_iters + s0 : nullptr;
+    per_chunk.y = reinterpret_cast<double*>(scr);
+    per_chunk.u = per_chunk.y + (size_t)n * nref * my * nit;
+    rc = launch_batch(s, cx, n, N2 + c0, Nu + c0, delta + c0 * my, lambda + c0 * nu, nref, r, v, &o, &per_chunk, stream);
+    if (rc == MPCT_OK)
+      rc = index_launch(per_chunk.y, per_chunk.u, r, n * nref, nref, my, nu, nit, p, io.from(s0, my, nu), stream);
+  }
+  cx->index_pending = hipEventRecord(cx->index_used, stream) == hipSuccess;
+  return rc;
+}
+
+extern "C" int32_t mpct_eval_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                            const double* delta, const double* lambda, int32_t nref, const double* r,
+                                            const double* v, const mpct_opts* opts, const mpct_index_params* params,
+                                            mpct_result* res, const mpct_index_result* out, void* stream) {
+  int rc = check_eval_indices(s, C, nref, N2, Nu, delta, lambda, r, v, opts, params, res, out);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
+  DevCtx* cx = nullptr;
+  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  if (rc) return rc;
+  return launch_indices(s, cx, C, N2, Nu, delta, lambda, nref, r, v, opts, params, res, out,
+                        static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_eval_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
+                                     const double* lambda, int32_t nref, const double* r, const double* v,
+                                     const mpct_opts* opts, const mpct_index_params* params, mpct_result* res,
+                                     const mpct_index_result* out) {
+  int rc = check_eval_indices(s, C, nref, N2, Nu, delta, lambda, r, v, opts, params, res, out);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
+  DevCtx* cx = nullptr;
+  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  if (rc) return rc;
+  // host buffers in, the records out on the context's own stream, staged as eval_host does
+  const int my = s->my, nu = s->nu;
+  const size_t S = (size_t)(C * nref);
+  HostStage hs(s, cx, C);
+  const size_t o_J1 = hs.slot(S * my * 8), o_j21 = hs.slot(S * my * 8), o_j22 = hs.slot(S * my * 8);
+  const size_t o_Jnu = hs.slot(S * nu * 8), o_st = hs.slot(S * 4), o_it = hs.slot(S * 8);
+  size_t o_f[13];
+  for (int k = 0; k < 13; ++k) o_f[k] = hs.slot(S * (k < 8 ? my : nu) * 8);
+  rc = hs.upload(s, N2, Nu, delta, lambda, nref, r, v);
+  if (rc) return rc;
+  mpct_result dres{};
+  if (res) {
+    dres.J1 = hs.at<double>(o_J1);
+    dres.j21 = hs.at<double>(o_j21);
+    dres.j22 = hs.at<double>(o_j22);
+    dres.Jnu = hs.at<double>(o_Jnu);
+    dres.status = hs.at<int32_t>(o_st);
+    dres.qp_iters = hs.at<int64_t>(o_it);
+  }
+  auto dd = [&](const void* want, int k) { return want ? hs.at<double>(o_f[k]) : nullptr; };
+  auto di = [&](const void* want, int k) { return want ? hs.at<int32_t>(o_f[k]) : nullptr; };
+  const mpct_index_result dout{dd(out->iae, 0),     dd(out->ise, 1),    dd(out->itae, 2), dd(out->emax, 3),
+                               di(out->t_emax, 4),  dd(out->over, 5),   dd(out->e_final, 6), di(out->settle, 7),
+                               dd(out->tv, 8),      dd(out->du2, 9),    dd(out->dumax, 10),  dd(out->u_lo, 11),
+                               dd(out->u_hi, 12)};
+  rc = launch_indices(s, cx, C, hs.N2(), hs.Nu(), hs.delta(), hs.lambda(), nref, hs.r, hs.v, opts, params,
+                      res ? &dres : nullptr, &dout, hs.st);
+  if (rc) return hs.abandon(rc);
+  if (res) {
+    hs.fetch(res->J1, o_J1, S * my * 8);
+    hs.fetch(res->j21, o_j21, S * my * 8);
+    hs.fetch(res->j22, o_j22, S * my * 8);
+    hs.fetch(res->Jnu, o_Jnu, S * nu * 8);
+    hs.fetch(res->status, o_st, S * 4);
+    hs.fetch(res->qp_iters, o_it, S * 8);
+  }
+  void* const dst[13] = {out->iae, out->ise, out->itae, out->emax, out->t_emax, out->over, out->e_final,
+                         out->settle, out->tv, out->du2, out->dumax, out->u_lo, out->u_hi};
+  for (int k = 0; k < 13; ++k) hs.fetch(dst[k], o_f[k], S * (k < 8 ? my : nu) * ((k == 4 || k == 7) ? 4 : 8));
+  return hs.finish();
 }
 
 static int32_t copy_name(const std::string& nm, char* buf, int32_t cap) {

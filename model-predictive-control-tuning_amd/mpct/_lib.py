@@ -90,6 +90,21 @@ class MpctParetoResult(C.Structure):
     _fields_ = [("dom_count", c_int32_p), ("layer", c_int32_p), ("front", c_int32_p), ("n_front", c_int32_p)]
 
 
+class MpctIndexParams(C.Structure):
+    _fields_ = [("t0", C.c_int32), ("band_rel", C.c_double), ("band_abs", C.c_double)]
+
+
+# the fields of mpct_index_result in the struct's order: (name, per output row?, integer?)
+INDEX_FIELDS = [("iae", True, False), ("ise", True, False), ("itae", True, False), ("emax", True, False),
+                ("t_emax", True, True), ("over", True, False), ("e_final", True, False), ("settle", True, True),
+                ("tv", False, False), ("du2", False, False), ("dumax", False, False), ("u_lo", False, False),
+                ("u_hi", False, False)]
+
+
+class MpctIndexResult(C.Structure):
+    _fields_ = [(n, c_int32_p if i else c_double_p) for n, _, i in INDEX_FIELDS]
+
+
 class MpctRobustTail(C.Structure):
     _fields_ = [("quantile", c_double_p), ("cvar", c_double_p), ("q_draw", c_int32_p)]
 
@@ -101,11 +116,13 @@ EXPORTS = [
     "mpct_rank_device", "mpct_eval_robust", "mpct_eval_robust_device", "mpct_robust_instance",
     "mpct_scenario_create_est", "mpct_nmpc_scenario_create_var", "mpct_eval_robust_tail",
     "mpct_eval_robust_tail_device", "mpct_pareto_device", "mpct_pareto",
+    "mpct_indices_device", "mpct_indices", "mpct_eval_indices", "mpct_eval_indices_device",
 ]
 
 ABI_VERSION = 7
 TAIL_MAX_LEVELS, TAIL_MAX_DRAWS = 8, 4096
 PARETO_MAX_OBJ, PARETO_MAX_C, PARETO_MAX_LAYERS = 16, 1048576, 64
+INDEX_MAX_ROWS, INDEX_SCRATCH_BYTES = 2147483647, 268435456
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
 ST_SQP_MAXITER, ST_BOUNDS, ST_NOT_RUN = 32, 64, 128
 NMPC_VANDEVUSSE = 1
@@ -202,6 +219,20 @@ def load():
     lib.mpct_internal_pareto_tuned.restype = C.c_int32
     lib.mpct_internal_pareto_grid.argtypes = [C.c_int64, c_int32_p]
     lib.mpct_internal_pareto_grid.restype = C.c_int32
+    index_args = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                  C.POINTER(MpctIndexParams)]
+    lib.mpct_indices_device.argtypes = index_args + [C.POINTER(MpctIndexResult), C.c_void_p]
+    lib.mpct_indices_device.restype = C.c_int32
+    lib.mpct_indices.argtypes = index_args + [C.c_int32, C.POINTER(MpctIndexResult)]
+    lib.mpct_indices.restype = C.c_int32
+    eval_index_args = batch_args[:10] + [C.POINTER(MpctIndexParams), C.POINTER(MpctResult), C.POINTER(MpctIndexResult)]
+    lib.mpct_eval_indices.argtypes = eval_index_args
+    lib.mpct_eval_indices.restype = C.c_int32
+    lib.mpct_eval_indices_device.argtypes = eval_index_args + [C.c_void_p]
+    lib.mpct_eval_indices_device.restype = C.c_int32
+    # the trajectory-scratch budget of the index entries in bytes (0: the default): a test / bench hook
+    lib.mpct_internal_index_budget.argtypes = [C.c_int64]
+    lib.mpct_internal_index_budget.restype = C.c_int32
     if lib.mpct_abi_version() != ABI_VERSION:
         raise ImportError("libmpct ABI version mismatch")
     _lib = lib

@@ -6,6 +6,10 @@
   closedloop_toolbox  drop-in for closedloop_toolbox.m:1 (one candidate, full trajectories)
   pareto              mpct_pareto: front, domination counts and layers of a [C, k] cost table
   pareto_device       mpct_pareto_device (torch CUDA tensors, enqueued on the current stream)
+  indices             mpct_indices: performance indices (IAE, overshoot, settling, valve travel ..) of trajectories
+  indices_device      mpct_indices_device (torch CUDA tensors, enqueued on the current stream)
+  eval_indices        mpct_eval_indices: score a batch and return only its index records
+  eval_indices_device mpct_eval_indices_device (torch CUDA tensors, enqueued on a stream)
 
 No CPU fallback: every numerical result comes from the HIP kernel.
 """
@@ -562,3 +566,189 @@ def pareto_device(costs, out: dict, max_layers: int = 0):
                                             int(max_layers), C.byref(r), C.c_void_p(stream))
     if rc != 0:
         raise MpctError("mpct_pareto_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+# --------------------------------------------------------------------------------------------
+# closed-loop performance indices per simulation (mpct_indices, mpct_eval_indices; include/mpct.h)
+INDEX_FIELDS = tuple(n for n, _, _ in _lib.INDEX_FIELDS)
+
+
+@dataclass
+class IndexResult:
+    """One array per field of mpct_index_result: the output-row fields (C, nref, my), the input-row fields
+    (C, nref, nu); a field that was not asked for is None.  An invalid row (a non-finite sample in
+    [t0, nit)) holds NaN / -1."""
+    iae: np.ndarray | None = None
+    ise: np.ndarray | None = None
+    itae: np.ndarray | None = None
+    emax: np.ndarray | None = None
+    t_emax: np.ndarray | None = None
+    over: np.ndarray | None = None
+    e_final: np.ndarray | None = None
+    settle: np.ndarray | None = None     # nit = not settled at the last sample
+    tv: np.ndarray | None = None
+    du2: np.ndarray | None = None
+    dumax: np.ndarray | None = None
+    u_lo: np.ndarray | None = None
+    u_hi: np.ndarray | None = None
+    nit: int = 0
+    t0: int = 0
+    batch: EvalResult | None = None      # eval_indices(want_costs=True): J1, j22, status, qp_iters of the same launch
+
+    def costs(self, names, reduce: str = "max") -> np.ndarray:
+        """(C, len(names)) float matrix for ``pareto``: each named field folded over the references and
+        channels by ``reduce`` ('max' or 'sum').  ``e_final`` enters by its magnitude, ``settle`` and
+        ``t_emax`` as samples after t0.  A candidate with an invalid row (NaN / -1) or, for ``settle``, an
+        unsettled one (settle = nit) gets NaN in that column: invalid for ``pareto``, last for ``rank``."""
+        if reduce not in ("max", "sum"):
+            raise ValueError("reduce must be 'max' or 'sum'")
+        cols = []
+        for name in names:
+            if name not in INDEX_FIELDS:
+                raise ValueError("unknown index field %r" % (name,))
+            a = getattr(self, name)
+            if a is None:
+                raise ValueError("this result has no %s" % name)
+            a = np.asarray(a)
+            x = a.reshape(a.shape[0], -1).astype(float)
+            if name in ("settle", "t_emax"):
+                bad = x < 0
+                if name == "settle":
+                    bad |= x >= self.nit
+                x = np.where(bad, np.nan, x - self.t0)
+            elif name == "e_final":
+                x = np.abs(x)
+            # a NaN in the row makes the fold NaN (np.max and np.sum propagate it)
+            cols.append(x.max(axis=1) if reduce == "max" else x.sum(axis=1))
+        return np.stack(cols, axis=1) if cols else np.zeros((0, 0))
+
+
+def _index_fields(fields):
+    fields = INDEX_FIELDS if fields is None else tuple(fields)
+    for f in fields:
+        if f not in INDEX_FIELDS:
+            raise ValueError("unknown index field %r" % (f,))
+    return fields
+
+
+def _index_result(Cn, nref, my, nu, nit, t0, fields):
+    """An IndexResult with the arrays of ``fields`` and the MpctIndexResult that points into them."""
+    res = IndexResult(nit=int(nit), t0=int(t0))
+    r = _lib.MpctIndexResult()
+    for name, is_y, is_int in _lib.INDEX_FIELDS:
+        if name in fields:
+            a = np.zeros((Cn, nref, my if is_y else nu), dtype=np.int32 if is_int else np.float64)
+            setattr(res, name, a)
+            setattr(r, name, _ip(a) if is_int else _dp(a))
+    return res, r
+
+
+def indices(y, u, r, t0=0, band_rel=0.02, band_abs=0.0, fields=None, device=-1) -> IndexResult:
+    """mpct_indices: the performance indices of stored trajectories, reduced on the GPU (host arrays in and
+    out).  ``y`` (S, my, nit), ``u`` (S, nu, nit), ``r`` (nref, my, nit); simulation s reads reference set
+    s % nref.  ``y`` and ``r`` may be None when ``fields`` names no output-row field, ``u`` when it names no
+    input-row field.  The arrays of the result are (S / nref, nref, my) and (S / nref, nref, nu)."""
+    fields = _index_fields(fields)
+    y = None if y is None else np.ascontiguousarray(y, dtype=np.float64)
+    u = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
+    r = None if r is None else np.ascontiguousarray(r, dtype=np.float64)
+    if (y is not None and y.ndim != 3) or (u is not None and u.ndim != 3) or (r is not None and r.ndim != 3):
+        raise ValueError("y, u and r must be 3-d: (S, my, nit), (S, nu, nit), (nref, my, nit)")
+    if y is None and u is None:
+        raise ValueError("y or u is needed")
+    S, nit = (y if y is not None else u).shape[0], (y if y is not None else u).shape[2]
+    my = y.shape[1] if y is not None else (r.shape[1] if r is not None else 0)
+    nu = u.shape[1] if u is not None else 0
+    nref = r.shape[0] if r is not None else 1
+    if (u is not None and u.shape[::2] != (S, nit)) or (r is not None and (r.shape[1] != my or r.shape[2] != nit)):
+        raise ValueError("y, u and r disagree on S, my or nit")
+    if S % nref:
+        raise ValueError("S must be a multiple of nref")
+    res, out = _index_result(S // nref, nref, my, nu, nit, t0, fields)
+    p = _lib.MpctIndexParams(int(t0), float(band_rel), float(band_abs))
+    rc = _lib.load().mpct_indices(y.ctypes.data if y is not None else None, u.ctypes.data if u is not None else None,
+                                  r.ctypes.data if r is not None else None, S, nref, my, nu, nit, C.byref(p), int(device),
+                                  C.byref(out))
+    if rc != 0:
+        raise MpctError("mpct_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return res
+
+
+def _index_struct(out: dict):
+    r = _lib.MpctIndexResult()
+    for name, _, is_int in _lib.INDEX_FIELDS:
+        setattr(r, name, _tptr(out.get(name), _lib.c_int32_p if is_int else _lib.c_double_p))
+    return r
+
+
+def indices_device(y, u, r, out: dict, t0=0, band_rel=0.02, band_abs=0.0):
+    """mpct_indices_device: ``y`` [S, my, nit], ``u`` [S, nu, nit], ``r`` [nref, my, nit] are contiguous float64
+    CUDA (HIP) tensors (None where no field needs them); the records are written into the tensors of ``out``
+    (keys as the fields of IndexResult: float64 / int32, [S, my] or [S, nu]; any may be absent).  Enqueued on
+    the current torch stream of the tensors' device and not synchronised."""
+    import torch
+
+    some = y if y is not None else u
+    for t in (y, u, r):
+        if t is not None and (t.dtype != torch.float64 or t.dim() != 3 or not t.is_contiguous()):
+            raise ValueError("y, u and r must be contiguous float64 tensors with three dimensions")
+    S, nit = some.shape[0], some.shape[2]
+    my = y.shape[1] if y is not None else (r.shape[1] if r is not None else 0)
+    nu = u.shape[1] if u is not None else 0
+    nref = r.shape[0] if r is not None else 1
+    p = _lib.MpctIndexParams(int(t0), float(band_rel), float(band_abs))
+    o = _index_struct(out)
+    stream = torch.cuda.current_stream(some.device).cuda_stream
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(some.device):
+        rc = _lib.load().mpct_indices_device(ptr(y), ptr(u), ptr(r), S, nref, my, nu, nit, C.byref(p), C.byref(o),
+                                             C.c_void_p(stream))
+    if rc != 0:
+        raise MpctError("mpct_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+def eval_indices(sc, N2, Nu, delta, lam, refs, v=None, t0=0, band_rel=0.02, band_abs=0.0, fields=None,
+                 want_costs=False, device=-1, max_qp_iter=0, feas_tol=0.0) -> IndexResult:
+    """mpct_eval_indices: score C candidates against nref reference sets and return only the index records
+    of the closed loops (host arrays in and out); the trajectories stay on the device.  ``want_costs`` adds
+    ``batch``: J1, j22, status and qp_iters of the same launch, as eval_batch returns them."""
+    fields = _index_fields(fields)
+    N2, Nu, delta, lam, refs, Cn, nref, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    res, out = _index_result(Cn, nref, sc.my, sc.nu, sc.nit, t0, fields)
+    br = None
+    if want_costs:
+        res.batch, br = _eval_result(sc, Cn * nref, nref, False, False)
+    p = _lib.MpctIndexParams(int(t0), float(band_rel), float(band_abs))
+    o = _opts(False, False, device, max_qp_iter, feas_tol)
+    rc = sc.lib.mpct_eval_indices(sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data, lam.ctypes.data,
+                                  nref, refs.ctypes.data, vv.ctypes.data if vv is not None else None, C.byref(o),
+                                  C.byref(p), C.byref(br) if br is not None else None, C.byref(out))
+    if rc != 0:
+        raise MpctError("mpct_eval_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return res
+
+
+def eval_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, v=None, t0=0, band_rel=0.02, band_abs=0.0,
+                        device=-1, stream=None):
+    """Device-pointer entry of eval_indices: every argument is a CUDA (HIP) torch tensor; the records are
+    written into the tensors of ``out`` (the keys of indices_device, [C * nref, my] / [C * nref, nu], plus
+    the optional J1, j21, j22, Jnu, status, qp_iters of eval_batch_device).  Enqueued on ``stream`` (torch
+    stream; default: current) and not synchronised."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    br = _lib.MpctResult()
+    br.J1, br.j21 = _tptr(out.get("J1"), _lib.c_double_p), _tptr(out.get("j21"), _lib.c_double_p)
+    br.j22, br.Jnu = _tptr(out.get("j22"), _lib.c_double_p), _tptr(out.get("Jnu"), _lib.c_double_p)
+    br.status, br.qp_iters = _tptr(out.get("status"), _lib.c_int32_p), _tptr(out.get("qp_iters"), _lib.c_int64_p)
+    p = _lib.MpctIndexParams(int(t0), float(band_rel), float(band_abs))
+    o = _opts(False, False, device)
+    io = _index_struct(out)
+    rc = sc.lib.mpct_eval_indices_device(
+        sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+        C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+        C.c_void_p(v.data_ptr()) if v is not None else None, C.byref(o), C.byref(p), C.byref(br), C.byref(io),
+        C.c_void_p(stream.cuda_stream))
+    if rc != 0:
+        raise MpctError("mpct_eval_indices_device failed (%d): %s" % (rc, _lib.last_error()))
