@@ -27,7 +27,9 @@
  *     (mpct_robust_tail, mpct_eval_robust_tail, mpct_eval_robust_tail_device) were added the same way,
  *     and so was the Pareto analysis of a scored grid (mpct_pareto_result, mpct_pareto_device, mpct_pareto),
  *     and the closed-loop performance indices (mpct_index_params, mpct_index_result, mpct_indices_device,
- *     mpct_indices, mpct_eval_indices, mpct_eval_indices_device).
+ *     mpct_indices, mpct_eval_indices, mpct_eval_indices_device), and the statistics of any per-simulation
+ *     table over its draws (mpct_draw_stats_result, mpct_draw_stats_device, mpct_draw_stats,
+ *     mpct_eval_robust_indices, mpct_eval_robust_indices_device).
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -684,6 +686,129 @@ int32_t mpct_eval_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2,
                                  const double* lambda, int32_t nref, const double* r, const double* v,
                                  const mpct_opts* opts, const mpct_index_params* params, mpct_result* res,
                                  const mpct_index_result* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Robust index statistics: per-candidate statistics of any per-simulation table over its draws, on the
+ * device (draw_stats.hip).  mpct_eval_robust reduces the C x D simulations of a plant-mismatch
+ * Monte-Carlo for the tracking cost only and the index entries give one record per simulation; these give
+ * what a robust tuner ranks by -- the worst overshoot over the draws, a quantile of the settling time, the
+ * CVaR of the valve travel -- one number per candidate and channel, as columns for mpct_pareto.
+ *
+ * The primitive.  x is [C][D][m] row-major, the layout of every per-simulation array of this library
+ * (simulation s = c*D + k: J1[s*my+i], iae[s*my+i], tv[s*nu+n]); x_type is MPCT_STAT_F64 (double) or
+ * MPCT_STAT_I32 (int32, converted to double exactly; a negative value is "no value", the -1 of an invalid
+ * index row).  alive is [C][D] or NULL (every draw alive).  Draw k SURVIVES in column (c, i) when alive is
+ * NULL or alive[c*D+k] != 0, and the value is finite (F64) or >= 0 (I32).  The columns are independent;
+ * n is the column's number of survivors.
+ *
+ * Per column, element c*m + i of each array:
+ *   n         the survivor count
+ *   mean      one accumulator from 0.0 over the surviving draws in ascending k, divided by (double)n
+ *   lo, lo_draw   the smallest surviving value and the lowest draw index that holds it
+ *   hi, hi_draw   the largest surviving value and the lowest draw index that holds it
+ *             lo and hi carry the bits of the value at lo_draw / hi_draw; -0.0 and +0.0 compare equal
+ * Per column and level j, element (c*m + i)*nlev + j: quantile, cvar, q_draw, defined as in
+ * mpct_eval_robust_tail on the column's survivors: ordered by value ascending and, among equal values, by
+ * draw index DESCENDING; m_j = ceil(a_j * (double)n) clamped to [1, n]; quantile the value of rank m_j
+ * (type 1, no interpolation), q_draw its draw, cvar = (sum of ranks m_j .. n) / (n - m_j + 1) with one
+ * accumulator from 0.0 in ascending rank order.
+ * n = 0: NaN in the doubles, -1 in the draws.  At level 1.0 quantile = cvar = hi and q_draw = hi_draw;
+ * duplicate levels give equal columns and the levels need not be sorted.  A repeated call is bitwise
+ * identical and a column's record depends neither on C nor on its place in the table.
+ * Any pointer of mpct_draw_stats_result may be NULL, not all of them.  levels is a HOST pointer in both entries;
+ * nlev may be 0.
+ *
+ * Argument errors, in this order and before any device is touched:
+ *   MPCT_EINVAL  C < 0, D < 1 or m < 1
+ *   MPCT_EINVAL  x_type neither MPCT_STAT_F64 nor MPCT_STAT_I32
+ *   MPCT_EINVAL  nlev < 0 or nlev > MPCT_TAIL_MAX_LEVELS
+ *   MPCT_EINVAL  nlev > 0 with levels NULL
+ *   MPCT_EINVAL  a level that is NaN, <= 0 or > 1
+ *   MPCT_EINVAL  out NULL, or all nine of its pointers NULL
+ *   MPCT_EINVAL  a quantile, cvar or q_draw pointer with nlev = 0
+ *   MPCT_EINVAL  x NULL with C > 0
+ *   MPCT_ERANGE  D > MPCT_TAIL_MAX_DRAWS (12 B of LDS per draw)
+ *   MPCT_ERANGE  C*m > MPCT_INDEX_MAX_ROWS
+ * C = 0 is MPCT_OK and writes nothing. */
+#define MPCT_STAT_F64 0
+#define MPCT_STAT_I32 1
+typedef struct mpct_draw_stats_result {
+  int32_t* n;        /* [C*m] */
+  double* mean;      /* [C*m] */
+  double* lo;        /* [C*m] */
+  int32_t* lo_draw;  /* [C*m] */
+  double* hi;        /* [C*m] */
+  int32_t* hi_draw;  /* [C*m] */
+  double* quantile;  /* [C*m*nlev] */
+  double* cvar;      /* [C*m*nlev] */
+  int32_t* q_draw;   /* [C*m*nlev] */
+} mpct_draw_stats_result;
+
+/* All pointers DEVICE pointers (levels excepted); enqueued on `stream` (NULL = default stream) and NOT
+ * synchronised.  Needs no scenario and no scratch: one kernel launch. */
+int32_t mpct_draw_stats_device(const void* x, int32_t x_type, const int32_t* alive, int64_t C, int32_t D, int32_t m,
+                               int32_t nlev, const double* levels, const mpct_draw_stats_result* out, void* stream);
+
+/* Host pointers (MATLAB and C callers).  device: HIP ordinal, -1 = the current device (an ordinal out of range
+ * is MPCT_EINVAL).  Stages on a stream of its own and waits for that stream only; the calling thread's current
+ * device is unchanged on return.  Without a device: MPCT_EDEVICE with a message. */
+int32_t mpct_draw_stats(const void* x, int32_t x_type, const int32_t* alive, int64_t C, int32_t D, int32_t m,
+                        int32_t nlev, const double* levels, int32_t device, const mpct_draw_stats_result* out);
+
+/* Score C candidates x D = nref draws and return, per candidate, the statistics over the draws of the
+ * selected performance indices (host pointers; arguments as mpct_eval_indices and mpct_eval_robust).
+ *   fields   HOST pointer to nsel distinct field ids, MPCT_IX_IAE .. MPCT_IX_U_HI in the member order of
+ *            mpct_index_result.  The selected fields lie side by side in selection order: W = sum of their
+ *            widths (my for an output-row field, nu for an input-row field), and every array of `out` is
+ *            [C][W] or [C][W][nlev] -- out->hi is directly a cost table for mpct_pareto_device.  t_emax and
+ *            settle enter as MPCT_STAT_I32, the others as MPCT_STAT_F64.
+ *   levels   HOST pointer, nlev may be 0 (then out's quantile, cvar and q_draw must be NULL).
+ *   base     optional: mean and worst of J1, n_failed, worst_draw and status exactly as mpct_eval_robust
+ *            defines them, from the same launch.  base->J1 must be NULL: the sample lives per chunk.
+ * Per chunk of whole candidates (the chunking of mpct_eval_indices, MPCT_INDEX_SCRATCH_BYTES of trajectory
+ * scratch) the closed loops run with their trajectories, J1 and status written to scratch of the scenario's
+ * context; traj_indices_kernel reduces the selected fields to per-simulation records there; a classify kernel
+ * writes alive[c][k] by the rule of mpct_eval_robust (status 0, J = sum_i J1_i finite, summed over
+ * i = 0 .. my-1 in that order, J <= j_bound with 0 = 1e100; a candidate carrying MPCT_ST_SKIPPED or
+ * MPCT_ST_BADHORIZON on any draw has no live draw); and the primitive above runs once per selected field.
+ * A draw also drops out of a column whose record is invalid (NaN / -1).  Every record is bitwise independent
+ * of the chunk size.
+ * Errors, in this order and before any device is touched.  MPCT_EINVAL: s NULL; params NULL; open_loop
+ * set; nsel < 1 or > 13, fields NULL, an id out of range or repeated; nref < 1; a negative or NaN j_bound;
+ * nlev < 0 or > MPCT_TAIL_MAX_LEVELS, nlev > 0 with levels NULL, a level that is NaN, <= 0 or > 1; no result
+ * pointer at all in `base` and `out`, base->J1 set, or a quantile / cvar / q_draw pointer with nlev = 0; then
+ * everything mpct_eval_batch rejects; then t0 or the bands as in mpct_indices_device.  Then MPCT_ERANGE for
+ * nref > MPCT_TAIL_MAX_DRAWS, and for C*nref*my or C*nref*nu > MPCT_INDEX_MAX_ROWS.
+ * C = 0 is MPCT_OK and writes nothing.  Without a device: MPCT_EDEVICE with a message. */
+#define MPCT_IX_IAE 0
+#define MPCT_IX_ISE 1
+#define MPCT_IX_ITAE 2
+#define MPCT_IX_EMAX 3
+#define MPCT_IX_T_EMAX 4
+#define MPCT_IX_OVER 5
+#define MPCT_IX_E_FINAL 6
+#define MPCT_IX_SETTLE 7
+#define MPCT_IX_TV 8
+#define MPCT_IX_DU2 9
+#define MPCT_IX_DUMAX 10
+#define MPCT_IX_U_LO 11
+#define MPCT_IX_U_HI 12
+int32_t mpct_eval_robust_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
+                                 const double* lambda, int32_t nref, const double* r, const double* v, double j_bound,
+                                 const mpct_opts* opts, const mpct_index_params* params, int32_t nsel,
+                                 const int32_t* fields, int32_t nlev, const double* levels, mpct_robust_result* base,
+                                 const mpct_draw_stats_result* out);
+
+/* Same, all pointers DEVICE pointers except fields and levels, enqueued on `stream` (NULL = default stream)
+ * and NOT synchronised: the contract of mpct_eval_indices_device, whose scratch and stream-ordering rule it
+ * shares (grow-only; a regrow waits for the work on the old buffer; a call on another stream waits for an
+ * event recorded after the previous call's last kernel). */
+int32_t mpct_eval_robust_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                        const double* delta, const double* lambda, int32_t nref, const double* r,
+                                        const double* v, double j_bound, const mpct_opts* opts,
+                                        const mpct_index_params* params, int32_t nsel, const int32_t* fields,
+                                        int32_t nlev, const double* levels, mpct_robust_result* base,
+                                        const mpct_draw_stats_result* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,25 @@
  *   I = mpct_mex('eval_indices', h, N2, Nu, delta, lambda, r, v, params)
  *                                                    score the batch and return only its index records
  *                                                    (mpct_eval_indices), plus J1, j22, status, iters
+ *   T = mpct_mex('draw_stats', x, alive, levels, device)
+ *                                                    statistics of a table over its draw axis (mpct_draw_stats; no
+ *                                                    scenario needed): x is D x m x C (page c is candidate c's D draws
+ *                                                    of m channels; an S x m field F of 'eval_indices' with D draws is
+ *                                                    permute(reshape(F, D, C, m), [1 3 2])); an int32 x enters as
+ *                                                    MPCT_STAT_I32, any other class as double.  alive D x C or [],
+ *                                                    levels 0 .. 8 values in (0, 1] or [], device optional.  Struct
+ *                                                    with n, mean, lo, lo_draw, hi, hi_draw (C x m) and levels
+ *                                                    (1 x nlev), quantile, cvar, q_draw (C x m x nlev; [] without
+ *                                                    levels); the draws are the library's 0-based k, -1: none
+ *   T = mpct_mex('eval_robust_indices', h, N2, Nu, delta, lambda, r, v, params)
+ *                                                    statistics of the performance indices over the D pages of r
+ *                                                    (mpct_eval_robust_indices).  params (optional struct): fields
+ *                                                    (vector of 0-based MPCT_IX_* ids, default all thirteen), levels,
+ *                                                    j_bound, t0, band_rel, band_abs, device.  Struct with field and
+ *                                                    channel (1 x W: the 0-based field id and the 1-based channel of
+ *                                                    each column), the arrays of 'draw_stats' as C x W (x nlev), and
+ *                                                    the robust record of J1: J1_mean, J1_worst (C x my), n_failed,
+ *                                                    worst_draw, status (C x 1)
  *   mpct_mex('destroy', h)
  *
  * MATLAB layouts (column-major, what the callers already hold):
@@ -730,6 +749,181 @@ static void cmd_eval_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = R;
 }
 
+/* ---- statistics over the draws (mpct_draw_stats, mpct_eval_robust_indices; include/mpct.h) */
+static const char* const kStatNames[10] = {"n", "mean", "lo", "lo_draw", "hi", "hi_draw", "levels", "quantile", "cvar", "q_draw"};
+
+/* levels: [] or absent gives 0; the count is checked before anything is sized by it, the values are the library's */
+static double* read_levels(const mxArray* a, long* nlev) {
+  *nlev = 0;
+  if (!a || mxIsEmpty(a)) return NULL;
+  double* lv = doubles(a, -1, "levels");
+  *nlev = (long)mxGetNumberOfElements(a);
+  if (*nlev > MPCT_TAIL_MAX_LEVELS)
+    mexErrMsgIdAndTxt("mpct:arg", "'levels' must hold 0 .. %d values (has %ld)", MPCT_TAIL_MAX_LEVELS, *nlev);
+  return lv;
+}
+
+/* the nine buffers of a record of `cols` columns */
+static mpct_draw_stats_result stats_buffers(long cols, long nlev) {
+  mpct_draw_stats_result r;
+  memset(&r, 0, sizeof r);
+  const size_t n = (size_t)(cols + 1), nl = (size_t)(cols * nlev + 1);
+  r.n = (int32_t*)mxCalloc(n, sizeof(int32_t));
+  r.mean = (double*)mxCalloc(n, sizeof(double));
+  r.lo = (double*)mxCalloc(n, sizeof(double));
+  r.lo_draw = (int32_t*)mxCalloc(n, sizeof(int32_t));
+  r.hi = (double*)mxCalloc(n, sizeof(double));
+  r.hi_draw = (int32_t*)mxCalloc(n, sizeof(int32_t));
+  if (nlev > 0) {
+    r.quantile = (double*)mxCalloc(nl, sizeof(double));
+    r.cvar = (double*)mxCalloc(nl, sizeof(double));
+    r.q_draw = (int32_t*)mxCalloc(nl, sizeof(int32_t));
+  }
+  return r;
+}
+
+/* C [C][w][nlev] of doubles (dp) or int32 (ip) -> MATLAB C x w x nlev; [] without levels */
+static mxArray* out_levels(const double* dp, const int32_t* ip, long C, int w, long nlev) {
+  if (nlev < 1) return mxCreateDoubleMatrix(0, 0, mxREAL);
+  mwSize dims[3] = {(mwSize)C, (mwSize)w, (mwSize)nlev};
+  mxArray* a = mxCreateNumericArray(3, dims, mxDOUBLE_CLASS, mxREAL);
+  double* q = mxGetPr(a);
+  for (long c = 0; c < C; ++c)
+    for (int i = 0; i < w; ++i)
+      for (long j = 0; j < nlev; ++j) {
+        const size_t e = ((size_t)c * w + i) * nlev + j;
+        q[((size_t)j * w + i) * C + c] = dp ? dp[e] : (double)ip[e];
+      }
+  return a;
+}
+
+/* the ten statistics fields into struct T: C x w (x nlev) */
+static void set_stats_fields(mxArray* T, const mpct_draw_stats_result* r, const double* levels, long nlev, long C, int w) {
+  mxSetField(T, 0, "n", out_int_rows(r->n, C, w));
+  mxSetField(T, 0, "mean", out_rows(r->mean, C, w));
+  mxSetField(T, 0, "lo", out_rows(r->lo, C, w));
+  mxSetField(T, 0, "lo_draw", out_int_rows(r->lo_draw, C, w));
+  mxSetField(T, 0, "hi", out_rows(r->hi, C, w));
+  mxSetField(T, 0, "hi_draw", out_int_rows(r->hi_draw, C, w));
+  mxSetField(T, 0, "levels", nlev > 0 ? out_rows(levels, 1, (int)nlev) : mxCreateDoubleMatrix(0, 0, mxREAL));
+  mxSetField(T, 0, "quantile", out_levels(r->quantile, NULL, C, w, nlev));
+  mxSetField(T, 0, "cvar", out_levels(r->cvar, NULL, C, w, nlev));
+  mxSetField(T, 0, "q_draw", out_levels(NULL, r->q_draw, C, w, nlev));
+}
+
+/* T = mpct_mex('draw_stats', x [, alive, levels, device]): x D x m x C column-major, transposed here into the
+ * library's [C][D][m]; the shapes are the library's to judge beyond what sizes a buffer here */
+static void cmd_draw_stats(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 2 || nrhs > 5) mexErrMsgIdAndTxt("mpct:arg", "usage: T = mpct_mex('draw_stats', x [, alive, levels, device])");
+  const mxArray* a = prhs[1];
+  if (!a || !mxIsNumeric(a) || mxIsComplex(a) || mxIsSparse(a) || mxGetNumberOfDimensions(a) > 3)
+    mexErrMsgIdAndTxt("mpct:arg", "'x' must be a real full D x m x C array");
+  const mwSize* d = mxGetDimensions(a);
+  const long D = (long)d[0], m = (long)d[1];
+  const long C = mxGetNumberOfElements(a) == 0 ? 0 : (mxGetNumberOfDimensions(a) >= 3 ? (long)d[2] : 1);
+  if (D > 2147483647L || m > 2147483647L) mexErrMsgIdAndTxt("mpct:arg", "'x' is too large");
+  const mxArray* al = nrhs > 2 && !mxIsEmpty(prhs[2]) ? prhs[2] : NULL;
+  if (al && ((long)mxGetM(al) != D || (long)mxGetN(al) != C)) mexErrMsgIdAndTxt("mpct:arg", "'alive' must be D x C like 'x'");
+  long nlev;
+  double* levels = read_levels(nrhs > 3 ? prhs[3] : NULL, &nlev);
+  const double dv = (nrhs > 4 && !mxIsEmpty(prhs[4])) ? scalar(prhs[4], "device") : -1.0;
+  if (dv != floor(dv) || fabs(dv) > 1e6) mexErrMsgIdAndTxt("mpct:arg", "'device' must be an integer");
+  const int is_int = mxGetClassID(a) == mxINT32_CLASS;
+  const size_t total = (size_t)C * D * m;
+  double* src = doubles(a, -1, "x");
+  void* x = mxMalloc((total + 1) * (is_int ? sizeof(int32_t) : sizeof(double)));
+  for (long c = 0; c < C; ++c)
+    for (long k = 0; k < D; ++k)
+      for (long i = 0; i < m; ++i) {
+        const double v = src[((size_t)c * m + i) * D + k];
+        const size_t e = ((size_t)c * D + k) * m + i;
+        if (is_int) ((int32_t*)x)[e] = (int32_t)v;
+        else ((double*)x)[e] = v;
+      }
+  int32_t* alive = NULL;
+  if (al) { /* D x C column-major is [C][D] row-major already */
+    double* av = doubles(al, C * D, "alive");
+    alive = (int32_t*)mxMalloc(((size_t)(C * D) + 1) * sizeof(int32_t));
+    for (long e = 0; e < C * D; ++e) alive[e] = av[e] != 0.0;
+  }
+  const mpct_draw_stats_result res = stats_buffers(C * m, nlev);
+  if (mpct_draw_stats(x, is_int ? MPCT_STAT_I32 : MPCT_STAT_F64, alive, C, (int32_t)D, (int32_t)m, (int32_t)nlev, levels,
+                      (int32_t)dv, &res) != MPCT_OK)
+    lib_error("mpct:draw_stats");
+  mxArray* T = mxCreateStructMatrix(1, 1, 10, (const char**)kStatNames);
+  set_stats_fields(T, &res, levels, nlev, C, (int)m);
+  plhs[0] = T;
+}
+
+/* T = mpct_mex('eval_robust_indices', h, N2, Nu, delta, lambda, r [, v, params]) */
+static void cmd_eval_robust_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 7 || nrhs > 9)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: T = mpct_mex('eval_robust_indices', h, N2, Nu, delta, lambda, r [, v, params])");
+  const mxArray* po = nrhs > 8 && !mxIsEmpty(prhs[8]) ? prhs[8] : NULL;
+  double device;
+  const mpct_index_params p = read_index_params(po, &device);
+  int32_t all[13], *fields = all;
+  long nsel = 13, nlev = 0;
+  double* levels = NULL;
+  double j_bound = 0.0;
+  for (int k = 0; k < 13; ++k) all[k] = k;
+  if (po) {
+    const mxArray* f = mxGetField(po, 0, "fields");
+    if (f && !mxIsEmpty(f)) { /* the count sizes the column table below; the ids are the library's to judge .. */
+      nsel = (long)mxGetNumberOfElements(f);
+      if (nsel > 13) mexErrMsgIdAndTxt("mpct:arg", "'fields' must hold 1 .. 13 ids (has %ld)", nsel);
+      fields = ints(f, -1, "fields");
+    }
+    levels = read_levels(mxGetField(po, 0, "levels"), &nlev);
+    j_bound = fscalar(po, "j_bound", 0.0);
+  }
+  const batch_args b = read_batch(nrhs, prhs, 2);
+  mpct_opts o = read_opts(NULL);
+  o.device = (int32_t)device;
+  const long C = b.C;
+  const int my = b.my, nu = b.nu;
+  int W = 0; /* .. but an id out of range must not size anything: it counts as one column */
+  for (long q = 0; q < nsel; ++q) W += (fields[q] >= 0 && fields[q] <= 12) ? (fields[q] < 8 ? my : nu) : 1;
+  const mpct_draw_stats_result res = stats_buffers(C * W, nlev);
+  mpct_robust_result base;
+  memset(&base, 0, sizeof base);
+  base.mean = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
+  base.worst = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
+  base.n_failed = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  base.worst_draw = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  base.status = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  if (mpct_eval_robust_indices(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, &p, (int32_t)nsel, fields,
+                               (int32_t)nlev, levels, &base, &res) != MPCT_OK)
+    lib_error("mpct:eval_robust_indices");
+  const char* names[17];
+  names[0] = "field";
+  names[1] = "channel";
+  for (int k = 0; k < 10; ++k) names[2 + k] = kStatNames[k];
+  names[12] = "J1_mean";
+  names[13] = "J1_worst";
+  names[14] = "n_failed";
+  names[15] = "worst_draw";
+  names[16] = "status";
+  mxArray* T = mxCreateStructMatrix(1, 1, 17, names);
+  mxArray* fa = mxCreateDoubleMatrix(1, (mwSize)W, mxREAL);
+  mxArray* ca = mxCreateDoubleMatrix(1, (mwSize)W, mxREAL);
+  int col = 0;
+  for (long q = 0; q < nsel; ++q)
+    for (int i = 0; i < (fields[q] < 8 ? my : nu); ++i, ++col) {
+      mxGetPr(fa)[col] = fields[q];
+      mxGetPr(ca)[col] = i + 1;
+    }
+  mxSetField(T, 0, "field", fa);
+  mxSetField(T, 0, "channel", ca);
+  set_stats_fields(T, &res, levels, nlev, C, W);
+  mxSetField(T, 0, "J1_mean", out_rows(base.mean, C, my));
+  mxSetField(T, 0, "J1_worst", out_rows(base.worst, C, my));
+  mxSetField(T, 0, "n_failed", out_int_rows(base.n_failed, C, 1));
+  mxSetField(T, 0, "worst_draw", out_int_rows(base.worst_draw, C, 1));
+  mxSetField(T, 0, "status", out_int_rows(base.status, C, 1));
+  plhs[0] = T;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (!g_atexit) {
     mexAtExit(destroy_all);
@@ -760,6 +954,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "eval_indices")) {
     cmd_eval_indices(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "draw_stats")) {
+    cmd_draw_stats(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "eval_robust_indices")) {
+    cmd_eval_robust_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "instance")) {
     if (nrhs < 2) mexErrMsgIdAndTxt("mpct:arg", "usage: name = mpct_mex('instance', h [, opts])");
     mpct_scenario* s = handle(prhs[1]);

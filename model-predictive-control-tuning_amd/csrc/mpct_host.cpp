@@ -16,6 +16,7 @@
 #include "dtc_robust.h"
 #include "pareto.h"
 #include "traj_indices.h"
+#include "draw_stats.h"
 
 namespace mpct {
 // defined in gpc_kernel_launch.hip
@@ -1017,12 +1018,18 @@ static IndexOut index_out(const mpct_index_result* o) {
 
 // the checks on the parameters and the record from t0 on, in the header's order (shared by the four
 // entries; have_y / have_u: the trajectories behind the fields exist)
-static int index_check_tail(int64_t S, int32_t my, int32_t nu, int32_t nit, const mpct_index_params* p,
-                            const mpct_index_result* out, bool have_y, bool have_u) {
+static int index_check_params(int32_t nit, const mpct_index_params* p) {
   if (p->t0 < 0 || p->t0 >= nit) return fail(MPCT_EINVAL, "t0 must be 0 .. nit-1");
   if (!(p->band_rel >= 0.0 && p->band_rel <= 1.7976931348623157e308 && p->band_abs >= 0.0 &&
         p->band_abs <= 1.7976931348623157e308))
     return fail(MPCT_EINVAL, "band_rel and band_abs must be finite and >= 0, not NaN");
+  return MPCT_OK;
+}
+
+static int index_check_tail(int64_t S, int32_t my, int32_t nu, int32_t nit, const mpct_index_params* p,
+                            const mpct_index_result* out, bool have_y, bool have_u) {
+  const int rc = index_check_params(nit, p);
+  if (rc) return rc;
   if (!out) return fail(MPCT_EINVAL, "no output pointer in mpct_index_result");
   const IndexOut io = index_out(out);
   if (!io.any_y() && !io.any_u()) return fail(MPCT_EINVAL, "no output pointer in mpct_index_result");
@@ -1280,6 +1287,308 @@ extern "C" int32_t mpct_eval_indices(mpct_scenario* s, int64_t C, const int32_t*
   void* const dst[13] = {out->iae, out->ise, out->itae, out->emax, out->t_emax, out->over, out->e_final,
                          out->settle, out->tv, out->du2, out->dumax, out->u_lo, out->u_hi};
   for (int k = 0; k < 13; ++k) hs.fetch(dst[k], o_f[k], S * (k < 8 ? my : nu) * ((k == 4 || k == 7) ? 4 : 8));
+  return hs.finish();
+}
+
+// ------------------------------------------------------------------------------------------
+// statistics of a table over its draw axis, and of the performance indices over the plant draws
+// (draw_stats.hip; include/mpct.h)
+
+static DrawStatsOut stats_out(const mpct_draw_stats_result* o) {
+  return DrawStatsOut{o->n, o->mean, o->lo, o->lo_draw, o->hi, o->hi_draw, o->quantile, o->cvar, o->q_draw};
+}
+
+// the level checks both entries share, in the header's order
+static int stats_check_levels(int32_t nlev, const double* levels) {
+  if (nlev < 0 || nlev > MPCT_TAIL_MAX_LEVELS) return fail(MPCT_EINVAL, "nlev must be 0 .. MPCT_TAIL_MAX_LEVELS (8)");
+  if (nlev > 0 && !levels) return fail(MPCT_EINVAL, "null levels");
+  for (int j = 0; j < nlev; ++j)
+    if (!(levels[j] > 0.0 && levels[j] <= 1.0)) return fail(MPCT_EINVAL, "every level must lie in (0, 1], not NaN");
+  return MPCT_OK;
+}
+
+// the argument checks of the primitive's two entries, in the header's order; nothing here touches a device
+static int stats_check(const void* x, int32_t x_type, int64_t C, int32_t D, int32_t m, int32_t nlev, const double* levels,
+                       const mpct_draw_stats_result* out) {
+  if (C < 0 || D < 1 || m < 1) return fail(MPCT_EINVAL, "bad shape: C < 0, D < 1 or m < 1");
+  if (x_type != MPCT_STAT_F64 && x_type != MPCT_STAT_I32) return fail(MPCT_EINVAL, "x_type must be MPCT_STAT_F64 or MPCT_STAT_I32");
+  const int rc = stats_check_levels(nlev, levels);
+  if (rc) return rc;
+  if (!out || !stats_out(out).any()) return fail(MPCT_EINVAL, "no output pointer in mpct_draw_stats_result");
+  if (nlev == 0 && stats_out(out).any_level()) return fail(MPCT_EINVAL, "quantile, cvar and q_draw need nlev >= 1");
+  if (C > 0 && !x) return fail(MPCT_EINVAL, "x is NULL");
+  if (D > MPCT_TAIL_MAX_DRAWS) return fail(MPCT_ERANGE, "D > MPCT_TAIL_MAX_DRAWS (4096): the kernel's LDS holds no more draws");
+  if (C * (int64_t)m > MPCT_INDEX_MAX_ROWS) return fail(MPCT_ERANGE, "C*m exceeds MPCT_INDEX_MAX_ROWS");
+  return MPCT_OK;
+}
+
+// the largest grid of draw_stats_kernel in workgroups; 0: kStatGridCap.  A test hook, not part of
+// include/mpct.h: the tests force the workgroups to stride at small sizes with it
+static int32_t g_stats_grid = 0;
+extern "C" int32_t mpct_internal_draw_stats_grid(int32_t groups) {
+  if (groups < 0) return fail(MPCT_EINVAL, "groups < 0");
+  g_stats_grid = groups;
+  return MPCT_OK;
+}
+
+static int32_t stats_launch(const void* x, int32_t x_type, const int32_t* alive, int64_t C, int32_t D, int32_t m,
+                            int32_t nlev, const double* levels, const DrawStatsOut& out, int ldo, int off,
+                            hipStream_t stream) {
+  std::string err;
+  const int rc = launch_draw_stats(x, x_type, alive, C, D, m, nlev, levels, out, ldo, off, g_stats_grid, stream, &err);
+  return rc ? fail(MPCT_EDEVICE, err) : MPCT_OK;
+}
+
+extern "C" int32_t mpct_draw_stats_device(const void* x, int32_t x_type, const int32_t* alive, int64_t C, int32_t D,
+                                          int32_t m, int32_t nlev, const double* levels,
+                                          const mpct_draw_stats_result* out, void* stream) {
+  const int rc = stats_check(x, x_type, C, D, m, nlev, levels, out);
+  if (rc) return rc;
+  return stats_launch(x, x_type, alive, C, D, m, nlev, levels, stats_out(out), m, 0, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_draw_stats(const void* x, int32_t x_type, const int32_t* alive, int64_t C, int32_t D, int32_t m,
+                                   int32_t nlev, const double* levels, int32_t device, const mpct_draw_stats_result* out) {
+  int rc = stats_check(x, x_type, C, D, m, nlev, levels, out);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage
+  int cur = -1, cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
+    return fail(MPCT_EDEVICE, "no HIP device (mpct_draw_stats needs a GPU)");
+  const int dev = device < 0 ? cur : device;
+  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
+  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
+  // one blob: x | alive | the nine fields, each 256-B aligned; a stream of this call's own
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t cols = (size_t)C * m, nl = (size_t)std::max(nlev, 1);
+  const size_t xb = (size_t)C * D * m * (x_type == MPCT_STAT_I32 ? 4 : 8), ab = alive ? (size_t)C * D * 4 : 0;
+  const size_t fb = al(cols * nl * 8);  // one field's slot, the largest of them
+  const size_t o_a = al(xb), o_f = o_a + al(ab);
+  hipStream_t st = nullptr;
+  char* blob = nullptr;
+  rc = MPCT_OK;
+  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
+  } else if (hipMalloc(reinterpret_cast<void**>(&blob), o_f + 9 * fb + 256) != hipSuccess) {
+    rc = fail(MPCT_ENOMEM, "hipMalloc failed (draw statistics staging)");
+  } else {
+    auto slot = [&](const void* want, int k) -> char* { return want ? blob + o_f + k * fb : nullptr; };
+    const DrawStatsOut dv{(int32_t*)slot(out->n, 0),       (double*)slot(out->mean, 1), (double*)slot(out->lo, 2),
+                          (int32_t*)slot(out->lo_draw, 3), (double*)slot(out->hi, 4),   (int32_t*)slot(out->hi_draw, 5),
+                          (double*)slot(out->quantile, 6), (double*)slot(out->cvar, 7), (int32_t*)slot(out->q_draw, 8)};
+    bool ok = hipMemcpyAsync(blob, x, xb, hipMemcpyHostToDevice, st) == hipSuccess &&
+              (!ab || hipMemcpyAsync(blob + o_a, alive, ab, hipMemcpyHostToDevice, st) == hipSuccess);
+    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (table)");
+    if (ok) {
+      rc = stats_launch(blob, x_type, ab ? reinterpret_cast<const int32_t*>(blob + o_a) : nullptr, C, D, m, nlev, levels,
+                        dv, m, 0, st);
+      ok = rc == MPCT_OK;
+    }
+    if (ok) {
+      auto d2h = [&](void* dst, const void* src, size_t b) {
+        return !dst || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, st) == hipSuccess;
+      };
+      ok = d2h(out->n, dv.n, cols * 4) && d2h(out->mean, dv.mean, cols * 8) && d2h(out->lo, dv.lo, cols * 8) &&
+           d2h(out->lo_draw, dv.lo_draw, cols * 4) && d2h(out->hi, dv.hi, cols * 8) &&
+           d2h(out->hi_draw, dv.hi_draw, cols * 4) && d2h(out->quantile, dv.quantile, cols * nl * 8) &&
+           d2h(out->cvar, dv.cvar, cols * nl * 8) && d2h(out->q_draw, dv.q_draw, cols * nl * 4);
+      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (draw statistics)");
+    }
+    // this call's stream only, also after an error: the blob is freed below
+    const hipError_t se = hipStreamSynchronize(st);
+    if (rc == MPCT_OK && se != hipSuccess)
+      rc = fail(MPCT_EDEVICE, std::string("mpct_draw_stats failed on the device: ") + hipGetErrorString(se));
+  }
+  if (blob) (void)hipFree(blob);
+  if (st) (void)hipStreamDestroy(st);
+  if (dev != cur) (void)hipSetDevice(cur);
+  return rc;
+}
+
+// width of index field id in a scenario's records, and whether it is an integer field
+static int field_width(const mpct_scenario* s, int id) { return id < 8 ? s->my : s->nu; }
+static bool field_is_int(int id) { return id == MPCT_IX_T_EMAX || id == MPCT_IX_SETTLE; }
+
+// the argument checks of the two robust index entries, in the header's order; nothing here touches a device
+static int check_robust_indices(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* N2, const int32_t* Nu,
+                                const double* delta, const double* lambda, const double* r, const double* v,
+                                double j_bound, const mpct_opts* opts, const mpct_index_params* p, int32_t nsel,
+                                const int32_t* fields, int32_t nlev, const double* levels,
+                                const mpct_robust_result* base, const mpct_draw_stats_result* out) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the index entries are closed-loop only: open_loop must be 0");
+  if (nsel < 1 || nsel > 13 || !fields) return fail(MPCT_EINVAL, "nsel must be 1 .. 13 with a field list");
+  unsigned seen = 0;
+  for (int q = 0; q < nsel; ++q) {
+    if (fields[q] < MPCT_IX_IAE || fields[q] > MPCT_IX_U_HI) return fail(MPCT_EINVAL, "field id out of range");
+    if (seen & (1u << fields[q])) return fail(MPCT_EINVAL, "field id repeated");
+    seen |= 1u << fields[q];
+  }
+  if (nref < 1) return fail(MPCT_EINVAL, "nref < 1: the statistics need at least one draw");
+  if (!(j_bound >= 0.0)) return fail(MPCT_EINVAL, "j_bound must be >= 0 (0 = 1e100, +inf allowed), not negative or NaN");
+  int rc = stats_check_levels(nlev, levels);
+  if (rc) return rc;
+  const bool any_base = base && (base->mean || base->worst || base->n_failed || base->worst_draw || base->status);
+  const bool any_out = out && stats_out(out).any();
+  if (!any_base && !any_out) return fail(MPCT_EINVAL, "every output pointer of base and out is NULL");
+  if (base && base->J1) return fail(MPCT_EINVAL, "base->J1 must be NULL: the sample lives per chunk");
+  if (nlev == 0 && out && stats_out(out).any_level()) return fail(MPCT_EINVAL, "quantile, cvar and q_draw need nlev >= 1");
+  const mpct_result any{};
+  rc = check_args(s, C, nref, N2, Nu, delta, lambda, r, v, opts, &any);
+  if (rc) return rc;
+  rc = index_check_params(s->nit, p);
+  if (rc) return rc;
+  if (nref > MPCT_TAIL_MAX_DRAWS) return fail(MPCT_ERANGE, "nref > MPCT_TAIL_MAX_DRAWS (4096): the kernel's LDS holds no more draws");
+  if (C * nref * (int64_t)s->my > kIndexMaxRows || C * nref * (int64_t)s->nu > kIndexMaxRows)
+    return fail(MPCT_ERANGE, "C*nref*my or C*nref*nu exceeds MPCT_INDEX_MAX_ROWS");
+  return MPCT_OK;
+}
+
+// enqueue one batch with device pointers on `stream` (ctx's device is current).  Per chunk of whole
+// candidates: the closed loops with trajectories, J1 and status into the context's index scratch, the
+// selected index records, alive[c][k], then the statistics of each selected field and the base record
+static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                 const double* delta, const double* lambda, int32_t nref, const double* r, const double* v,
+                                 double j_bound, const mpct_opts* opts, const mpct_index_params* p, int32_t nsel,
+                                 const int32_t* fields, int32_t nlev, const double* levels, const RobustOut& base,
+                                 const DrawStatsOut& out, hipStream_t stream) {
+  if (C == 0) return MPCT_OK;
+  const int my = s->my, nu = s->nu, nit = s->nit;
+  const double bound = j_bound == 0.0 ? kRobustDefaultBound : j_bound;
+  const size_t per = (size_t)nref * (my + nu) * nit * 8;  // one candidate's trajectories: launch_indices' chunking
+  const size_t budget = g_index_budget > 0 ? (size_t)g_index_budget : (size_t)MPCT_INDEX_SCRATCH_BYTES;
+  const int64_t cc = std::min<int64_t>(C, std::max<int64_t>(1, (int64_t)(budget / per)));
+  // the chunk's scratch: y | u | J1 | status | alive | the selected fields' records, each 256-B aligned
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t Sc = (size_t)cc * nref;
+  const size_t o_j1 = al((size_t)cc * per), o_st = o_j1 + al(Sc * my * 8), o_al = o_st + al(Sc * 4);
+  size_t o_f[13], off = o_al + al(Sc * 4);
+  int W = 0;
+  for (int q = 0; q < nsel; ++q) {
+    o_f[q] = off;
+    off += al(Sc * field_width(s, fields[q]) * (field_is_int(fields[q]) ? 4 : 8));
+    W += field_width(s, fields[q]);
+  }
+  char* scr = nullptr;
+  int rc = index_scratch(cx, off, stream, &scr);
+  if (rc) return rc;
+  mpct_opts o = opts ? *opts : mpct_opts{0, 0, 0, -1, 0.0};
+  o.open_loop = 0;
+  o.want_traj = 1;
+  void* rec[13] = {nullptr};
+  for (int q = 0; q < nsel; ++q) rec[fields[q]] = scr + o_f[q];
+  const IndexOut io{(double*)rec[0], (double*)rec[1], (double*)rec[2], (double*)rec[3],  (int*)rec[4],
+                    (double*)rec[5], (double*)rec[6], (int*)rec[7],    (double*)rec[8],  (double*)rec[9],
+                    (double*)rec[10], (double*)rec[11], (double*)rec[12]};
+  const bool any_base = base.mean || base.worst || base.n_failed || base.worst_draw || base.status;
+  std::string err;
+  for (int64_t c0 = 0; c0 < C && rc == MPCT_OK; c0 += cc) {
+    const int64_t n = std::min(cc, C - c0);
+    mpct_result per_chunk{};
+    per_chunk.J1 = reinterpret_cast<double*>(scr + o_j1);
+    per_chunk.status = reinterpret_cast<int32_t*>(scr + o_st);
+    per_chunk.y = reinterpret_cast<double*>(scr);
+    per_chunk.u = per_chunk.y + (size_t)n * nref * my * nit;
+    int32_t* alive = reinterpret_cast<int32_t*>(scr + o_al);
+    rc = launch_batch(s, cx, n, N2 + c0, Nu + c0, delta + c0 * my, lambda + c0 * nu, nref, r, v, &o, &per_chunk, stream);
+    if (rc == MPCT_OK) rc = index_launch(per_chunk.y, per_chunk.u, r, n * nref, nref, my, nu, nit, p, io, stream);
+    if (rc != MPCT_OK) break;
+    int lrc = launch_draw_alive(n, nref, my, bound, per_chunk.J1, per_chunk.status, alive, stream, &err);
+    if (lrc == 0 && any_base) {
+      auto d = [](double* q, int64_t e) { return q ? q + e : nullptr; };
+      auto i = [](int32_t* q, int64_t e) { return q ? q + e : nullptr; };
+      const RobustOut ro{d(base.mean, c0 * my), d(base.worst, c0 * my), i(base.n_failed, c0), i(base.worst_draw, c0),
+                         i(base.status, c0)};
+      lrc = launch_robust_reduce(n, nref, my, bound, per_chunk.J1, per_chunk.status, ro, stream, &err);
+    }
+    if (lrc) {
+      rc = fail(MPCT_EDEVICE, err);
+      break;
+    }
+    if (!out.any()) continue;
+    int col = 0;
+    for (int q = 0; q < nsel && rc == MPCT_OK; ++q) {
+      const int w = field_width(s, fields[q]);
+      rc = stats_launch(rec[fields[q]], field_is_int(fields[q]) ? MPCT_STAT_I32 : MPCT_STAT_F64, alive, n, nref, w, nlev,
+                        levels, out.from(c0, W, nlev), W, col, stream);
+      col += w;
+    }
+  }
+  cx->index_pending = hipEventRecord(cx->index_used, stream) == hipSuccess;
+  return rc;
+}
+
+extern "C" int32_t mpct_eval_robust_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                   const double* delta, const double* lambda, int32_t nref,
+                                                   const double* r, const double* v, double j_bound,
+                                                   const mpct_opts* opts, const mpct_index_params* params, int32_t nsel,
+                                                   const int32_t* fields, int32_t nlev, const double* levels,
+                                                   mpct_robust_result* base, const mpct_draw_stats_result* out,
+                                                   void* stream) {
+  int rc = check_robust_indices(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, params, nsel, fields, nlev, levels,
+                                base, out);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
+  DevCtx* cx = nullptr;
+  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  if (rc) return rc;
+  const RobustOut ro = base ? RobustOut{base->mean, base->worst, base->n_failed, base->worst_draw, base->status} : RobustOut{};
+  return launch_robust_indices(s, cx, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, params, nsel, fields, nlev,
+                               levels, ro, out ? stats_out(out) : DrawStatsOut{}, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_eval_robust_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                            const double* delta, const double* lambda, int32_t nref, const double* r,
+                                            const double* v, double j_bound, const mpct_opts* opts,
+                                            const mpct_index_params* params, int32_t nsel, const int32_t* fields,
+                                            int32_t nlev, const double* levels, mpct_robust_result* base,
+                                            const mpct_draw_stats_result* out) {
+  int rc = check_robust_indices(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, params, nsel, fields, nlev, levels,
+                                base, out);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
+  DevCtx* cx = nullptr;
+  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  if (rc) return rc;
+  // host buffers in, the records out on the context's own stream, staged as eval_host does
+  const int my = s->my;
+  size_t W = 0;
+  for (int q = 0; q < nsel; ++q) W += field_width(s, fields[q]);
+  const size_t cols = (size_t)C * W, nl = (size_t)std::max(nlev, 1);
+  const mpct_robust_result hb = base ? *base : mpct_robust_result{};
+  const mpct_draw_stats_result ho = out ? *out : mpct_draw_stats_result{};
+  HostStage hs(s, cx, C);
+  const size_t o_mean = hs.slot(C * my * 8), o_worst = hs.slot(C * my * 8), o_nf = hs.slot(C * 4), o_wd = hs.slot(C * 4);
+  const size_t o_st = hs.slot(C * 4);
+  const size_t o_n = hs.slot(cols * 4), o_mn = hs.slot(cols * 8), o_lo = hs.slot(cols * 8), o_ld = hs.slot(cols * 4);
+  const size_t o_hi = hs.slot(cols * 8), o_hd = hs.slot(cols * 4), o_q = hs.slot(cols * nl * 8);
+  const size_t o_cv = hs.slot(cols * nl * 8), o_qd = hs.slot(cols * nl * 4);
+  rc = hs.upload(s, N2, Nu, delta, lambda, nref, r, v);
+  if (rc) return rc;
+  auto dd = [&](const void* want, size_t o) { return want ? hs.at<double>(o) : nullptr; };
+  auto di = [&](const void* want, size_t o) { return want ? hs.at<int32_t>(o) : nullptr; };
+  const RobustOut ro{dd(hb.mean, o_mean), dd(hb.worst, o_worst), di(hb.n_failed, o_nf), di(hb.worst_draw, o_wd),
+                     di(hb.status, o_st)};
+  const DrawStatsOut dv{di(ho.n, o_n),   dd(ho.mean, o_mn),    dd(ho.lo, o_lo),   di(ho.lo_draw, o_ld), dd(ho.hi, o_hi),
+                        di(ho.hi_draw, o_hd), dd(ho.quantile, o_q), dd(ho.cvar, o_cv), di(ho.q_draw, o_qd)};
+  rc = launch_robust_indices(s, cx, C, hs.N2(), hs.Nu(), hs.delta(), hs.lambda(), nref, hs.r, hs.v, j_bound, opts, params,
+                             nsel, fields, nlev, levels, ro, dv, hs.st);
+  if (rc) return hs.abandon(rc);
+  hs.fetch(hb.mean, o_mean, C * my * 8);
+  hs.fetch(hb.worst, o_worst, C * my * 8);
+  hs.fetch(hb.n_failed, o_nf, C * 4);
+  hs.fetch(hb.worst_draw, o_wd, C * 4);
+  hs.fetch(hb.status, o_st, C * 4);
+  hs.fetch(ho.n, o_n, cols * 4);
+  hs.fetch(ho.mean, o_mn, cols * 8);
+  hs.fetch(ho.lo, o_lo, cols * 8);
+  hs.fetch(ho.lo_draw, o_ld, cols * 4);
+  hs.fetch(ho.hi, o_hi, cols * 8);
+  hs.fetch(ho.hi_draw, o_hd, cols * 4);
+  hs.fetch(ho.quantile, o_q, cols * nl * 8);
+  hs.fetch(ho.cvar, o_cv, cols * nl * 8);
+  hs.fetch(ho.q_draw, o_qd, cols * nl * 4);
   return hs.finish();
 }
 

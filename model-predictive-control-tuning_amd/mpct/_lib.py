@@ -109,6 +109,16 @@ class MpctRobustTail(C.Structure):
     _fields_ = [("quantile", c_double_p), ("cvar", c_double_p), ("q_draw", c_int32_p)]
 
 
+# the fields of mpct_draw_stats_result in the struct's order: (name, integer?, per level?)
+STATS_FIELDS = [("n", True, False), ("mean", False, False), ("lo", False, False), ("lo_draw", True, False),
+                ("hi", False, False), ("hi_draw", True, False), ("quantile", False, True), ("cvar", False, True),
+                ("q_draw", True, True)]
+
+
+class MpctDrawStats(C.Structure):
+    _fields_ = [(n, c_int32_p if i else c_double_p) for n, i, _ in STATS_FIELDS]
+
+
 EXPORTS = [
     "mpct_abi_version", "mpct_last_error", "mpct_scenario_create", "mpct_scenario_destroy",
     "mpct_scenario_table", "mpct_eval_batch", "mpct_eval_batch_device", "mpct_lds_bytes", "mpct_lds_bytes_opts",
@@ -117,12 +127,14 @@ EXPORTS = [
     "mpct_scenario_create_est", "mpct_nmpc_scenario_create_var", "mpct_eval_robust_tail",
     "mpct_eval_robust_tail_device", "mpct_pareto_device", "mpct_pareto",
     "mpct_indices_device", "mpct_indices", "mpct_eval_indices", "mpct_eval_indices_device",
+    "mpct_draw_stats_device", "mpct_draw_stats", "mpct_eval_robust_indices", "mpct_eval_robust_indices_device",
 ]
 
 ABI_VERSION = 7
 TAIL_MAX_LEVELS, TAIL_MAX_DRAWS = 8, 4096
 PARETO_MAX_OBJ, PARETO_MAX_C, PARETO_MAX_LAYERS = 16, 1048576, 64
 INDEX_MAX_ROWS, INDEX_SCRATCH_BYTES = 2147483647, 268435456
+STAT_F64, STAT_I32 = 0, 1
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
 ST_SQP_MAXITER, ST_BOUNDS, ST_NOT_RUN = 32, 64, 128
 NMPC_VANDEVUSSE = 1
@@ -233,6 +245,20 @@ def load():
     # the trajectory-scratch budget of the index entries in bytes (0: the default): a test / bench hook
     lib.mpct_internal_index_budget.argtypes = [C.c_int64]
     lib.mpct_internal_index_budget.restype = C.c_int32
+    stats_args = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_double_p]
+    lib.mpct_draw_stats_device.argtypes = stats_args + [C.POINTER(MpctDrawStats), C.c_void_p]
+    lib.mpct_draw_stats_device.restype = C.c_int32
+    lib.mpct_draw_stats.argtypes = stats_args + [C.c_int32, C.POINTER(MpctDrawStats)]
+    lib.mpct_draw_stats.restype = C.c_int32
+    robust_index_args = robust_args[:11] + [C.POINTER(MpctIndexParams), C.c_int32, c_int32_p, C.c_int32, c_double_p,
+                                            C.POINTER(MpctRobustResult), C.POINTER(MpctDrawStats)]
+    lib.mpct_eval_robust_indices.argtypes = robust_index_args
+    lib.mpct_eval_robust_indices.restype = C.c_int32
+    lib.mpct_eval_robust_indices_device.argtypes = robust_index_args + [C.c_void_p]
+    lib.mpct_eval_robust_indices_device.restype = C.c_int32
+    # the largest grid of draw_stats_kernel in workgroups (0: the default): a test hook
+    lib.mpct_internal_draw_stats_grid.argtypes = [C.c_int32]
+    lib.mpct_internal_draw_stats_grid.restype = C.c_int32
     if lib.mpct_abi_version() != ABI_VERSION:
         raise ImportError("libmpct ABI version mismatch")
     _lib = lib

@@ -10,6 +10,10 @@
   indices_device      mpct_indices_device (torch CUDA tensors, enqueued on the current stream)
   eval_indices        mpct_eval_indices: score a batch and return only its index records
   eval_indices_device mpct_eval_indices_device (torch CUDA tensors, enqueued on a stream)
+  draw_stats          mpct_draw_stats: per-column statistics of a [C, D, m] table over its draw axis
+  draw_stats_device   mpct_draw_stats_device (torch CUDA tensors, enqueued on the current stream)
+  eval_robust_indices mpct_eval_robust_indices: per-candidate statistics of the indices over the plant draws
+  eval_robust_indices_device  mpct_eval_robust_indices_device (torch CUDA tensors, enqueued on a stream)
 
 No CPU fallback: every numerical result comes from the HIP kernel.
 """
@@ -752,3 +756,209 @@ def eval_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, v=None, t0=0, b
         C.c_void_p(stream.cuda_stream))
     if rc != 0:
         raise MpctError("mpct_eval_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+# --------------------------------------------------------------------------------------------
+# statistics of a table over its draw axis, and of the indices over the plant draws (mpct_draw_stats,
+# mpct_eval_robust_indices; include/mpct.h)
+@dataclass
+class DrawStats:
+    """One record per column (c, i) of a (C, D, m) table over its surviving draws; NaN / -1 where none survives."""
+    n: np.ndarray                        # (C, m) surviving draws
+    mean: np.ndarray                     # (C, m)
+    lo: np.ndarray                       # (C, m) smallest surviving value
+    lo_draw: np.ndarray                  # (C, m) the lowest draw that holds it
+    hi: np.ndarray                       # (C, m) largest surviving value
+    hi_draw: np.ndarray                  # (C, m) the lowest draw that holds it
+    levels: np.ndarray | None = None     # (nlev,)
+    quantile: np.ndarray | None = None   # (C, m, nlev) type-1 quantile of the survivors
+    cvar: np.ndarray | None = None       # (C, m, nlev) mean of the survivors from that rank upwards
+    q_draw: np.ndarray | None = None     # (C, m, nlev) the draw whose value is the quantile
+
+
+def _stats_arrays(Cn, m, nlev):
+    """The nine arrays of a statistics record (the per-level ones None without levels) and the MpctDrawStats
+    that points into them."""
+    arr, r = {}, _lib.MpctDrawStats()
+    for name, is_int, per_level in _lib.STATS_FIELDS:
+        if per_level and not nlev:
+            arr[name] = None
+            continue
+        a = np.zeros((Cn, m, nlev) if per_level else (Cn, m), dtype=np.int32 if is_int else np.float64)
+        arr[name] = a
+        setattr(r, name, _ip(a) if is_int else _dp(a))
+    return arr, r
+
+
+def _stats_struct(out: dict):
+    r = _lib.MpctDrawStats()
+    for name, is_int, _ in _lib.STATS_FIELDS:
+        setattr(r, name, _tptr(out.get(name), _lib.c_int32_p if is_int else _lib.c_double_p))
+    return r
+
+
+def draw_stats(x, alive=None, levels=None, device=-1) -> DrawStats:
+    """mpct_draw_stats: statistics of the (C, D, m) table ``x`` over its draw axis, reduced on the GPU (host
+    arrays in and out).  An integer ``x`` enters as int32 (a negative value is "no value"), anything else as
+    float64 (a non-finite value is no value).  ``alive`` (C, D): a zero drops the draw from every column of
+    its candidate.  ``levels`` (up to 8 values in (0, 1]) adds quantile, cvar and q_draw."""
+    x = np.asarray(x)
+    is_int = np.issubdtype(x.dtype, np.integer)
+    x = np.ascontiguousarray(x, dtype=np.int32 if is_int else np.float64)
+    if x.ndim != 3:
+        raise ValueError("x must be (C, D, m)")
+    Cn, D, m = x.shape
+    al = None
+    if alive is not None:
+        al = np.ascontiguousarray(alive, dtype=np.int32)
+        if al.shape != (Cn, D):
+            raise ValueError("alive must be (C, D)")
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    arr, r = _stats_arrays(Cn, m, nlev)
+    rc = _lib.load().mpct_draw_stats(x.ctypes.data, _lib.STAT_I32 if is_int else _lib.STAT_F64,
+                                     al.ctypes.data if al is not None else None, Cn, D, m, nlev,
+                                     _dp(lv) if nlev else None, int(device), C.byref(r))
+    if rc != 0:
+        raise MpctError("mpct_draw_stats failed (%d): %s" % (rc, _lib.last_error()))
+    return DrawStats(levels=lv, **arr)
+
+
+def draw_stats_device(x, out: dict, alive=None, levels=None):
+    """mpct_draw_stats_device: ``x`` is a contiguous float64 or int32 CUDA (HIP) tensor [C, D, m], ``alive`` an
+    int32 tensor [C, D] or None; the records are written into the tensors of ``out`` (keys as the fields of
+    DrawStats: n, lo_draw, hi_draw, q_draw int32, the others float64; [C, m] or [C, m, nlev]; any may be
+    absent).  ``levels`` is a HOST sequence.  Enqueued on the current torch stream of the tensor's device and
+    not synchronised."""
+    import torch
+
+    if x.dtype not in (torch.float64, torch.int32) or x.dim() != 3 or not x.is_contiguous():
+        raise ValueError("x must be a contiguous float64 or int32 tensor [C, D, m]")
+    if alive is not None and (alive.dtype != torch.int32 or tuple(alive.shape) != tuple(x.shape[:2]) or
+                              not alive.is_contiguous()):
+        raise ValueError("alive must be a contiguous int32 tensor [C, D]")
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    r = _stats_struct(out)
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    with torch.cuda.device(x.device):
+        rc = _lib.load().mpct_draw_stats_device(
+            C.c_void_p(x.data_ptr()), _lib.STAT_I32 if x.dtype == torch.int32 else _lib.STAT_F64,
+            C.c_void_p(alive.data_ptr()) if alive is not None else None, x.shape[0], x.shape[1], x.shape[2], nlev,
+            _dp(lv) if nlev else None, C.byref(r), C.c_void_p(stream))
+    if rc != 0:
+        raise MpctError("mpct_draw_stats_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+@dataclass
+class RobustIndexResult:
+    """Per candidate and column, the statistics of the selected performance indices over the surviving plant
+    draws.  ``columns`` names the W columns: (field name, channel) in selection order, an output-row field
+    contributing my columns and an input-row field nu.  ``base`` is the RobustResult of the same launch
+    (mean / worst of J1, n_failed, worst_draw, status)."""
+    columns: list
+    n: np.ndarray                        # (C, W)
+    mean: np.ndarray
+    lo: np.ndarray
+    lo_draw: np.ndarray
+    hi: np.ndarray
+    hi_draw: np.ndarray
+    base: RobustResult                   # costs() masks by its n_failed
+    levels: np.ndarray | None = None
+    quantile: np.ndarray | None = None   # (C, W, nlev)
+    cvar: np.ndarray | None = None
+    q_draw: np.ndarray | None = None
+
+    def costs(self, stat="hi", names=None, max_failed: int = 0) -> np.ndarray:
+        """(C, k) cost table for ``pareto``: the statistic ``stat`` ('mean', 'lo', 'hi', ('quantile', j) or
+        ('cvar', j) with j the level's index) of the columns whose field is in ``names`` (None: every column,
+        in selection order).  NaN for every candidate with more than ``max_failed`` failed draws, as
+        RobustResult.scores masks."""
+        if isinstance(stat, str):
+            if stat not in ("mean", "lo", "hi"):
+                raise ValueError("stat must be 'mean', 'lo', 'hi', ('quantile', j) or ('cvar', j)")
+            tab = getattr(self, stat)
+        else:
+            name, j = stat
+            if name not in ("quantile", "cvar"):
+                raise ValueError("stat must be 'mean', 'lo', 'hi', ('quantile', j) or ('cvar', j)")
+            if getattr(self, name) is None:
+                raise ValueError("this result has no %s: call eval_robust_indices with levels=" % name)
+            tab = getattr(self, name)[:, :, int(j)]
+        if names is None:
+            keep = list(range(len(self.columns)))
+        else:
+            for nm in names:
+                if not any(f == nm for f, _ in self.columns):
+                    raise ValueError("this result has no field %r" % (nm,))
+            keep = [k for nm in names for k, (f, _) in enumerate(self.columns) if f == nm]
+        out = np.array(np.asarray(tab, dtype=float)[:, keep], dtype=float, copy=True)
+        out[np.asarray(self.base.n_failed) > int(max_failed)] = np.nan
+        return out
+
+    def pareto(self, stat="hi", names=None, max_failed: int = 0, max_layers: int = 0, device: int = -1):
+        """Pareto analysis (``pareto``) of the table ``costs`` returns."""
+        return pareto(self.costs(stat, names, max_failed), max_layers=max_layers, device=device)
+
+
+def _field_ids(sc, fields):
+    """The ids of the selected fields as the int32 vector the library reads, and the (field, channel) columns."""
+    fields = _index_fields(fields)
+    ids = np.ascontiguousarray([INDEX_FIELDS.index(f) for f in fields], dtype=np.int32)
+    is_y = {n: y for n, y, _ in _lib.INDEX_FIELDS}
+    cols = [(f, ch) for f in fields for ch in range(sc.my if is_y[f] else sc.nu)]
+    return ids, cols
+
+
+def eval_robust_indices(sc, N2, Nu, delta, lam, refs, v=None, fields=None, levels=None, j_bound=0.0, t0=0,
+                        band_rel=0.02, band_abs=0.0, device=-1, max_qp_iter=0, feas_tol=0.0) -> RobustIndexResult:
+    """mpct_eval_robust_indices: score C candidates over the D = len(refs) draws and reduce, on the device, the
+    performance indices ``fields`` (default: all thirteen) of the C x D closed loops to per-candidate
+    statistics over the surviving draws (host arrays in and out).  A draw survives by eval_robust's rule
+    (status 0, total J1 finite and <= ``j_bound``); ``levels`` adds quantile, cvar and q_draw per column."""
+    N2, Nu, delta, lam, refs, Cn, D, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    ids, cols = _field_ids(sc, fields)
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    arr, out = _stats_arrays(Cn, len(cols), nlev)
+    base = RobustResult(mean=np.zeros((Cn, sc.my)), worst=np.zeros((Cn, sc.my)), n_failed=np.zeros(Cn, dtype=np.int32),
+                        worst_draw=np.zeros(Cn, dtype=np.int32), status=np.zeros(Cn, dtype=np.int32), draws=D)
+    br = _lib.MpctRobustResult()
+    br.mean, br.worst = _dp(base.mean), _dp(base.worst)
+    br.n_failed, br.worst_draw, br.status = _ip(base.n_failed), _ip(base.worst_draw), _ip(base.status)
+    p = _lib.MpctIndexParams(int(t0), float(band_rel), float(band_abs))
+    o = _opts(False, False, device, max_qp_iter, feas_tol)
+    rc = sc.lib.mpct_eval_robust_indices(sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data, lam.ctypes.data,
+                                         D, refs.ctypes.data, vv.ctypes.data if vv is not None else None, float(j_bound),
+                                         C.byref(o), C.byref(p), ids.size, _ip(ids), nlev, _dp(lv) if nlev else None,
+                                         C.byref(br), C.byref(out))
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return RobustIndexResult(columns=cols, levels=lv, base=base, **arr)
+
+
+def eval_robust_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, base: dict | None = None, v=None, fields=None,
+                               levels=None, j_bound=0.0, t0=0, band_rel=0.02, band_abs=0.0, device=-1, stream=None):
+    """Device-pointer entry of eval_robust_indices: every argument is a CUDA (HIP) torch tensor (``fields`` and
+    ``levels`` are HOST sequences); the statistics are written into the tensors of ``out`` (the keys of
+    draw_stats_device, [C, W] / [C, W, nlev]) and the robust record of J1 into those of ``base`` (the keys
+    of eval_robust_device without J1).  Enqueued on ``stream`` (torch stream; default: current) and not
+    synchronised."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    ids, _ = _field_ids(sc, fields)
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    br = _robust_struct(base or {})
+    p = _lib.MpctIndexParams(int(t0), float(band_rel), float(band_abs))
+    o = _opts(False, False, device)
+    so = _stats_struct(out)
+    rc = sc.lib.mpct_eval_robust_indices_device(
+        sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+        C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+        C.c_void_p(v.data_ptr()) if v is not None else None, float(j_bound), C.byref(o), C.byref(p), ids.size, _ip(ids),
+        nlev, _dp(lv) if nlev else None, C.byref(br), C.byref(so), C.c_void_p(stream.cuda_stream))
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_indices_device failed (%d): %s" % (rc, _lib.last_error()))
