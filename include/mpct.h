@@ -29,7 +29,8 @@
  *     and the closed-loop performance indices (mpct_index_params, mpct_index_result, mpct_indices_device,
  *     mpct_indices, mpct_eval_indices, mpct_eval_indices_device), and the statistics of any per-simulation
  *     table over its draws (mpct_draw_stats_result, mpct_draw_stats_device, mpct_draw_stats,
- *     mpct_eval_robust_indices, mpct_eval_robust_indices_device).
+ *     mpct_eval_robust_indices, mpct_eval_robust_indices_device), and the hypervolume of a front with its
+ *     members' exclusive contributions (mpct_hv_result, mpct_hypervolume_device, mpct_hypervolume).
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -569,6 +570,87 @@ int32_t mpct_pareto_device(const double* costs, int64_t C, int32_t k, int32_t ma
  * the calling thread's current device is unchanged on return.  Without a device: MPCT_EDEVICE with a message. */
 int32_t mpct_pareto(const double* costs, int64_t C, int32_t k, int32_t max_layers, int32_t device,
                     const mpct_pareto_result* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Hypervolume of a set of cost vectors inside a box, and every member's exclusive contribution, on the
+ * device (hypervolume.hip).  mpct_pareto ends in a front that is too large to read; this
+ * says how good a front is (the volume of the box it dominates: compare two fronts in one box) and which
+ * of its members matter (the volume a member alone dominates: 0 = redundant, the largest = the knees).
+ * Exact hypervolume is exponential in k, so this is a Monte-Carlo estimate over a counter-based sample
+ * set: N points x M members x k column tests, and every result an integer count.
+ *
+ * costs is [C][k] row-major, mpct_pareto's table: 1 <= k <= MPCT_PARETO_MAX_OBJ, 0 <= C <= MPCT_PARETO_MAX_C.
+ * members[M] are int32 indices into costs, 0 <= M <= MPCT_PARETO_MAX_C.  members NULL means candidates
+ * 0 .. C-1, and then M must equal C.  An entry -1 is SKIPPED, so the -1-padded front of mpct_pareto may
+ * be passed as it is with M = C.  Any other entry outside [0, C) is MPCT_EINVAL for mpct_hypervolume,
+ * which reads the entries on the host; mpct_hypervolume_device cannot see them before it enqueues and
+ * treats such an entry as skipped.  A duplicated index counts twice.
+ *
+ * lo[k], ref[k] are the box: every value finite and lo[j] < ref[j].  n_samples = N, 1 <= N <=
+ * MPCT_HV_MAX_SAMPLES; seed is any uint64.
+ *
+ * A member row with a NaN among its k costs covers nothing (mpct_pareto's validity rule); +-INFINITY are
+ * ordinary values; -0.0 equals +0.0.
+ *
+ * SAMPLE POINTS, part of the contract, in uint64 arithmetic that wraps.  Point i in [0, N), column j in [0, k):
+ *     x = seed + 0x9E3779B97F4A7C15 * (16*i + j + 1)
+ *     x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9
+ *     x ^= x >> 27;  x *= 0x94D049BB133111EB
+ *     x ^= x >> 31
+ *     u   = (double)(x >> 11) * 2^-53
+ *     p_j = lo_j + u * (ref_j - lo_j)
+ * with the difference and the product each rounded to double before the sum (no fused multiply-add).
+ *
+ * Member a COVERS point p when a_j <= p_j for every j < k.  depth(p) is the number of entries of members,
+ * neither skipped nor NaN, that cover p.
+ *
+ *   n_covered[0]    number of points with depth >= 1
+ *   excl[m]         number of points with depth exactly 1 whose one covering entry is members[m]; 0 for a
+ *                   skipped or NaN entry; equal vectors cover the same points, so each of them gets 0
+ *   depth_hist[b]   number of points with depth 0, 1, .., 6 and (b = 7) >= 7: how much the members overlap
+ *   hv[0]           ((double)n_covered / (double)N) * vol, vol the product over ascending j of (ref_j - lo_j)
+ *                   starting from 1.0, every factor and product rounded
+ * Any of the four pointers may be NULL, not all of them.  A repeated call is bitwise identical; a
+ * permutation of members permutes excl and changes nothing else; no result depends on the launch geometry.
+ *
+ * Argument errors, in this order and before any device is touched:
+ *   MPCT_EINVAL  k < 1 or k > MPCT_PARETO_MAX_OBJ
+ *   MPCT_EINVAL  C < 0 or M < 0
+ *   MPCT_ERANGE  C or M > MPCT_PARETO_MAX_C
+ *   MPCT_ERANGE  n_samples > MPCT_HV_MAX_SAMPLES
+ *   MPCT_EINVAL  n_samples < 1
+ *   MPCT_EINVAL  costs NULL (with M > 0)
+ *   MPCT_EINVAL  members NULL with M != C
+ *   MPCT_EINVAL  lo or ref NULL
+ *   MPCT_EINVAL  out NULL, or all four of its pointers NULL
+ *   MPCT_EINVAL  (mpct_hypervolume only) a value of lo or ref not finite, or lo[j] >= ref[j]
+ *   MPCT_EINVAL  (mpct_hypervolume only) an entry of members below -1 or >= C
+ * The last two read the caller's arrays, which only the host entry can do: mpct_hypervolume_device writes
+ * hv[0] = NaN for such a box (the counts are then whatever the comparisons give) and skips such an entry.
+ * M = 0 is legal: every count is 0, depth_hist[0] = N and hv[0] follows from n_covered = 0. */
+#define MPCT_HV_MAX_SAMPLES 1073741824
+#define MPCT_HV_BINS 8
+typedef struct mpct_hv_result {
+  int64_t* n_covered;  /* [1] */
+  int64_t* excl;       /* [M] */
+  int64_t* depth_hist; /* [MPCT_HV_BINS] */
+  double* hv;          /* [1] */
+} mpct_hv_result;
+
+/* All pointers DEVICE pointers, lo, ref and the outputs included; enqueued on `stream` (NULL = default
+ * stream) and NOT synchronised.  Scratch comes from hipMallocAsync / hipFreeAsync on that stream, as in
+ * mpct_pareto_device, so calls on different streams are independent.  The work is bounded by N, M and k alone. */
+int32_t mpct_hypervolume_device(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                                const double* lo, const double* ref, int64_t n_samples, uint64_t seed,
+                                const mpct_hv_result* out, void* stream);
+
+/* Host pointers (MATLAB and C callers); needs no scenario.  device: HIP ordinal, -1 = the current device
+ * (an ordinal out of range is MPCT_EINVAL).  Stages on a stream of its own and waits for that stream only;
+ * the calling thread's current device is unchanged on return.  M = 0 needs no device.  Without a device:
+ * MPCT_EDEVICE with a message. */
+int32_t mpct_hypervolume(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                         const double* lo, const double* ref, int64_t n_samples, uint64_t seed, int32_t device,
+                         const mpct_hv_result* out);
 
 /* ---------------------------------------------------------------------------------------------
  * Closed-loop performance indices per simulation, reduced on the device from the trajectories

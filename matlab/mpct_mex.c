@@ -37,6 +37,14 @@
  *                                                    defines them, -1: a candidate with a NaN cost); layer is
  *                                                    [] with max_layers = 0; max_layers and device optional
  *                                                    (0: no layers; -1: the current device)
+ *   H = mpct_mex('hypervolume', costs, members, lo, ref, n_samples, seed, device)
+ *                                                    Monte-Carlo hypervolume the rows `members` of the C x k cost
+ *                                                    table dominate inside the box [lo, ref] (mpct_hypervolume;
+ *                                                    no scenario needed): members are 1-BASED rows, e.g. P.front
+ *                                                    ([]: all rows, 0: a skipped entry); struct with hv, n_covered,
+ *                                                    n_samples, volume (scalars), excl and contribution (M x 1:
+ *                                                    the points / the volume a member alone covers) and depth_hist
+ *                                                    (8 x 1); n_samples (2^20), seed (0) and device (-1) optional
  *   I = mpct_mex('indices', y, u, r, params)         performance indices of stored trajectories (mpct_indices;
  *                                                    no scenario needed): y my x nit x S, u nu x nit x S,
  *                                                    r my x nit x nref; struct with iae, ise, itae, emax, t_emax,
@@ -598,6 +606,73 @@ static void cmd_pareto(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = P;
 }
 
+/* an optional integer argument: [] or absent gives dflt */
+static double opt_integer(int nrhs, const mxArray* prhs[], int i, const char* what, double dflt, double lo, double hi) {
+  const double v = (nrhs > i && !mxIsEmpty(prhs[i])) ? scalar(prhs[i], what) : dflt;
+  if (v != floor(v) || v < lo || v > hi) mexErrMsgIdAndTxt("mpct:arg", "'%s' must be an integer in range", what);
+  return v;
+}
+
+/* H = mpct_mex('hypervolume', costs, members, lo, ref [, n_samples, seed, device]): costs is C x k column-major,
+ * transposed here into the library's [C][k] rows; members are 1-BASED rows of costs ([]: all of them, 0: a
+ * skipped entry, the library's -1); the shapes and the box are the library's to judge (its message is surfaced) */
+static void cmd_hypervolume(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 5 || nrhs > 8)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: H = mpct_mex('hypervolume', costs, members, lo, ref [, n_samples, seed, device])");
+  const mxArray* a = prhs[1];
+  if (!a || !mxIsNumeric(a) || mxIsComplex(a) || mxIsSparse(a) || mxGetNumberOfDimensions(a) != 2)
+    mexErrMsgIdAndTxt("mpct:arg", "'costs' must be a real full C x k matrix");
+  const long C = (long)mxGetM(a), k = (long)mxGetN(a);
+  if (k > 1000000) mexErrMsgIdAndTxt("mpct:arg", "'costs' has too many columns");
+  const int all = mxIsEmpty(prhs[2]);
+  const long M = all ? C : (long)mxGetNumberOfElements(prhs[2]);
+  const double ns = opt_integer(nrhs, prhs, 5, "n_samples", 1048576.0, -9007199254740992.0, 9007199254740992.0);
+  const double sd = opt_integer(nrhs, prhs, 6, "seed", 0.0, 0.0, 9007199254740992.0);
+  const double dv = opt_integer(nrhs, prhs, 7, "device", -1.0, -1e6, 1e6);
+  double* mm = all ? NULL : doubles(prhs[2], M, "members");
+  int32_t* mem = all ? NULL : (int32_t*)mxMalloc((size_t)(M + 1) * sizeof(int32_t));
+  for (long m = 0; !all && m < M; ++m) {
+    if (mm[m] != floor(mm[m]) || mm[m] < 0.0 || mm[m] > 2147483647.0)
+      mexErrMsgIdAndTxt("mpct:arg", "'members' must hold 1-based row indices (0: skipped)");
+    mem[m] = (int32_t)mm[m] - 1;
+  }
+  double* lo = doubles(prhs[3], k, "lo");
+  double* ref = doubles(prhs[4], k, "ref");
+  double* cm = doubles(a, C * k, "costs");
+  double* rows = (double*)mxMalloc((size_t)(C * k + 1) * sizeof(double));
+  for (long c = 0; c < C; ++c)
+    for (long j = 0; j < k; ++j) rows[c * k + j] = cm[(size_t)j * C + c];
+  int64_t ncov = 0, hist[MPCT_HV_BINS];
+  double hv = 0.0;
+  mpct_hv_result r;
+  r.n_covered = &ncov;
+  r.excl = (int64_t*)mxCalloc((size_t)(M + 1), sizeof(int64_t));
+  r.depth_hist = hist;
+  r.hv = &hv;
+  if (mpct_hypervolume(rows, C, (int32_t)k, mem, M, lo, ref, (int64_t)ns, (uint64_t)sd, (int32_t)dv, &r) != MPCT_OK)
+    lib_error("mpct:hypervolume");
+  double vol = 1.0;
+  for (long j = 0; j < k; ++j) vol *= ref[j] - lo[j];
+  const char* names[7] = {"hv", "n_covered", "n_samples", "excl", "depth_hist", "contribution", "volume"};
+  mxArray* H = mxCreateStructMatrix(1, 1, 7, names);
+  mxSetField(H, 0, "hv", mxCreateDoubleScalar(hv));
+  mxSetField(H, 0, "n_covered", mxCreateDoubleScalar((double)ncov));
+  mxSetField(H, 0, "n_samples", mxCreateDoubleScalar(ns));
+  mxArray* e = mxCreateDoubleMatrix((mwSize)M, 1, mxREAL);
+  mxArray* cb = mxCreateDoubleMatrix((mwSize)M, 1, mxREAL);
+  for (long m = 0; m < M; ++m) {
+    mxGetPr(e)[m] = (double)r.excl[m];
+    mxGetPr(cb)[m] = (double)r.excl[m] / ns * vol;
+  }
+  mxSetField(H, 0, "excl", e);
+  mxArray* d = mxCreateDoubleMatrix(MPCT_HV_BINS, 1, mxREAL);
+  for (int b = 0; b < MPCT_HV_BINS; ++b) mxGetPr(d)[b] = (double)hist[b];
+  mxSetField(H, 0, "depth_hist", d);
+  mxSetField(H, 0, "contribution", cb);
+  mxSetField(H, 0, "volume", mxCreateDoubleScalar(vol));
+  plhs[0] = H;
+}
+
 /* ---- closed-loop performance indices (mpct_indices, mpct_eval_indices; include/mpct.h) */
 static const char* const kIndexNames[13] = {"iae", "ise", "itae", "emax", "t_emax", "over", "e_final", "settle",
                                             "tv", "du2", "dumax", "u_lo", "u_hi"};
@@ -950,6 +1025,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_eval_robust(plhs, nrhs, prhs, 1);
   } else if (!strcmp(cmd, "pareto")) {
     cmd_pareto(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "hypervolume")) {
+    cmd_hypervolume(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "indices")) {
     cmd_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "eval_indices")) {

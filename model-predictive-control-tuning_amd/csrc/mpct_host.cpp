@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -15,6 +16,7 @@
 #include "work_order.h"
 #include "dtc_robust.h"
 #include "pareto.h"
+#include "hypervolume.h"
 #include "traj_indices.h"
 #include "draw_stats.h"
 
@@ -491,6 +493,126 @@ extern "C" int32_t mpct_pareto(const double* costs, int64_t C, int32_t k, int32_
     const hipError_t se = hipStreamSynchronize(st);
     if (rc == MPCT_OK && se != hipSuccess)
       rc = fail(MPCT_EDEVICE, std::string("mpct_pareto failed on the device: ") + hipGetErrorString(se));
+  }
+  if (blob) (void)hipFree(blob);
+  if (st) (void)hipStreamDestroy(st);
+  if (dev != cur) (void)hipSetDevice(cur);
+  return rc;
+}
+
+// ---- Hypervolume of a front and per-member contributions (hypervolume.hip).  The argument checks of both
+// entries, in the order include/mpct.h states, before any device is touched; nothing is dereferenced
+static int hv_check(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M, const double* lo,
+                    const double* ref, int64_t N, const mpct_hv_result* out) {
+  if (k < 1 || k > MPCT_PARETO_MAX_OBJ) return fail(MPCT_EINVAL, "k must be 1 .. MPCT_PARETO_MAX_OBJ");
+  if (C < 0 || M < 0) return fail(MPCT_EINVAL, "C < 0 or M < 0");
+  if (C > MPCT_PARETO_MAX_C || M > MPCT_PARETO_MAX_C) return fail(MPCT_ERANGE, "C or M exceeds MPCT_PARETO_MAX_C");
+  if (N > MPCT_HV_MAX_SAMPLES) return fail(MPCT_ERANGE, "n_samples exceeds MPCT_HV_MAX_SAMPLES");
+  if (N < 1) return fail(MPCT_EINVAL, "n_samples < 1");
+  if (M > 0 && !costs) return fail(MPCT_EINVAL, "costs is NULL");
+  if (!members && M != C) return fail(MPCT_EINVAL, "members is NULL: M must equal C");
+  if (!lo || !ref) return fail(MPCT_EINVAL, "lo or ref is NULL");
+  if (!out || !(out->n_covered || out->excl || out->depth_hist || out->hv))
+    return fail(MPCT_EINVAL, "no output pointer in mpct_hv_result");
+  return MPCT_OK;
+}
+
+// tile length (128 or 256; 0: the default) and the largest grid in workgroups (0: the default) of
+// hv_count_kernel.  A test hook, not part of include/mpct.h: the tests reach the multi-tile and striding
+// paths at small shapes with it, tools/hv_bench.py runs its A/B with it
+static int32_t g_hv_tile = 0, g_hv_blocks = 0;
+extern "C" int32_t mpct_internal_hv_tuned(int32_t tile, int32_t max_blocks) {
+  if ((tile != 0 && tile != 128 && tile != 256) || max_blocks < 0) return fail(MPCT_EINVAL, "tile must be 0, 128 or 256, max_blocks >= 0");
+  g_hv_tile = tile;
+  g_hv_blocks = max_blocks;
+  return MPCT_OK;
+}
+
+static int32_t hv_launch(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M, const double* lo,
+                         const double* ref, int64_t N, uint64_t seed, const mpct_hv_result* out, hipStream_t stream) {
+  std::string err;
+  const HvOut ho{reinterpret_cast<long long*>(out->n_covered), reinterpret_cast<long long*>(out->excl),
+                 reinterpret_cast<long long*>(out->depth_hist), out->hv};
+  const int rc = hypervolume_device(costs, C, k, members, M, lo, ref, N, seed, ho, stream, &err, g_hv_tile, g_hv_blocks);
+  if (rc) return fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err);
+  return MPCT_OK;
+}
+
+extern "C" int32_t mpct_hypervolume_device(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                                           const double* lo, const double* ref, int64_t n_samples, uint64_t seed,
+                                           const mpct_hv_result* out, void* stream) {
+  const int rc = hv_check(costs, C, k, members, M, lo, ref, n_samples, out);
+  if (rc) return rc;
+  return hv_launch(costs, C, k, members, M, lo, ref, n_samples, seed, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_hypervolume(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                                    const double* lo, const double* ref, int64_t n_samples, uint64_t seed, int32_t device,
+                                    const mpct_hv_result* out) {
+  int rc = hv_check(costs, C, k, members, M, lo, ref, n_samples, out);
+  if (rc) return rc;
+  double vol = 1.0;
+  for (int j = 0; j < k; ++j) {
+    if (!std::isfinite(lo[j]) || !std::isfinite(ref[j]) || !(lo[j] < ref[j]))
+      return fail(MPCT_EINVAL, "the box needs finite lo and ref with lo[j] < ref[j]");
+    vol *= ref[j] - lo[j];
+  }
+  for (int64_t m = 0; members && m < M; ++m)
+    if (members[m] < -1 || members[m] >= C) return fail(MPCT_EINVAL, "an entry of members is below -1 or >= C");
+  if (M == 0) {  // nothing to stage
+    if (out->n_covered) out->n_covered[0] = 0;
+    for (int b = 0; out->depth_hist && b < MPCT_HV_BINS; ++b) out->depth_hist[b] = b ? 0 : n_samples;
+    if (out->hv) out->hv[0] = (0.0 / (double)n_samples) * vol;
+    return MPCT_OK;
+  }
+  int cur = -1, cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
+    return fail(MPCT_EDEVICE, "no HIP device (mpct_hypervolume needs a GPU)");
+  const int dev = device < 0 ? cur : device;
+  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
+  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
+  // one blob: costs | members | lo | ref | excl | n_covered, depth_hist, hv; each 256-B aligned; a stream of this call's own
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t nc = al((size_t)C * k * sizeof(double)), nm = al((size_t)M * sizeof(int32_t)), nb = al((size_t)k * sizeof(double)),
+               ne = al((size_t)M * sizeof(int64_t));
+  hipStream_t st = nullptr;
+  char* blob = nullptr;
+  rc = MPCT_OK;
+  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
+  } else if (hipMalloc(reinterpret_cast<void**>(&blob), nc + nm + 2 * nb + ne + 3 * 256) != hipSuccess) {
+    rc = fail(MPCT_ENOMEM, "hipMalloc failed (hypervolume staging)");
+  } else {
+    double* dcosts = reinterpret_cast<double*>(blob);
+    int32_t* dmem = members ? reinterpret_cast<int32_t*>(blob + nc) : nullptr;
+    double* dlo = reinterpret_cast<double*>(blob + nc + nm);
+    double* dref = reinterpret_cast<double*>(blob + nc + nm + nb);
+    char* tail = blob + nc + nm + 2 * nb + ne;
+    mpct_hv_result d{};
+    d.excl = out->excl ? reinterpret_cast<int64_t*>(blob + nc + nm + 2 * nb) : nullptr;
+    d.n_covered = out->n_covered ? reinterpret_cast<int64_t*>(tail) : nullptr;
+    d.depth_hist = out->depth_hist ? reinterpret_cast<int64_t*>(tail + 256) : nullptr;
+    d.hv = out->hv ? reinterpret_cast<double*>(tail + 512) : nullptr;
+    bool ok = hipMemcpyAsync(dcosts, costs, (size_t)C * k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
+              (!dmem || hipMemcpyAsync(dmem, members, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, st) == hipSuccess) &&
+              hipMemcpyAsync(dlo, lo, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(dref, ref, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hypervolume inputs)");
+    if (ok) {
+      rc = hv_launch(dcosts, C, k, dmem, M, dlo, dref, n_samples, seed, &d, st);
+      ok = rc == MPCT_OK;
+    }
+    if (ok) {
+      ok = (!d.excl || hipMemcpyAsync(out->excl, d.excl, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.n_covered || hipMemcpyAsync(out->n_covered, d.n_covered, sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.depth_hist || hipMemcpyAsync(out->depth_hist, d.depth_hist, MPCT_HV_BINS * sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.hv || hipMemcpyAsync(out->hv, d.hv, sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess);
+      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hypervolume results)");
+    }
+    // this call's stream only, also after an error: the blob is freed below
+    const hipError_t se = hipStreamSynchronize(st);
+    if (rc == MPCT_OK && se != hipSuccess)
+      rc = fail(MPCT_EDEVICE, std::string("mpct_hypervolume failed on the device: ") + hipGetErrorString(se));
   }
   if (blob) (void)hipFree(blob);
   if (st) (void)hipStreamDestroy(st);

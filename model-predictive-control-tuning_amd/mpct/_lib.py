@@ -90,6 +90,10 @@ class MpctParetoResult(C.Structure):
     _fields_ = [("dom_count", c_int32_p), ("layer", c_int32_p), ("front", c_int32_p), ("n_front", c_int32_p)]
 
 
+class MpctHvResult(C.Structure):
+    _fields_ = [("n_covered", c_int64_p), ("excl", c_int64_p), ("depth_hist", c_int64_p), ("hv", c_double_p)]
+
+
 class MpctIndexParams(C.Structure):
     _fields_ = [("t0", C.c_int32), ("band_rel", C.c_double), ("band_abs", C.c_double)]
 
@@ -128,11 +132,13 @@ EXPORTS = [
     "mpct_eval_robust_tail_device", "mpct_pareto_device", "mpct_pareto",
     "mpct_indices_device", "mpct_indices", "mpct_eval_indices", "mpct_eval_indices_device",
     "mpct_draw_stats_device", "mpct_draw_stats", "mpct_eval_robust_indices", "mpct_eval_robust_indices_device",
+    "mpct_hypervolume_device", "mpct_hypervolume",
 ]
 
 ABI_VERSION = 7
 TAIL_MAX_LEVELS, TAIL_MAX_DRAWS = 8, 4096
 PARETO_MAX_OBJ, PARETO_MAX_C, PARETO_MAX_LAYERS = 16, 1048576, 64
+HV_MAX_SAMPLES, HV_BINS = 1073741824, 8
 INDEX_MAX_ROWS, INDEX_SCRATCH_BYTES = 2147483647, 268435456
 STAT_F64, STAT_I32 = 0, 1
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
@@ -231,6 +237,14 @@ def load():
     lib.mpct_internal_pareto_tuned.restype = C.c_int32
     lib.mpct_internal_pareto_grid.argtypes = [C.c_int64, c_int32_p]
     lib.mpct_internal_pareto_grid.restype = C.c_int32
+    hv_args = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64]
+    lib.mpct_hypervolume_device.argtypes = hv_args + [C.POINTER(MpctHvResult), C.c_void_p]
+    lib.mpct_hypervolume_device.restype = C.c_int32
+    lib.mpct_hypervolume.argtypes = hv_args + [C.c_int32, C.POINTER(MpctHvResult)]
+    lib.mpct_hypervolume.restype = C.c_int32
+    # the tile length (0, 128, 256) and the largest grid (0: the default) of hv_count_kernel: a test / bench hook
+    lib.mpct_internal_hv_tuned.argtypes = [C.c_int32, C.c_int32]
+    lib.mpct_internal_hv_tuned.restype = C.c_int32
     index_args = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                   C.POINTER(MpctIndexParams)]
     lib.mpct_indices_device.argtypes = index_args + [C.POINTER(MpctIndexResult), C.c_void_p]

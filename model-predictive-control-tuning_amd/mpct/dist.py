@@ -198,6 +198,101 @@ def pareto_candidates(costs: torch.Tensor, C: int | None = None, max_layers: int
     return res
 
 
+def _hv_points(lo: torch.Tensor, ref: torch.Tensor, seed: int, i0: int, i1: int) -> torch.Tensor:
+    """Sample points i0 .. i1 - 1 of the hypervolume contract (include/mpct.h), [i1 - i0, k] on lo's device.
+    torch has no uint64 arithmetic: int64 products wrap to the same bits, and a logical right shift is an
+    arithmetic one with the copied sign bits masked off."""
+    def s64(c):
+        c &= (1 << 64) - 1
+        return c - (1 << 64) if c >= (1 << 63) else c
+
+    def lsr(x, s):
+        return (x >> s) & ((1 << (64 - s)) - 1)
+
+    dev, k = lo.device, lo.numel()
+    i = torch.arange(i0, i1, dtype=torch.int64, device=dev)[:, None]
+    j = torch.arange(k, dtype=torch.int64, device=dev)[None, :]
+    x = (16 * i + j + 1) * s64(0x9E3779B97F4A7C15) + s64(int(seed))
+    x = (x ^ lsr(x, 30)) * s64(0xBF58476D1CE4E5B9)
+    x = (x ^ lsr(x, 27)) * s64(0x94D049BB133111EB)
+    x = x ^ lsr(x, 31)
+    u = lsr(x, 11).to(torch.float64) * 2.0 ** -53
+    return lo + u * (ref - lo)          # three kernels: the difference and the product are rounded
+
+
+def _hypervolume_torch(costs: torch.Tensor, members, lo: torch.Tensor, ref: torch.Tensor, n_samples: int, seed: int,
+                       chunk: int = 4096, mchunk: int = 2048):
+    """The contract of mpct_hypervolume_device (include/mpct.h) as chunked torch expressions, on the tensor's
+    device: the CPU path of hypervolume_candidates, and what tools/hv_bench.py times the kernel against.
+    Returns (n_covered, excl [M] int64, depth_hist [8] int64, hv)."""
+    Cn, k = costs.shape
+    dev = costs.device
+    mem = torch.arange(Cn, dtype=torch.int64, device=dev) if members is None else members.to(torch.int64)
+    pos = torch.nonzero((mem >= 0) & (mem < Cn)).flatten()      # an entry outside [0, C) is skipped
+    A = costs[mem[pos]]                                         # a NaN row covers nothing: NaN <= p is false
+    excl = torch.zeros(mem.numel(), dtype=torch.int64, device=dev)
+    hist = torch.zeros(8, dtype=torch.int64, device=dev)
+    for i0 in range(0, n_samples, chunk):
+        P = _hv_points(lo, ref, seed, i0, min(n_samples, i0 + chunk))
+        depth = torch.zeros(P.shape[0], dtype=torch.int64, device=dev)
+        which = torch.zeros(P.shape[0], dtype=torch.int64, device=dev)
+        for m0 in range(0, A.shape[0], mchunk):
+            le = (A[None, m0:m0 + mchunk, :] <= P[:, None, :]).all(dim=2)
+            depth += le.sum(dim=1)
+            which += (le * pos[None, m0:m0 + mchunk]).sum(dim=1)   # the covering entry itself where depth == 1
+        hist += torch.bincount(depth.clamp(max=7), minlength=8)
+        excl += torch.bincount(which[depth == 1], minlength=mem.numel())
+    n_cov = int(n_samples - hist[0].item())
+    vol = 1.0
+    for l, r in zip(lo.tolist(), ref.tolist()):
+        vol *= r - l
+    return n_cov, excl, hist, (float(n_cov) / float(n_samples)) * vol
+
+
+def hypervolume_candidates(costs: torch.Tensor, front=None, lo=None, ref=None, n_samples: int = 1 << 20, seed: int = 0,
+                           C: int | None = None) -> dict:
+    """Hypervolume of the members ``front`` (indices into the gathered cost records, e.g. pareto_candidates'
+    front; -1 entries are skipped; None: every record) inside the box [lo, ref], and every member's exclusive
+    contribution (contract: mpct_hypervolume_device in include/mpct.h).  Returns a dict: hv (float), n_covered
+    (int), n_samples, excl [M] int64 and depth_hist [8] int64 on the costs' device, lo and ref [k] float64
+    there too.  Identical on every rank: the sample points are a function of (seed, i) and all counts are
+    integers.  ``lo`` / ``ref`` None: mpct.engine.default_box on the host.  GPU tensors go through
+    mpct_hypervolume_device on the current stream; CPU tensors (the gloo tests) through chunked torch
+    expressions."""
+    from . import engine
+
+    if C is not None:
+        costs = costs[:C]
+    if costs.dim() == 1:
+        costs = costs[:, None]
+    c = costs.to(torch.float64).contiguous()
+    n, k = c.shape
+    if not 1 <= k <= 16:
+        raise ValueError("k must be 1 .. 16")
+    if not 1 <= int(n_samples) <= 1 << 30:
+        raise ValueError("n_samples must be 1 .. 2**30")
+    mem = None if front is None else torch.as_tensor(front).to(device=c.device, dtype=torch.int32).contiguous().flatten()
+    if lo is None or ref is None or not torch.is_tensor(lo) or not torch.is_tensor(ref):
+        lo, ref = engine.default_box(c.cpu().numpy(), None if mem is None else mem.cpu().numpy(),
+                                     lo.cpu().numpy() if torch.is_tensor(lo) else lo,
+                                     ref.cpu().numpy() if torch.is_tensor(ref) else ref)
+    lo = torch.as_tensor(lo, dtype=torch.float64).to(c.device).contiguous()
+    ref = torch.as_tensor(ref, dtype=torch.float64).to(c.device).contiguous()
+    if not (bool(torch.isfinite(lo).all()) and bool(torch.isfinite(ref).all()) and bool((lo < ref).all())):
+        raise ValueError("the box needs finite lo and ref with lo < ref")
+    M = n if mem is None else mem.numel()
+    if c.is_cuda:
+        out = dict(n_covered=torch.empty(1, dtype=torch.int64, device=c.device),
+                   excl=torch.empty(M, dtype=torch.int64, device=c.device),
+                   depth_hist=torch.empty(8, dtype=torch.int64, device=c.device),
+                   hv=torch.empty(1, dtype=torch.float64, device=c.device))
+        engine.hypervolume_device(c, out, lo, ref, members=mem, n_samples=n_samples, seed=seed)
+        n_cov, excl, hist, hv = int(out["n_covered"].item()), out["excl"], out["depth_hist"], float(out["hv"].item())
+    else:
+        n_cov, excl, hist, hv = _hypervolume_torch(c, mem, lo, ref, int(n_samples), int(seed))
+    return dict(hv=hv, n_covered=n_cov, n_samples=int(n_samples), excl=excl, depth_hist=hist, lo=lo, ref=ref)
+
+
 # measured one-GPU time of every config-3 cell alone (tools/shard_balance.py --cells): the (N2, Nu)
 # cells of mpct.scenarios.config3_grid with 1024 lambda draws each, whole and in two halves
 CELL_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "config3_cells.json")

@@ -6,6 +6,8 @@
   closedloop_toolbox  drop-in for closedloop_toolbox.m:1 (one candidate, full trajectories)
   pareto              mpct_pareto: front, domination counts and layers of a [C, k] cost table
   pareto_device       mpct_pareto_device (torch CUDA tensors, enqueued on the current stream)
+  hypervolume         mpct_hypervolume: Monte-Carlo hypervolume of a front in a box, per-member contributions
+  hypervolume_device  mpct_hypervolume_device (torch CUDA tensors, enqueued on the current stream)
   indices             mpct_indices: performance indices (IAE, overshoot, settling, valve travel ..) of trajectories
   indices_device      mpct_indices_device (torch CUDA tensors, enqueued on the current stream)
   eval_indices        mpct_eval_indices: score a batch and return only its index records
@@ -409,6 +411,15 @@ class RobustResult:
         than ``max_failed`` failed draws is invalid: dom_count and layer -1, never on the front.
         ``columns`` adds tail columns of an eval_robust(levels=...) result as further objectives: pairs
         (name, j) with name 'quantile' or 'cvar' and j the level's index."""
+        return pareto(self._cost_table(stat, max_failed, columns), max_layers=max_layers, device=device)
+
+    def hypervolume(self, stat: str = "worst", max_failed: int = 0, columns=(), device: int = -1, **kw):
+        """``hypervolume`` of the front of the cost table ``pareto`` analyses (same ``stat``, ``max_failed`` and
+        ``columns``); ``kw`` are hypervolume's lo, ref, n_samples and seed."""
+        costs = self._cost_table(stat, max_failed, columns)
+        return pareto(costs, device=device).hypervolume(costs, device=device, **kw)
+
+    def _cost_table(self, stat, max_failed, columns):
         cols = [self.scores(max_failed, stat)]
         for name, j in columns:
             if name not in ("quantile", "cvar"):
@@ -419,7 +430,7 @@ class RobustResult:
             cols.append(np.asarray(tab, dtype=float)[:, int(j)].reshape(-1, 1))
         costs = np.hstack(cols)
         costs[np.isnan(cols[0]).any(axis=1)] = np.nan   # the masking of scores covers the added columns too
-        return pareto(costs, max_layers=max_layers, device=device)
+        return costs
 
 
 def _levels(levels):
@@ -529,6 +540,10 @@ class ParetoResult:
     layer: np.ndarray | None        # (C,) non-dominated-sorting layer, max_layers = deeper; -1 = invalid; None without max_layers
     front: np.ndarray               # (n_front,) the candidates with dom_count 0, ascending
 
+    def hypervolume(self, costs, **kw):
+        """``hypervolume`` of this front: ``costs`` is the table the front was computed from."""
+        return hypervolume(costs, members=self.front, **kw)
+
 
 def _pareto_costs(costs):
     a = np.ascontiguousarray(costs, dtype=np.float64)
@@ -570,6 +585,117 @@ def pareto_device(costs, out: dict, max_layers: int = 0):
                                             int(max_layers), C.byref(r), C.c_void_p(stream))
     if rc != 0:
         raise MpctError("mpct_pareto_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+# --------------------------------------------------------------------------------------------
+# Hypervolume of a front in a box and per-member contributions (mpct_hypervolume, include/mpct.h)
+@dataclass
+class HypervolumeResult:
+    """Monte-Carlo over ``n_samples`` counter-based points of the box [lo, ref]: member a covers point p when
+    a <= p in every objective."""
+    hv: float                       # n_covered / n_samples * volume
+    n_covered: int                  # points covered by at least one member
+    n_samples: int
+    excl: np.ndarray                # (M,) int64 points that member m alone covers; 0: redundant
+    depth_hist: np.ndarray          # (8,) int64 points covered by 0, 1, .., 6 and >= 7 members
+    lo: np.ndarray                  # (k,) the box
+    ref: np.ndarray
+    volume: float                   # of the box
+    members: np.ndarray | None = None   # (M,) the candidates excl refers to (-1: skipped); None: all, in order
+
+    @property
+    def contribution(self) -> np.ndarray:
+        """(M,) the volume each member alone dominates"""
+        return self.excl / self.n_samples * self.volume
+
+
+def box_volume(lo, ref) -> float:
+    """The product over ascending j of (ref_j - lo_j) from 1.0, every factor rounded (the contract's vol)."""
+    vol = 1.0
+    for l, r in zip(np.asarray(lo, dtype=np.float64).tolist(), np.asarray(ref, dtype=np.float64).tolist()):
+        vol *= r - l
+    return vol
+
+
+def default_box(costs, members=None, lo=None, ref=None):
+    """(lo, ref) with the ones not given computed over the members that have no NaN: lo = the column minima,
+    ref = hi + 0.1 (hi - lo) with hi the column maxima, and hi + 0.1 max(|hi|, 1) where hi == lo."""
+    a = _pareto_costs(costs)
+    if lo is None or ref is None:
+        m = None if members is None else np.asarray(members, dtype=np.int64).reshape(-1)
+        rows = a if m is None else a[m[(m >= 0) & (m < a.shape[0])]]
+        rows = rows[~np.isnan(rows).any(axis=1)]
+        if rows.shape[0] == 0:
+            raise ValueError("no member without NaN: give lo and ref explicitly")
+        cmin, cmax = rows.min(axis=0), rows.max(axis=0)
+        with np.errstate(invalid="ignore"):
+            span = np.where(cmax == cmin, np.maximum(np.abs(cmax), 1.0), cmax - cmin)
+        lo = cmin if lo is None else lo
+        ref = cmax + 0.1 * span if ref is None else ref
+    lo = np.array(np.broadcast_to(np.asarray(lo, dtype=np.float64), (a.shape[1],)))   # owned copies
+    ref = np.array(np.broadcast_to(np.asarray(ref, dtype=np.float64), (a.shape[1],)))
+    if not (np.isfinite(lo).all() and np.isfinite(ref).all()):
+        raise ValueError("the box is not finite (lo = %s, ref = %s): give lo and ref explicitly" % (lo, ref))
+    return lo, ref
+
+
+def hypervolume(costs, members=None, lo=None, ref=None, n_samples: int = 1 << 20, seed: int = 0,
+                device: int = -1) -> HypervolumeResult:
+    """mpct_hypervolume: the hypervolume the rows ``members`` of the (C, k) cost table dominate inside the box
+    [lo, ref] (None: all rows; -1 entries are skipped, so a -1-padded front may be passed), estimated over
+    ``n_samples`` counter-based points on the GPU, with every member's exclusive contribution.  ``lo`` / ``ref``
+    None: ``default_box``."""
+    a = _pareto_costs(costs)
+    Cn, k = a.shape
+    mem = None if members is None else np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+    M = Cn if mem is None else mem.size
+    lo, ref = default_box(a, mem, lo, ref)
+    excl = np.zeros(M, dtype=np.int64)
+    hist = np.zeros(_lib.HV_BINS, dtype=np.int64)
+    ncov = np.zeros(1, dtype=np.int64)
+    hv = np.zeros(1, dtype=np.float64)
+    i64 = lambda x: x.ctypes.data_as(_lib.c_int64_p)
+    r = _lib.MpctHvResult(i64(ncov), i64(excl), i64(hist), _dp(hv))
+    rc = _lib.load().mpct_hypervolume(a.ctypes.data, Cn, k, mem.ctypes.data if mem is not None else None, M,
+                                      lo.ctypes.data, ref.ctypes.data, int(n_samples), int(seed) & (2 ** 64 - 1),
+                                      int(device), C.byref(r))
+    if rc != 0:
+        raise MpctError("mpct_hypervolume failed (%d): %s" % (rc, _lib.last_error()))
+    return HypervolumeResult(hv=float(hv[0]), n_covered=int(ncov[0]), n_samples=int(n_samples), excl=excl,
+                             depth_hist=hist, lo=lo, ref=ref, volume=box_volume(lo, ref),
+                             members=None if mem is None else mem.copy())
+
+
+def hypervolume_device(costs, out: dict, lo, ref, members=None, n_samples: int = 1 << 20, seed: int = 0):
+    """mpct_hypervolume_device: ``costs`` is a float64 CUDA (HIP) tensor [C, k], ``members`` an int32 tensor [M]
+    or None (all rows), ``lo`` and ``ref`` float64 tensors [k] on the same device (there is no default box:
+    computing one would wait for the device).  The results are written into the tensors of ``out`` (keys
+    n_covered [1], excl [M], depth_hist [8]: int64; hv [1]: float64; any may be absent).  Enqueued on the
+    current torch stream of the tensor's device and not synchronised."""
+    import torch
+
+    if costs.dtype != torch.float64 or costs.dim() != 2 or not costs.is_contiguous():
+        raise ValueError("costs must be a contiguous float64 tensor [C, k]")
+    k = costs.shape[1]
+    for name, t in (("lo", lo), ("ref", ref)):
+        if t.dtype != torch.float64 or t.shape != (k,) or not t.is_contiguous() or t.device != costs.device:
+            raise ValueError("%s must be a contiguous float64 tensor [k] on the costs' device" % name)
+    if members is not None and (members.dtype != torch.int32 or members.dim() != 1 or not members.is_contiguous()
+                                or members.device != costs.device):
+        raise ValueError("members must be a contiguous int32 tensor [M] on the costs' device")
+    M = costs.shape[0] if members is None else members.shape[0]
+    if out.get("excl") is not None and out["excl"].numel() < M:
+        raise ValueError("out['excl'] holds fewer than M entries")
+    r = _lib.MpctHvResult(*[_tptr(out.get(f), _lib.c_int64_p) for f in ("n_covered", "excl", "depth_hist")],
+                          _tptr(out.get("hv"), _lib.c_double_p))
+    stream = torch.cuda.current_stream(costs.device).cuda_stream
+    with torch.cuda.device(costs.device):
+        rc = _lib.load().mpct_hypervolume_device(C.c_void_p(costs.data_ptr()), costs.shape[0], k,
+                                                 C.c_void_p(members.data_ptr()) if members is not None else None, M,
+                                                 C.c_void_p(lo.data_ptr()), C.c_void_p(ref.data_ptr()), int(n_samples),
+                                                 int(seed) & (2 ** 64 - 1), C.byref(r), C.c_void_p(stream))
+    if rc != 0:
+        raise MpctError("mpct_hypervolume_device failed (%d): %s" % (rc, _lib.last_error()))
 
 
 # --------------------------------------------------------------------------------------------
@@ -899,6 +1025,12 @@ class RobustIndexResult:
     def pareto(self, stat="hi", names=None, max_failed: int = 0, max_layers: int = 0, device: int = -1):
         """Pareto analysis (``pareto``) of the table ``costs`` returns."""
         return pareto(self.costs(stat, names, max_failed), max_layers=max_layers, device=device)
+
+    def hypervolume(self, stat="hi", names=None, max_failed: int = 0, device: int = -1, **kw):
+        """``hypervolume`` of the front of the table ``costs`` returns; ``kw`` are hypervolume's lo, ref,
+        n_samples and seed."""
+        costs = self.costs(stat, names, max_failed)
+        return pareto(costs, device=device).hypervolume(costs, device=device, **kw)
 
 
 def _field_ids(sc, fields):
