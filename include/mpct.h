@@ -314,7 +314,14 @@ void mpct_scenario_destroy(mpct_scenario* s);
 /* Host-table inspection (testing / MATLAB-side debugging; no device needed).
  *   which: 0 = MV step table [my][nu][tlen], 1 = free-response table Phi [my*n2_max][nx],
  *          2 = dims {my, nu, nd, n2_max, nu_max, tlen, nx, nyh, nup, nit, nq},
- *          3 = Phi on the device state basis [y-r, backward differences of y | du history]
+ *          3 = Phi on the device state basis [y-r, backward differences of y | du history],
+ *          4 = the pre-factored prologue rows a device context of this scenario uploads: per
+ *              horizon pair (N2 <= n2_max, Nu <= min(N2, nu_max)), in that order, my*min(N2, nu*Nu)
+ *              rows of width nu*Nu + nx, row my*k + i = row k of [R_i | T_i] with G_i = Q_i R_i,
+ *              T_i = Q_i' Phi_i (table 3's rows).  Empty (0) when the scenario's kernel streams
+ *              [G | Phi] instead: not a small plant, more than 16 MiB of rows, or the scenario was
+ *              created with the environment variable MPCT_NO_QR_TABLES set to a non-zero number
+ *              (the streamed prologue, for comparisons of the two row sources in one process).
  * Copies at most cap doubles into buf; returns the number of doubles the table holds, or <0. */
 int64_t mpct_scenario_table(const mpct_scenario* s, int32_t which, double* buf, int64_t cap);
 

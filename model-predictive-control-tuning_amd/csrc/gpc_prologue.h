@@ -24,13 +24,36 @@ namespace mpct {
 // nullptr = identity).  Returns false (uniformly) when R is not positive definite.
 // RINV = false: no R^-1 (an unconstrained loop has no QP); FIRST = true: only the first-move rows
 // m = n Nu of A, stored as row n (DTC_GPC_WW.m:105 Km: the unconstrained loop applies those alone)
-template <int MAXM, bool PACKED = false, bool RINV = true, bool FIRST = false, int kHB = 8>
+// TABLES = true: when the scenario carries the pre-factored rows (sc.qrt, scenario_tables.h
+// qr_tables) the QR streams those instead: my min(N2, M) rows sqrt(delta_i) [R_i | T_i] (G_i = Q_i R_i,
+// T_i = Q_i' Phi_i, factored once per horizon pair on the host) in place of the my N2 dense rows, the
+// same R (diagonal positive) and T up to rounding, and each block's reflections start at its first
+// nonzero column.  The choice is uniform over a launch (one scenario); without the tables, and in
+// every TABLES = false instance, the rows are streamed as before (bitwise the results of the
+// prologue without the switch).  Passes (M + nx > 64) read their own T columns of the table rows, as
+// they do of Phi, so the tables serve that case too.  Both row sources share one block loop and
+// branch (wave-uniformly) where a row is read: with a loop per source gpc_small_kernel kept R's
+// columns and the prefetched block live across the join and spilled (128 VGPRs, 92 B of scratch,
+// against 121 and none).
+template <int MAXM, bool PACKED = false, bool RINV = true, bool FIRST = false, int kHB = 8, bool TABLES = false>
 __device__ __forceinline__ bool gpc_prologue(const DevScenario& sc, int lane, int M, int Nu, int N2,
                                              const double* dl, const double* lm, double* sR, double* sRi,
                                              double* sA, int astride, const int* acol) {
   const int my = sc.my, nu = sc.nu, nx = sc.nx;
   const int vper = kWave - M;  // V columns per pass (host guarantees M < 64)
   const int npass = (nx + vper - 1) / vper;
+  const double* tab = nullptr;  // this horizon pair's table rows, their count and width
+  int trows = 0, tw = 0;
+  if constexpr (TABLES) {
+    if (sc.qrt) {
+      const int off = sc.qrt_off[(N2 - 1) * sc.numax + (Nu - 1)];
+      if (off >= 0) {
+        tab = sc.qrt + off;
+        trows = my * (N2 < M ? N2 : M);
+        tw = M + nx;
+      }
+    }
+  }
   double rcol[MAXM];
   int gn = 0, gc = 0;
   if (lane < M) {
@@ -108,22 +131,45 @@ __device__ __forceinline__ bool gpc_prologue(const DevScenario& sc, int lane, in
 #pragma unroll
       for (int i = 0; i < kHB; ++i) w[i] = fma(-f, wk[i], w[i]);
     };
-    const int P = my * N2;
+    // lane's entry of the next table row (row my k + i: row k of output ti = i): column l of R_i
+    // (l < M) or the lane's T_i column, scaled like a streamed row; zero rows pad the last block.
+    // The row pointer is wave-uniform, the lane adds its column
+    const unsigned tcol = lane < M ? lane : M + vc;
+    const bool tlane = lane < M || vlane;
+    const double* trow = tab;
+    int tp = 0, ti = 0;
+    auto table_row = [&]() __attribute__((always_inline)) -> double {
+      double v = 0.0;
+      if (tp < trows) {
+        if (tlane) v = trow[tcol];
+        v *= bcast(sqv, ti);
+        trow += tw;
+        ++tp;
+        if (++ti == my) ti = 0;
+      }
+      return v;
+    };
+    // one block loop for both row sources (the branch in next() is uniform over the launch)
+    auto next = [&]() __attribute__((always_inline)) -> double { return tab ? table_row() : fetch(); };
+    const int P = tab ? trows : my * N2;
     const int nblk = (P + kHB - 1) / kHB;
     double nb[kHB];
 #pragma unroll
-    for (int i = 0; i < kHB; ++i) nb[i] = fetch();
+    for (int i = 0; i < kHB; ++i) nb[i] = next();
     for (int blk = 0; blk < nblk; ++blk) {
       double w[kHB];
 #pragma unroll
       for (int i = 0; i < kHB; ++i) w[i] = nb[i];
       if (blk + 1 < nblk) {  // prefetch the next block (L2 latency under the reflections)
 #pragma unroll
-        for (int i = 0; i < kHB; ++i) nb[i] = fetch();
+        for (int i = 0; i < kHB; ++i) nb[i] = next();
       }
+      // table rows my k + i are zero left of column k: the block's reflections start at the level
+      // of its first row (wave-uniform) instead of finding sig == 0 after the broadcasts
+      const int k0 = tab ? (blk * kHB) / my : 0;
 #pragma unroll
       for (int k = 0; k < MAXM; ++k)
-        if (k < M) reflect(w, k);
+        if (k >= k0 && k < M) reflect(w, k);
     }
     if (pass == 0) {  // R to LDS; singular R -> status
       lds_sync();

@@ -21,6 +21,11 @@ constexpr long long kOrderMinC = 256;  // at most one workgroup per CU: a single
 constexpr int kGramM = 16;                              // QP size of the dispatch-key Gram tables
 constexpr int kGramOut = kGramM * kGramM + kGramM;      // doubles per output and (N2, Nu) block
 constexpr long long kGramMaxBytes = 64ll << 20;         // larger tables are not built
+// the prologue's pre-factored rows (DevScenario::qrt): Shell 3x3 needs 1.2 MB at n2max = 30,
+// numax = 5 (nx = 35), 2.7 MB at numax = 8 and 10 MB at n2max = 60, numax = 10, which stay in the
+// Infinity Cache beside a launch's working set; wider search ranges (60 MB at n2max = 127,
+// numax = 15) keep the streamed prologue
+constexpr long long kQrtMaxBytes = 16ll << 20;
 
 
 constexpr int kMaxOut = 16;    // outputs (my)
@@ -89,6 +94,12 @@ struct DevScenario {
   // triangles) then G_o'1 (kGramM), G_o = the forced-response matrix of output o (MatG.m); only
   // for nu Nu <= kGramM and my <= 4
   const double* gram;
+  // the prologue's pre-factored rows (scenario_tables.h qr_tables; nullptr when not built: the
+  // prologue then streams the weighted rows of [G | Phi], gpc_prologue.h).  qrt_off[(N2 - 1) numax +
+  // Nu - 1] is the cell's offset in doubles (-1: no such cell); the cell holds my min(N2, M) rows of
+  // width M + nx, row my k + i = row k of [R_i | T_i] (G_i = Q_i R_i, T_i = Q_i' Phi_i)
+  const double* qrt;
+  const int* qrt_off;
   const double* phi;    // [my*n2max][nx]   free response rows (Diophantine F | deltaUFree Hp)
   const int* n1;        // [my]   first predicted step
   const int* yoff;      // [my]   offset of y_i history (length na_i+1) in the state

@@ -90,6 +90,10 @@ extern "C" const char* mpct_last_error(void) { return g_err.c_str(); }
 // hand a builder's scenario to the caller, or report why there is none
 static int32_t created(std::unique_ptr<mpct_scenario> s, const BuildError& err, mpct_scenario** out) {
   if (!s) return fail(err.code, err.msg);
+  // MPCT_NO_QR_TABLES=1 at creation: this scenario's prologue streams its rows (scenario_tables.h
+  // qr_tables are not packed), so both row sources can be run and timed in one process
+  const char* e = getenv("MPCT_NO_QR_TABLES");
+  if (e && *e && atoi(e) != 0) s->qr_tables = 0;
   *out = s.release();
   g_err.clear();
   return MPCT_OK;
@@ -185,6 +189,10 @@ extern "C" int64_t mpct_scenario_table(const mpct_scenario* s, int32_t which, do
   else if (which == 2) {
     dims = {(double)s->my, (double)s->nu, (double)s->nd, (double)s->n2max, (double)s->numax,
             (double)s->tlen, (double)s->nx, (double)s->nyh, (double)s->nup, (double)s->nit, (double)s->nq};
+    src = &dims;
+  } else if (which == 4) {  // what pack_tables packs: the rows of a small plant unless switched off
+    std::vector<int> off;
+    if (s->qr_tables && dev_scenario(s).small) qr_tables(s, dims, off);
     src = &dims;
   } else
     return fail(MPCT_EINVAL, "unknown table");

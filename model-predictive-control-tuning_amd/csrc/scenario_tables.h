@@ -72,6 +72,9 @@ struct mpct_scenario {
   std::vector<int> xc;      // [ny] 0-based output states
   std::vector<double> nm;   // see DevScenario::nm
   std::vector<double> nmv;  // plant variants [nvar][NM_NPAR + 3] (DevScenario::nmv); empty: plant = model
+  // 0: no pre-factored prologue rows are packed (qr_tables), the prologue streams [G | Phi] as it
+  // does for a scenario over kQrtMaxBytes (mpct_scenario_create: environment MPCT_NO_QR_TABLES)
+  int qr_tables = 1;
   // device state, one context per device ordinal (created on first use, kept until destroy):
   // a scenario can be evaluated on several GPUs of one process (mpct_eval_batch_multi)
   std::vector<DevCtx*> ctx;
@@ -784,6 +787,74 @@ inline void gram_tables(const mpct_scenario* s, std::vector<double>& g) {
     }
 }
 
+// the prologue's pre-factored rows (DevScenario::qrt, gpc_prologue.h).  Output i contributes the rows
+// sqrt(delta_i) [G_i | Phi_i] to the prologue's QR, with G_i (N2 x M, M = nu Nu, the entries of
+// gram_tables' G_o) and Phi_i (N2 x nx, the device basis phid) depending on the scenario and the
+// horizon pair alone.  With the Householder QR G_i = Q_i R_i and T_i = Q_i' Phi_i,
+//   W'W = sum_i delta_i R_i'R_i + Lambda   and   W'V = sum_i delta_i R_i'T_i,
+// so the QR of the stacked rows sqrt(delta_i) [R_i | T_i], seeded with Lambda^1/2, gives the
+// prologue's R and T = Q1'V; no normal equations are formed.  For every pair N2 <= n2max,
+// Nu <= min(N2, numax) the table holds the first min(N2, M) rows of every [R_i | T_i], width M + nx,
+// interleaved over the outputs: row my k + i is row k of output i, which is zero left of column k, so
+// a block of the kernel's row stream is one contiguous read whose first nonzero column is known.  A
+// column that is already zero below its diagonal (dead time; the last row) takes no reflection.
+// off[(N2 - 1) numax + Nu - 1] is the cell's offset in doubles, -1 where there is no cell.  Both
+// stay empty when the scenario has no free-response table (band, NMPC) or the rows would exceed
+// max_bytes
+inline void qr_tables(const mpct_scenario* s, std::vector<double>& q, std::vector<int>& off,
+                      long long max_bytes = kQrtMaxBytes) {
+  q.clear();
+  off.clear();
+  const int my = s->my, nu = s->nu, nx = s->nx, n2max = s->n2max, numax = s->numax, tlen = s->tlen;
+  if (s->nmpc || s->mdband || nu < 1 || s->step.empty() || s->phid.empty()) return;
+  std::vector<int> o((size_t)n2max * numax, -1);
+  long long total = 0;
+  for (int N2 = 1; N2 <= n2max; ++N2)
+    for (int Nu = 1; Nu <= std::min(N2, numax); ++Nu) {
+      const int M = nu * Nu;
+      o[(size_t)(N2 - 1) * numax + (Nu - 1)] = (int)total;
+      total += (long long)my * std::min(N2, M) * (M + nx);
+      if (total * 8 > max_bytes) return;
+    }
+  q.assign((size_t)total, 0.0);
+  std::vector<double> a;  // [G_i | Phi_i], N2 x (M + nx), factored in place
+  for (int N2 = 1; N2 <= n2max; ++N2)
+    for (int Nu = 1; Nu <= std::min(N2, numax); ++Nu) {
+      const int M = nu * Nu, W = M + nx, rn = std::min(N2, M);
+      double* cell = q.data() + o[(size_t)(N2 - 1) * numax + (Nu - 1)];
+      for (int i = 0; i < my; ++i) {
+        a.assign((size_t)N2 * W, 0.0);
+        for (int r = 0; r < N2; ++r) {
+          double* row = &a[(size_t)r * W];
+          for (int c = 0; c < M; ++c) {
+            const int n = c / Nu, tt = s->n1[i] + r - (c - n * Nu);
+            row[c] = tt >= 0 ? s->step[((size_t)i * nu + n) * tlen + tt] : 0.0;
+          }
+          std::copy_n(&s->phid[((size_t)i * n2max + r) * nx], nx, row + M);
+        }
+        for (int k = 0; k < rn; ++k) {
+          double sig = 0.0;
+          for (int r = k + 1; r < N2; ++r) sig += a[(size_t)r * W + k] * a[(size_t)r * W + k];
+          if (sig == 0.0) continue;
+          const double x0 = a[(size_t)k * W + k], nrm = std::sqrt(x0 * x0 + sig);
+          const double alpha = x0 > 0.0 ? -nrm : nrm, v0 = x0 - alpha;  // same signs: no cancellation
+          const double tau = 2.0 / (v0 * v0 + sig);
+          for (int c = k + 1; c < W; ++c) {
+            double dot = v0 * a[(size_t)k * W + c];
+            for (int r = k + 1; r < N2; ++r) dot += a[(size_t)r * W + k] * a[(size_t)r * W + c];
+            dot *= tau;
+            a[(size_t)k * W + c] -= dot * v0;
+            for (int r = k + 1; r < N2; ++r) a[(size_t)r * W + c] -= dot * a[(size_t)r * W + k];
+          }
+          a[(size_t)k * W + k] = alpha;
+          for (int r = k + 1; r < N2; ++r) a[(size_t)r * W + k] = 0.0;
+        }
+        for (int k = 0; k < rn; ++k) std::copy_n(&a[(size_t)k * W], W, cell + ((size_t)k * my + i) * W);
+      }
+    }
+  off = std::move(o);
+}
+
 // longest run of numerator taps from an entry's first nonzero one (mdband_kernel.hip keeps only
 // those in LDS: the delay's leading zeros are skipped by pl_off / mz_off anyway)
 inline int compact_taps(const ZTables& z) {
@@ -909,6 +980,15 @@ inline PackedTables pack_tables(const mpct_scenario* s) {
   if (s->nmv.empty()) p.dslots.pop_back();  // plant = model: the pointer stays null
   putd(&DevScenario::gram, gram);
   if (gram.empty()) p.dslots.pop_back();  // not built: the pointer stays null (its padding stays in the blob)
+  // the prologue's pre-factored rows, for the kernel that reads them (gpc_small_kernel); not built,
+  // over kQrtMaxBytes or switched off: both pointers stay null and the prologue streams its rows
+  std::vector<double> qrt;
+  std::vector<int> qoff;
+  if (p.ds.small && s->qr_tables) qr_tables(s, qrt, qoff);
+  if (!qrt.empty()) {
+    putd(&DevScenario::qrt, qrt);
+    puti(&DevScenario::qrt_off, qoff);
+  }
   putd(&DevScenario::sm_coef, smt.coef);
   puti(&DevScenario::sm_hoff, smt.hoff);
   puti(&DevScenario::sm_hc, smt.hc);
