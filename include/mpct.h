@@ -30,7 +30,9 @@
  *     mpct_indices, mpct_eval_indices, mpct_eval_indices_device), and the statistics of any per-simulation
  *     table over its draws (mpct_draw_stats_result, mpct_draw_stats_device, mpct_draw_stats,
  *     mpct_eval_robust_indices, mpct_eval_robust_indices_device), and the hypervolume of a front with its
- *     members' exclusive contributions (mpct_hv_result, mpct_hypervolume_device, mpct_hypervolume).
+ *     members' exclusive contributions (mpct_hv_result, mpct_hypervolume_device, mpct_hypervolume), and
+ *     the greedy selection of the members that carry a front (mpct_hv_select_result,
+ *     mpct_hv_select_device, mpct_hv_select).
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -658,6 +660,82 @@ int32_t mpct_hypervolume_device(const double* costs, int64_t C, int32_t k, const
 int32_t mpct_hypervolume(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
                          const double* lo, const double* ref, int64_t n_samples, uint64_t seed, int32_t device,
                          const mpct_hv_result* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Hypervolume subset selection: the n members that carry a front, by greedy forward selection on the
+ * coverage count, on the device (hv_select.hip).  excl of mpct_hypervolume says what a member
+ * alone dominates with every other member present, so two near-duplicate knees hide each other and a short
+ * list of the largest excl can miss whole regions of the trade-off.  This call picks, round by round, the
+ * member that covers the most sample points no earlier pick covers.  The count is monotone and submodular,
+ * so the first n picks cover at least 1 - (1 - 1/n)^n of what the best n-subset covers of the same sample
+ * set, and the gains order the members so that the list may be cut anywhere.
+ *
+ * costs, C, k, members, M, lo, ref, n_samples and seed are mpct_hypervolume's, with its sample points, its
+ * coverage rule, NaN rows and -1 entries that cover nothing, +-INFINITY as ordinary values, -0.0 equal to
+ * +0.0 and a duplicated index as a separate entry.  n_pick = K is the number of rounds, 1 <= K <=
+ * MPCT_HVSEL_MAX_PICKS; K may exceed M.
+ *
+ * U_0 is all N points.  Round r = 0 .. K-1: gain_r(m) = #{i in U_r : members[m] covers p_i}.  If the largest
+ * gain is 0 the selection ENDS: n_picked = r, and the slots r .. K-1 hold the fill stated below.  Otherwise
+ * m_r is the smallest m with the largest gain, and U_(r+1) = U_r minus the points m_r covers.
+ *
+ *   n_picked[0]       rounds that picked a member
+ *   pos[r]            m_r, the position in members of round r's pick; -1 after the end
+ *   index[r]          members[m_r] (m_r when members is NULL); -1 after the end
+ *   gain[r]           points newly covered by round r's pick; 0 after the end
+ *   covered[r]        gain[0] + .. + gain[r]; stays at its last value after the end (0 when nothing was picked)
+ *   hv[r]             ((double)covered[r] / (double)N) * vol, vol as in mpct_hypervolume
+ *   ties[r]           entries of members that held round r's largest gain (1: the pick was forced); 0 after the end
+ *   n_covered_all[0]  points covered by any entry: mpct_hypervolume's n_covered
+ * Any of the eight pointers may be NULL, not all of them.  A repeated call is bitwise identical; no result
+ * depends on the launch geometry; gain is non-increasing; if the selection ends before K,
+ * covered[n_picked - 1] == n_covered_all; where every ties[r] == 1, a permutation of members leaves index,
+ * gain, covered and hv unchanged and permutes pos.
+ *
+ * Argument errors, in this order and before any device is touched:
+ *   MPCT_EINVAL  k < 1 or k > MPCT_PARETO_MAX_OBJ
+ *   MPCT_EINVAL  C < 0 or M < 0
+ *   MPCT_ERANGE  C or M > MPCT_PARETO_MAX_C
+ *   MPCT_ERANGE  n_samples > MPCT_HV_MAX_SAMPLES
+ *   MPCT_EINVAL  n_samples < 1
+ *   MPCT_EINVAL  n_pick < 1
+ *   MPCT_ERANGE  n_pick > MPCT_HVSEL_MAX_PICKS
+ *   MPCT_EINVAL  costs NULL (with M > 0)
+ *   MPCT_EINVAL  members NULL with M != C
+ *   MPCT_EINVAL  lo or ref NULL
+ *   MPCT_EINVAL  out NULL, or all eight of its pointers NULL
+ *   MPCT_EINVAL  (mpct_hv_select only) a value of lo or ref not finite, or lo[j] >= ref[j]
+ *   MPCT_EINVAL  (mpct_hv_select only) an entry of members below -1 or >= C
+ * As for mpct_hypervolume, only the host entry can read the caller's arrays: mpct_hv_select_device writes
+ * hv[r] = NaN for such a box and skips such an entry.  M = 0 is legal: n_picked = 0 and every slot holds
+ * the fill. */
+#define MPCT_HVSEL_MAX_PICKS 1024
+typedef struct mpct_hv_select_result {
+  int64_t* n_picked;      /* [1]  rounds that picked a member                                   */
+  int32_t* pos;           /* [K]  position m_r in members of round r's pick; -1 after the end   */
+  int32_t* index;         /* [K]  members[m_r] (m_r when members is NULL); -1 after the end     */
+  int64_t* gain;          /* [K]  points newly covered by round r's pick; 0 after the end       */
+  int64_t* covered;       /* [K]  gain[0] + .. + gain[r]; stays at its last value after the end */
+  double*  hv;            /* [K]  ((double)covered[r] / (double)N) * vol, vol as in mpct_hypervolume */
+  int32_t* ties;          /* [K]  entries of members that held round r's maximal gain (1 = the pick was forced); 0 after the end */
+  int64_t* n_covered_all; /* [1]  points covered by any entry: mpct_hypervolume's n_covered     */
+} mpct_hv_select_result;
+
+/* All pointers DEVICE pointers, lo, ref and the outputs included; enqueued on `stream` (NULL = default
+ * stream) and NOT synchronised: a fixed sequence of launches that depends on n_pick, n_samples and M only.
+ * Scratch (the per-member gains and one "still uncovered" bit per point, 128 MiB at N = 2^30) comes from
+ * hipMallocAsync / hipFreeAsync on that stream, so calls on different streams are independent. */
+int32_t mpct_hv_select_device(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                              const double* lo, const double* ref, int64_t n_samples, uint64_t seed, int32_t n_pick,
+                              const mpct_hv_select_result* out, void* stream);
+
+/* Host pointers (MATLAB and C callers); needs no scenario.  device: HIP ordinal, -1 = the current device
+ * (an ordinal out of range is MPCT_EINVAL).  Stages on a stream of its own and waits for that stream only;
+ * the calling thread's current device is unchanged on return.  M = 0 needs no device.  Without a device:
+ * MPCT_EDEVICE with a message. */
+int32_t mpct_hv_select(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                       const double* lo, const double* ref, int64_t n_samples, uint64_t seed, int32_t n_pick,
+                       int32_t device, const mpct_hv_select_result* out);
 
 /* ---------------------------------------------------------------------------------------------
  * Closed-loop performance indices per simulation, reduced on the device from the trajectories

@@ -45,6 +45,14 @@
  *                                                    n_samples, volume (scalars), excl and contribution (M x 1:
  *                                                    the points / the volume a member alone covers) and depth_hist
  *                                                    (8 x 1); n_samples (2^20), seed (0) and device (-1) optional
+ *   S = mpct_mex('hv_select', costs, members, lo, ref, n_pick, n_samples, seed, device)
+ *                                                    the n_pick members that carry the front, by greedy selection
+ *                                                    on the coverage count of 'hypervolume's sample points
+ *                                                    (mpct_hv_select; no scenario needed): members as above;
+ *                                                    struct with n_picked, n_covered_all, n_samples, volume
+ *                                                    (scalars) and pos, index (1-BASED, 0 after the end of the
+ *                                                    selection), gain, covered, hv, ties, share (n_pick x 1);
+ *                                                    n_samples (2^20), seed (0) and device (-1) optional
  *   I = mpct_mex('indices', y, u, r, params)         performance indices of stored trajectories (mpct_indices;
  *                                                    no scenario needed): y my x nit x S, u nu x nit x S,
  *                                                    r my x nit x nref; struct with iae, ise, itae, emax, t_emax,
@@ -673,6 +681,81 @@ static void cmd_hypervolume(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = H;
 }
 
+/* S = mpct_mex('hv_select', costs, members, lo, ref, n_pick [, n_samples, seed, device]): the arguments of
+ * 'hypervolume' plus the number of rounds; members, and the outputs pos and index, are 1-BASED (0: a skipped
+ * entry going in, a slot after the end of the selection coming out); the shapes, the box and n_pick are the
+ * library's to judge (its message is surfaced) */
+static void cmd_hv_select(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 6 || nrhs > 9)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: S = mpct_mex('hv_select', costs, members, lo, ref, n_pick [, n_samples, seed, device])");
+  const mxArray* a = prhs[1];
+  if (!a || !mxIsNumeric(a) || mxIsComplex(a) || mxIsSparse(a) || mxGetNumberOfDimensions(a) != 2)
+    mexErrMsgIdAndTxt("mpct:arg", "'costs' must be a real full C x k matrix");
+  const long C = (long)mxGetM(a), k = (long)mxGetN(a);
+  if (k > 1000000) mexErrMsgIdAndTxt("mpct:arg", "'costs' has too many columns");
+  const int all = mxIsEmpty(prhs[2]);
+  const long M = all ? C : (long)mxGetNumberOfElements(prhs[2]);
+  const double np = scalar(prhs[5], "n_pick");
+  if (np != floor(np) || fabs(np) > 1e6) mexErrMsgIdAndTxt("mpct:arg", "'n_pick' must be an integer");
+  const double ns = opt_integer(nrhs, prhs, 6, "n_samples", 1048576.0, -9007199254740992.0, 9007199254740992.0);
+  const double sd = opt_integer(nrhs, prhs, 7, "seed", 0.0, 0.0, 9007199254740992.0);
+  const double dv = opt_integer(nrhs, prhs, 8, "device", -1.0, -1e6, 1e6);
+  double* mm = all ? NULL : doubles(prhs[2], M, "members");
+  int32_t* mem = all ? NULL : (int32_t*)mxMalloc((size_t)(M + 1) * sizeof(int32_t));
+  for (long m = 0; !all && m < M; ++m) {
+    if (mm[m] != floor(mm[m]) || mm[m] < 0.0 || mm[m] > 2147483647.0)
+      mexErrMsgIdAndTxt("mpct:arg", "'members' must hold 1-based row indices (0: skipped)");
+    mem[m] = (int32_t)mm[m] - 1;
+  }
+  double* lo = doubles(prhs[3], k, "lo");
+  double* ref = doubles(prhs[4], k, "ref");
+  double* cm = doubles(a, C * k, "costs");
+  double* rows = (double*)mxMalloc((size_t)(C * k + 1) * sizeof(double));
+  for (long c = 0; c < C; ++c)
+    for (long j = 0; j < k; ++j) rows[c * k + j] = cm[(size_t)j * C + c];
+  const long K = np > 0.0 ? (long)np : 0; /* the slots the library may write: it refuses n_pick < 1 itself */
+  int64_t npicked = 0, nall = 0;
+  mpct_hv_select_result r;
+  r.n_picked = &npicked;
+  r.pos = (int32_t*)mxCalloc((size_t)(K + 1), sizeof(int32_t));
+  r.index = (int32_t*)mxCalloc((size_t)(K + 1), sizeof(int32_t));
+  r.gain = (int64_t*)mxCalloc((size_t)(K + 1), sizeof(int64_t));
+  r.covered = (int64_t*)mxCalloc((size_t)(K + 1), sizeof(int64_t));
+  r.hv = (double*)mxCalloc((size_t)(K + 1), sizeof(double));
+  r.ties = (int32_t*)mxCalloc((size_t)(K + 1), sizeof(int32_t));
+  r.n_covered_all = &nall;
+  if (mpct_hv_select(rows, C, (int32_t)k, mem, M, lo, ref, (int64_t)ns, (uint64_t)sd, (int32_t)np, (int32_t)dv, &r) != MPCT_OK)
+    lib_error("mpct:hv_select");
+  double vol = 1.0;
+  for (long j = 0; j < k; ++j) vol *= ref[j] - lo[j];
+  const char* names[11] = {"n_picked", "pos", "index", "gain", "covered", "hv", "ties", "n_covered_all", "share",
+                           "n_samples", "volume"};
+  mxArray* S = mxCreateStructMatrix(1, 1, 11, names);
+  mxArray* col[7];
+  for (int f = 0; f < 7; ++f) col[f] = mxCreateDoubleMatrix((mwSize)K, 1, mxREAL);
+  for (long q = 0; q < K; ++q) {
+    mxGetPr(col[0])[q] = (double)r.pos[q] + 1.0;   /* 1-based; 0 after the end */
+    mxGetPr(col[1])[q] = (double)r.index[q] + 1.0; /* 1-based; 0 after the end */
+    mxGetPr(col[2])[q] = (double)r.gain[q];
+    mxGetPr(col[3])[q] = (double)r.covered[q];
+    mxGetPr(col[4])[q] = r.hv[q];
+    mxGetPr(col[5])[q] = (double)r.ties[q];
+    mxGetPr(col[6])[q] = (double)r.covered[q] / (double)nall;
+  }
+  mxSetField(S, 0, "n_picked", mxCreateDoubleScalar((double)npicked));
+  mxSetField(S, 0, "pos", col[0]);
+  mxSetField(S, 0, "index", col[1]);
+  mxSetField(S, 0, "gain", col[2]);
+  mxSetField(S, 0, "covered", col[3]);
+  mxSetField(S, 0, "hv", col[4]);
+  mxSetField(S, 0, "ties", col[5]);
+  mxSetField(S, 0, "n_covered_all", mxCreateDoubleScalar((double)nall));
+  mxSetField(S, 0, "share", col[6]);
+  mxSetField(S, 0, "n_samples", mxCreateDoubleScalar(ns));
+  mxSetField(S, 0, "volume", mxCreateDoubleScalar(vol));
+  plhs[0] = S;
+}
+
 /* ---- closed-loop performance indices (mpct_indices, mpct_eval_indices; include/mpct.h) */
 static const char* const kIndexNames[13] = {"iae", "ise", "itae", "emax", "t_emax", "over", "e_final", "settle",
                                             "tv", "du2", "dumax", "u_lo", "u_hi"};
@@ -1027,6 +1110,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_pareto(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "hypervolume")) {
     cmd_hypervolume(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "hv_select")) {
+    cmd_hv_select(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "indices")) {
     cmd_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "eval_indices")) {

@@ -6,10 +6,11 @@
 
 #include <string>
 
+#include "hv_points.h"
+
 namespace mpct {
 
 constexpr long long kHvMaxSamples = 1LL << 30;  // MPCT_HV_MAX_SAMPLES
-constexpr int kHvBlock = 256;                   // threads of a workgroup: one sample point per lane
 constexpr int kHvTile = 128;                    // T: members per LDS tile [K][T]; 256 is the other instance
 constexpr int kHvGridCap = 1 << 20;             // workgroups at most; beyond, they stride over the sample blocks
 constexpr int kHvBins = 8;                      // depth_hist: 0, 1, .., 6 and >= 7

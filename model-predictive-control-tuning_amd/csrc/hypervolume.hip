@@ -14,23 +14,13 @@
 // N, M, k and the grid; nothing waits on another workgroup.
 //
 // Every product is rounded before it is added: contraction is off for this unit (the pragma below and the
-// unit's flags, __graft_entry__.UNIT_FLAGS), so the sample points are restatable in numpy bit for bit.
+// unit's flags, __graft_entry__.UNIT_FLAGS), so the sample points are restatable in numpy bit for bit.  The
+// point generation and the tile staging are hv_points.h's, shared with hv_select.hip.
 #include "hypervolume.h"
 
 #pragma clang fp contract(off)
 
 namespace mpct {
-
-// coordinate j of sample point i in [0, 1): splitmix64's finaliser over the counter 16 i + j + 1
-__device__ __forceinline__ double hv_unit(unsigned long long seed, unsigned long long i, int j) {
-  unsigned long long x = seed + 0x9E3779B97F4A7C15ull * (16ull * i + (unsigned long long)j + 1ull);
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return (double)(x >> 11) * 0x1.0p-53;
-}
 
 template <int K, int T>
 __global__ void __launch_bounds__(kHvBlock)
@@ -40,8 +30,7 @@ __global__ void __launch_bounds__(kHvBlock)
                     unsigned long long* __restrict__ excl) {
   __shared__ __attribute__((aligned(16))) double sA[K * T];
   const int tid = threadIdx.x;
-  const double nan = __longlong_as_double(0x7ff8000000000000ll);
-  for (int e = k * T + tid; e < K * T; e += kHvBlock) sA[e] = 0.0;  // the padded columns, once
+  hv_tile_pad<K, T>(sA, k, tid);
   unsigned long long h[kHvBins];  // this wave's points per depth bin: the same value in every lane
 #pragma unroll
   for (int b = 0; b < kHvBins; ++b) h[b] = 0;
@@ -50,27 +39,10 @@ __global__ void __launch_bounds__(kHvBlock)
     const long long i = blk * kHvBlock + tid;
     const bool active = i < N;
     double p[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      p[j] = 0.0;
-      if (j < k) {
-        const double w = ref[j] - lo[j];
-        const double s = hv_unit(seed, (unsigned long long)i, j) * w;
-        p[j] = active ? lo[j] + s : nan;
-      }
-    }
+    hv_point<K>(p, k, lo, ref, seed, i, active);
     int depth = 0, last = 0;
     for (int t0 = 0; t0 < M; t0 += T) {
-      // entries [t0, t0 + T) gathered through `members` and transposed into [k][T]
-      for (int e = tid; e < T * k; e += kHvBlock) {
-        const int t = e / k, j = e - t * k, m = t0 + t;
-        double v = nan;
-        if (m < M) {
-          const int c = members ? members[m] : m;
-          if (c >= 0 && c < C) v = costs[(size_t)c * k + j];
-        }
-        sA[j * T + t] = v;
-      }
+      hv_stage_tile<T>(sA, costs, C, k, members, M, t0, tid);
       __syncthreads();
 #pragma unroll 4
       for (int t = 0; t < T; ++t) {
@@ -106,13 +78,8 @@ __global__ void hv_finish_kernel(const unsigned long long* __restrict__ counts, 
   if (depth_hist)
     for (int b = 0; b < kHvBins; ++b) depth_hist[b] = (long long)counts[1 + b];
   if (hv) {
-    double vol = 1.0;
     bool box = true;
-    for (int j = 0; j < k; ++j) {
-      const double l = lo[j], r = ref[j];
-      box = box && l - l == 0.0 && r - r == 0.0 && l < r;  // finite and not empty
-      vol *= r - l;
-    }
+    const double vol = hv_box_volume(k, lo, ref, &box);
     hv[0] = box ? ((double)counts[0] / (double)N) * vol : __longlong_as_double(0x7ff8000000000000ll);
   }
 }

@@ -16,6 +16,7 @@
 #include "work_order.h"
 #include "dtc_robust.h"
 #include "pareto.h"
+#include "hv_select.h"
 #include "hypervolume.h"
 #include "traj_indices.h"
 #include "draw_stats.h"
@@ -510,16 +511,29 @@ extern "C" int32_t mpct_pareto(const double* costs, int64_t C, int32_t k, int32_
 
 // ---- Hypervolume of a front and per-member contributions (hypervolume.hip).  The argument checks of both
 // entries, in the order include/mpct.h states, before any device is touched; nothing is dereferenced
-static int hv_check(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M, const double* lo,
-                    const double* ref, int64_t N, const mpct_hv_result* out) {
+// (mpct_hv_select puts its n_pick checks between the sizes and the pointers)
+static int hv_check_sizes(int64_t C, int32_t k, int64_t M, int64_t N) {
   if (k < 1 || k > MPCT_PARETO_MAX_OBJ) return fail(MPCT_EINVAL, "k must be 1 .. MPCT_PARETO_MAX_OBJ");
   if (C < 0 || M < 0) return fail(MPCT_EINVAL, "C < 0 or M < 0");
   if (C > MPCT_PARETO_MAX_C || M > MPCT_PARETO_MAX_C) return fail(MPCT_ERANGE, "C or M exceeds MPCT_PARETO_MAX_C");
   if (N > MPCT_HV_MAX_SAMPLES) return fail(MPCT_ERANGE, "n_samples exceeds MPCT_HV_MAX_SAMPLES");
   if (N < 1) return fail(MPCT_EINVAL, "n_samples < 1");
+  return MPCT_OK;
+}
+
+static int hv_check_inputs(const double* costs, int64_t C, const int32_t* members, int64_t M, const double* lo,
+                           const double* ref) {
   if (M > 0 && !costs) return fail(MPCT_EINVAL, "costs is NULL");
   if (!members && M != C) return fail(MPCT_EINVAL, "members is NULL: M must equal C");
   if (!lo || !ref) return fail(MPCT_EINVAL, "lo or ref is NULL");
+  return MPCT_OK;
+}
+
+static int hv_check(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M, const double* lo,
+                    const double* ref, int64_t N, const mpct_hv_result* out) {
+  int rc = hv_check_sizes(C, k, M, N);
+  if (rc == MPCT_OK) rc = hv_check_inputs(costs, C, members, M, lo, ref);
+  if (rc) return rc;
   if (!out || !(out->n_covered || out->excl || out->depth_hist || out->hv))
     return fail(MPCT_EINVAL, "no output pointer in mpct_hv_result");
   return MPCT_OK;
@@ -621,6 +635,158 @@ extern "C" int32_t mpct_hypervolume(const double* costs, int64_t C, int32_t k, c
     const hipError_t se = hipStreamSynchronize(st);
     if (rc == MPCT_OK && se != hipSuccess)
       rc = fail(MPCT_EDEVICE, std::string("mpct_hypervolume failed on the device: ") + hipGetErrorString(se));
+  }
+  if (blob) (void)hipFree(blob);
+  if (st) (void)hipStreamDestroy(st);
+  if (dev != cur) (void)hipSetDevice(cur);
+  return rc;
+}
+
+// ---- Greedy hypervolume subset selection (hv_select.hip).  The argument checks of both entries, in the
+// order include/mpct.h states, before any device is touched; nothing is dereferenced
+static int hvsel_check(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M, const double* lo,
+                       const double* ref, int64_t N, int32_t n_pick, const mpct_hv_select_result* out) {
+  int rc = hv_check_sizes(C, k, M, N);
+  if (rc) return rc;
+  if (n_pick < 1) return fail(MPCT_EINVAL, "n_pick < 1");
+  if (n_pick > MPCT_HVSEL_MAX_PICKS) return fail(MPCT_ERANGE, "n_pick exceeds MPCT_HVSEL_MAX_PICKS");
+  rc = hv_check_inputs(costs, C, members, M, lo, ref);
+  if (rc) return rc;
+  if (!out || !(out->n_picked || out->pos || out->index || out->gain || out->covered || out->hv || out->ties ||
+                out->n_covered_all))
+    return fail(MPCT_EINVAL, "no output pointer in mpct_hv_select_result");
+  return MPCT_OK;
+}
+
+// tile length (128 or 256; 0: the default) and the largest grid in workgroups (0: the default) of
+// hvsel_gain_kernel, as mpct_internal_hv_tuned; and the tools' round timing (a host array of n floats that the
+// NEXT call alone fills, waiting for its stream, when its n_pick <= n; NULL: off).  Test and tool hooks, not
+// part of include/mpct.h
+static int32_t g_hvsel_tile = 0, g_hvsel_blocks = 0;
+static float* g_hvsel_round_ms = nullptr;
+static int32_t g_hvsel_round_n = 0;
+extern "C" int32_t mpct_internal_hvsel_tuned(int32_t tile, int32_t max_blocks) {
+  if ((tile != 0 && tile != 128 && tile != 256) || max_blocks < 0) return fail(MPCT_EINVAL, "tile must be 0, 128 or 256, max_blocks >= 0");
+  g_hvsel_tile = tile;
+  g_hvsel_blocks = max_blocks;
+  return MPCT_OK;
+}
+extern "C" int32_t mpct_internal_hvsel_round_ms(float* ms, int32_t n) {
+  if (ms && n < 1) return fail(MPCT_EINVAL, "the round-time array needs n >= 1");
+  g_hvsel_round_ms = ms;
+  g_hvsel_round_n = ms ? n : 0;
+  return MPCT_OK;
+}
+
+static int32_t hvsel_launch(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M, const double* lo,
+                            const double* ref, int64_t N, uint64_t seed, int32_t n_pick, const mpct_hv_select_result* out,
+                            hipStream_t stream) {
+  std::string err;
+  const HvSelOut so{reinterpret_cast<long long*>(out->n_picked), out->pos, out->index, reinterpret_cast<long long*>(out->gain),
+                    reinterpret_cast<long long*>(out->covered), out->hv, out->ties,
+                    reinterpret_cast<long long*>(out->n_covered_all)};
+  float* round_ms = n_pick <= g_hvsel_round_n ? g_hvsel_round_ms : nullptr;  // never past the tool's array
+  g_hvsel_round_ms = nullptr;                                                // one call only
+  g_hvsel_round_n = 0;
+  const int rc = hv_select_device(costs, C, k, members, M, lo, ref, N, seed, n_pick, so, stream, &err, g_hvsel_tile,
+                                  g_hvsel_blocks, round_ms);
+  if (rc) return fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err);
+  return MPCT_OK;
+}
+
+extern "C" int32_t mpct_hv_select_device(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                                         const double* lo, const double* ref, int64_t n_samples, uint64_t seed,
+                                         int32_t n_pick, const mpct_hv_select_result* out, void* stream) {
+  const int rc = hvsel_check(costs, C, k, members, M, lo, ref, n_samples, n_pick, out);
+  if (rc) return rc;
+  return hvsel_launch(costs, C, k, members, M, lo, ref, n_samples, seed, n_pick, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_hv_select(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                                  const double* lo, const double* ref, int64_t n_samples, uint64_t seed, int32_t n_pick,
+                                  int32_t device, const mpct_hv_select_result* out) {
+  int rc = hvsel_check(costs, C, k, members, M, lo, ref, n_samples, n_pick, out);
+  if (rc) return rc;
+  double vol = 1.0;
+  for (int j = 0; j < k; ++j) {
+    if (!std::isfinite(lo[j]) || !std::isfinite(ref[j]) || !(lo[j] < ref[j]))
+      return fail(MPCT_EINVAL, "the box needs finite lo and ref with lo[j] < ref[j]");
+    vol *= ref[j] - lo[j];
+  }
+  for (int64_t m = 0; members && m < M; ++m)
+    if (members[m] < -1 || members[m] >= C) return fail(MPCT_EINVAL, "an entry of members is below -1 or >= C");
+  if (M == 0) {  // nothing to stage: the end-of-selection fill from slot 0
+    if (out->n_picked) out->n_picked[0] = 0;
+    if (out->n_covered_all) out->n_covered_all[0] = 0;
+    for (int r = 0; r < n_pick; ++r) {
+      if (out->pos) out->pos[r] = -1;
+      if (out->index) out->index[r] = -1;
+      if (out->gain) out->gain[r] = 0;
+      if (out->covered) out->covered[r] = 0;
+      if (out->hv) out->hv[r] = (0.0 / (double)n_samples) * vol;
+      if (out->ties) out->ties[r] = 0;
+    }
+    return MPCT_OK;
+  }
+  int cur = -1, cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
+    return fail(MPCT_EDEVICE, "no HIP device (mpct_hv_select needs a GPU)");
+  const int dev = device < 0 ? cur : device;
+  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
+  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
+  // one blob: costs | members | lo | ref | pos, index, ties (int32 [K]) | gain, covered, hv (8 B [K]) |
+  // n_picked, n_covered_all; each 256-B aligned; a stream of this call's own
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t nc = al((size_t)C * k * sizeof(double)), nm = al((size_t)M * sizeof(int32_t)), nb = al((size_t)k * sizeof(double)),
+               n4 = al((size_t)n_pick * sizeof(int32_t)), n8 = al((size_t)n_pick * sizeof(int64_t));
+  hipStream_t st = nullptr;
+  char* blob = nullptr;
+  rc = MPCT_OK;
+  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
+  } else if (hipMalloc(reinterpret_cast<void**>(&blob), nc + nm + 2 * nb + 3 * n4 + 3 * n8 + 2 * 256) != hipSuccess) {
+    rc = fail(MPCT_ENOMEM, "hipMalloc failed (hv_select staging)");
+  } else {
+    double* dcosts = reinterpret_cast<double*>(blob);
+    int32_t* dmem = members ? reinterpret_cast<int32_t*>(blob + nc) : nullptr;
+    double* dlo = reinterpret_cast<double*>(blob + nc + nm);
+    double* dref = reinterpret_cast<double*>(blob + nc + nm + nb);
+    char* res = blob + nc + nm + 2 * nb;
+    mpct_hv_select_result d{};
+    d.pos = out->pos ? reinterpret_cast<int32_t*>(res) : nullptr;
+    d.index = out->index ? reinterpret_cast<int32_t*>(res + n4) : nullptr;
+    d.ties = out->ties ? reinterpret_cast<int32_t*>(res + 2 * n4) : nullptr;
+    d.gain = out->gain ? reinterpret_cast<int64_t*>(res + 3 * n4) : nullptr;
+    d.covered = out->covered ? reinterpret_cast<int64_t*>(res + 3 * n4 + n8) : nullptr;
+    d.hv = out->hv ? reinterpret_cast<double*>(res + 3 * n4 + 2 * n8) : nullptr;
+    d.n_picked = out->n_picked ? reinterpret_cast<int64_t*>(res + 3 * n4 + 3 * n8) : nullptr;
+    d.n_covered_all = out->n_covered_all ? reinterpret_cast<int64_t*>(res + 3 * n4 + 3 * n8 + 256) : nullptr;
+    bool ok = hipMemcpyAsync(dcosts, costs, (size_t)C * k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
+              (!dmem || hipMemcpyAsync(dmem, members, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, st) == hipSuccess) &&
+              hipMemcpyAsync(dlo, lo, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(dref, ref, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hv_select inputs)");
+    if (ok) {
+      rc = hvsel_launch(dcosts, C, k, dmem, M, dlo, dref, n_samples, seed, n_pick, &d, st);
+      ok = rc == MPCT_OK;
+    }
+    if (ok) {
+      const size_t b4 = (size_t)n_pick * sizeof(int32_t), b8 = (size_t)n_pick * sizeof(int64_t);
+      ok = (!d.pos || hipMemcpyAsync(out->pos, d.pos, b4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.index || hipMemcpyAsync(out->index, d.index, b4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.ties || hipMemcpyAsync(out->ties, d.ties, b4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.gain || hipMemcpyAsync(out->gain, d.gain, b8, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.covered || hipMemcpyAsync(out->covered, d.covered, b8, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.hv || hipMemcpyAsync(out->hv, d.hv, b8, hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.n_picked || hipMemcpyAsync(out->n_picked, d.n_picked, sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.n_covered_all ||
+            hipMemcpyAsync(out->n_covered_all, d.n_covered_all, sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess);
+      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hv_select results)");
+    }
+    // this call's stream only, also after an error: the blob is freed below
+    const hipError_t se = hipStreamSynchronize(st);
+    if (rc == MPCT_OK && se != hipSuccess)
+      rc = fail(MPCT_EDEVICE, std::string("mpct_hv_select failed on the device: ") + hipGetErrorString(se));
   }
   if (blob) (void)hipFree(blob);
   if (st) (void)hipStreamDestroy(st);

@@ -94,6 +94,11 @@ class MpctHvResult(C.Structure):
     _fields_ = [("n_covered", c_int64_p), ("excl", c_int64_p), ("depth_hist", c_int64_p), ("hv", c_double_p)]
 
 
+class MpctHvSelectResult(C.Structure):
+    _fields_ = [("n_picked", c_int64_p), ("pos", c_int32_p), ("index", c_int32_p), ("gain", c_int64_p),
+                ("covered", c_int64_p), ("hv", c_double_p), ("ties", c_int32_p), ("n_covered_all", c_int64_p)]
+
+
 class MpctIndexParams(C.Structure):
     _fields_ = [("t0", C.c_int32), ("band_rel", C.c_double), ("band_abs", C.c_double)]
 
@@ -132,13 +137,14 @@ EXPORTS = [
     "mpct_eval_robust_tail_device", "mpct_pareto_device", "mpct_pareto",
     "mpct_indices_device", "mpct_indices", "mpct_eval_indices", "mpct_eval_indices_device",
     "mpct_draw_stats_device", "mpct_draw_stats", "mpct_eval_robust_indices", "mpct_eval_robust_indices_device",
-    "mpct_hypervolume_device", "mpct_hypervolume",
+    "mpct_hypervolume_device", "mpct_hypervolume", "mpct_hv_select_device", "mpct_hv_select",
 ]
 
 ABI_VERSION = 7
 TAIL_MAX_LEVELS, TAIL_MAX_DRAWS = 8, 4096
 PARETO_MAX_OBJ, PARETO_MAX_C, PARETO_MAX_LAYERS = 16, 1048576, 64
 HV_MAX_SAMPLES, HV_BINS = 1073741824, 8
+HVSEL_MAX_PICKS = 1024
 INDEX_MAX_ROWS, INDEX_SCRATCH_BYTES = 2147483647, 268435456
 STAT_F64, STAT_I32 = 0, 1
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
@@ -245,6 +251,16 @@ def load():
     # the tile length (0, 128, 256) and the largest grid (0: the default) of hv_count_kernel: a test / bench hook
     lib.mpct_internal_hv_tuned.argtypes = [C.c_int32, C.c_int32]
     lib.mpct_internal_hv_tuned.restype = C.c_int32
+    lib.mpct_hv_select_device.argtypes = hv_args + [C.c_int32, C.POINTER(MpctHvSelectResult), C.c_void_p]
+    lib.mpct_hv_select_device.restype = C.c_int32
+    lib.mpct_hv_select.argtypes = hv_args + [C.c_int32, C.c_int32, C.POINTER(MpctHvSelectResult)]
+    lib.mpct_hv_select.restype = C.c_int32
+    # the tile length and the largest grid of hvsel_gain_kernel, and the per-round event times of the next
+    # call alone (a host float array and its length, at least n_pick; None: off): test / tool hooks
+    lib.mpct_internal_hvsel_tuned.argtypes = [C.c_int32, C.c_int32]
+    lib.mpct_internal_hvsel_tuned.restype = C.c_int32
+    lib.mpct_internal_hvsel_round_ms.argtypes = [C.c_void_p, C.c_int32]
+    lib.mpct_internal_hvsel_round_ms.restype = C.c_int32
     index_args = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                   C.POINTER(MpctIndexParams)]
     lib.mpct_indices_device.argtypes = index_args + [C.POINTER(MpctIndexResult), C.c_void_p]

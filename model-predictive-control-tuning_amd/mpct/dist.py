@@ -293,6 +293,107 @@ def hypervolume_candidates(costs: torch.Tensor, front=None, lo=None, ref=None, n
     return dict(hv=hv, n_covered=n_cov, n_samples=int(n_samples), excl=excl, depth_hist=hist, lo=lo, ref=ref)
 
 
+def _hv_select_torch(costs: torch.Tensor, members, lo: torch.Tensor, ref: torch.Tensor, n_samples: int, seed: int,
+                     n_pick: int, chunk: int = 4096, mchunk: int = 2048) -> dict:
+    """The contract of mpct_hv_select_device (include/mpct.h) as chunked torch expressions in int64 arithmetic,
+    on the tensor's device: the CPU path of hv_select_candidates, and what tools/hv_select_bench.py times the
+    kernels against.  Every round regenerates the points chunk by chunk; the "still uncovered" bits stay."""
+    Cn, k = costs.shape
+    dev = costs.device
+    mem = torch.arange(Cn, dtype=torch.int64, device=dev) if members is None else members.to(torch.int64)
+    M = mem.numel()
+    pos = torch.nonzero((mem >= 0) & (mem < Cn)).flatten()      # an entry outside [0, C) is skipped
+    A = costs[mem[pos]]                                         # a NaN row covers nothing
+    alive = torch.ones(n_samples, dtype=torch.bool, device=dev)
+    out = dict(pos=torch.full((n_pick,), -1, dtype=torch.int32, device=dev),
+               index=torch.full((n_pick,), -1, dtype=torch.int32, device=dev),
+               gain=torch.zeros(n_pick, dtype=torch.int64, device=dev),
+               covered=torch.zeros(n_pick, dtype=torch.int64, device=dev),
+               ties=torch.zeros(n_pick, dtype=torch.int32, device=dev))
+    n_picked, covered, n_all, row = 0, 0, 0, None
+    for r in range(n_pick if pos.numel() else 0):
+        gains = torch.zeros(M, dtype=torch.int64, device=dev)
+        for i0 in range(0, n_samples, chunk):
+            i1 = min(n_samples, i0 + chunk)
+            P = _hv_points(lo, ref, seed, i0, i1)
+            if row is not None:
+                alive[i0:i1] &= ~(row[None, :] <= P).all(dim=1)
+            live = alive[i0:i1]
+            if not bool(live.any()):
+                continue
+            anyc = torch.zeros(i1 - i0, dtype=torch.bool, device=dev)
+            for m0 in range(0, A.shape[0], mchunk):
+                le = (A[None, m0:m0 + mchunk, :] <= P[:, None, :]).all(dim=2)
+                anyc |= le.any(dim=1)
+                gains[pos[m0:m0 + mchunk]] += (le & live[:, None]).sum(dim=0)
+            if r == 0:                                          # a point that nothing covers never counts again
+                alive[i0:i1] &= anyc
+        if r == 0:
+            n_all = int(alive.sum().item())
+        best = int(gains.max().item())
+        if best == 0:
+            break
+        m = int(torch.nonzero(gains == best).flatten()[0].item())
+        covered += best
+        n_picked = r + 1
+        row = costs[int(mem[m].item())]
+        out["pos"][r], out["index"][r], out["gain"][r] = m, int(mem[m].item()), best
+        out["covered"][r], out["ties"][r] = covered, int((gains == best).sum().item())
+    out["covered"][n_picked:] = covered
+    vol = 1.0
+    for l, h in zip(lo.tolist(), ref.tolist()):
+        vol *= h - l
+    out["hv"] = (out["covered"].to(torch.float64) / float(n_samples)) * vol
+    out.update(n_picked=n_picked, n_covered_all=n_all)
+    return out
+
+
+def hv_select_candidates(costs: torch.Tensor, n_pick: int, front=None, lo=None, ref=None, n_samples: int = 1 << 20,
+                         seed: int = 0, C: int | None = None) -> dict:
+    """The ``n_pick`` members of ``front`` (indices into the gathered cost records, e.g. pareto_candidates' front;
+    -1 entries are skipped; None: every record) that carry it, by greedy forward selection on the coverage
+    count (contract: mpct_hv_select_device in include/mpct.h).  Returns a dict: n_picked, n_covered_all, n_samples
+    (int); pos, index, ties [n_pick] int32, gain, covered [n_pick] int64 and hv [n_pick] float64 on the costs'
+    device, lo and ref [k] there too.  Identical on every rank, as hypervolume_candidates.  GPU tensors go
+    through mpct_hv_select_device on the current stream; CPU tensors (the gloo tests) through chunked torch
+    expressions."""
+    from . import engine
+
+    if C is not None:
+        costs = costs[:C]
+    if costs.dim() == 1:
+        costs = costs[:, None]
+    c = costs.to(torch.float64).contiguous()
+    n, k = c.shape
+    if not 1 <= k <= 16:
+        raise ValueError("k must be 1 .. 16")
+    if not 1 <= int(n_samples) <= 1 << 30:
+        raise ValueError("n_samples must be 1 .. 2**30")
+    if not 1 <= int(n_pick) <= 1024:
+        raise ValueError("n_pick must be 1 .. 1024")
+    n_pick = int(n_pick)
+    mem = None if front is None else torch.as_tensor(front).to(device=c.device, dtype=torch.int32).contiguous().flatten()
+    if lo is None or ref is None or not torch.is_tensor(lo) or not torch.is_tensor(ref):
+        lo, ref = engine.default_box(c.cpu().numpy(), None if mem is None else mem.cpu().numpy(),
+                                     lo.cpu().numpy() if torch.is_tensor(lo) else lo,
+                                     ref.cpu().numpy() if torch.is_tensor(ref) else ref)
+    lo = torch.as_tensor(lo, dtype=torch.float64).to(c.device).contiguous()
+    ref = torch.as_tensor(ref, dtype=torch.float64).to(c.device).contiguous()
+    if not (bool(torch.isfinite(lo).all()) and bool(torch.isfinite(ref).all()) and bool((lo < ref).all())):
+        raise ValueError("the box needs finite lo and ref with lo < ref")
+    if c.is_cuda:
+        i32 = lambda: torch.empty(n_pick, dtype=torch.int32, device=c.device)
+        i64 = lambda m: torch.empty(m, dtype=torch.int64, device=c.device)
+        out = dict(n_picked=i64(1), pos=i32(), index=i32(), gain=i64(n_pick), covered=i64(n_pick),
+                   hv=torch.empty(n_pick, dtype=torch.float64, device=c.device), ties=i32(), n_covered_all=i64(1))
+        engine.hv_select_device(c, n_pick, out, lo, ref, members=mem, n_samples=n_samples, seed=seed)
+        out["n_picked"], out["n_covered_all"] = int(out["n_picked"].item()), int(out["n_covered_all"].item())
+    else:
+        out = _hv_select_torch(c, mem, lo, ref, int(n_samples), int(seed), n_pick)
+    out.update(n_samples=int(n_samples), lo=lo, ref=ref)
+    return out
+
+
 # measured one-GPU time of every config-3 cell alone (tools/shard_balance.py --cells): the (N2, Nu)
 # cells of mpct.scenarios.config3_grid with 1024 lambda draws each, whole and in two halves
 CELL_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "config3_cells.json")

@@ -8,6 +8,8 @@
   pareto_device       mpct_pareto_device (torch CUDA tensors, enqueued on the current stream)
   hypervolume         mpct_hypervolume: Monte-Carlo hypervolume of a front in a box, per-member contributions
   hypervolume_device  mpct_hypervolume_device (torch CUDA tensors, enqueued on the current stream)
+  hv_select           mpct_hv_select: the n members that carry a front, by greedy selection on the coverage count
+  hv_select_device    mpct_hv_select_device (torch CUDA tensors, enqueued on the current stream)
   indices             mpct_indices: performance indices (IAE, overshoot, settling, valve travel ..) of trajectories
   indices_device      mpct_indices_device (torch CUDA tensors, enqueued on the current stream)
   eval_indices        mpct_eval_indices: score a batch and return only its index records
@@ -419,6 +421,12 @@ class RobustResult:
         costs = self._cost_table(stat, max_failed, columns)
         return pareto(costs, device=device).hypervolume(costs, device=device, **kw)
 
+    def select(self, n_pick: int, stat: str = "worst", max_failed: int = 0, columns=(), device: int = -1, **kw):
+        """``ParetoResult.select`` on the front of the cost table ``pareto`` analyses: the candidate indices of the
+        ``n_pick`` members that carry it, in pick order; ``kw`` are hv_select's lo, ref, n_samples and seed."""
+        costs = self._cost_table(stat, max_failed, columns)
+        return pareto(costs, device=device).select(costs, n_pick, device=device, **kw)
+
     def _cost_table(self, stat, max_failed, columns):
         cols = [self.scores(max_failed, stat)]
         for name, j in columns:
@@ -543,6 +551,11 @@ class ParetoResult:
     def hypervolume(self, costs, **kw):
         """``hypervolume`` of this front: ``costs`` is the table the front was computed from."""
         return hypervolume(costs, members=self.front, **kw)
+
+    def select(self, costs, n_pick: int, **kw):
+        """The candidate indices of the ``n_pick`` members that carry this front (fewer when the selection ends
+        early), in pick order: ``hv_select`` over the front; ``costs`` is the table the front was computed from."""
+        return hv_select(costs, n_pick, members=self.front, **kw).picked
 
 
 def _pareto_costs(costs):
@@ -696,6 +709,105 @@ def hypervolume_device(costs, out: dict, lo, ref, members=None, n_samples: int =
                                                  int(seed) & (2 ** 64 - 1), C.byref(r), C.c_void_p(stream))
     if rc != 0:
         raise MpctError("mpct_hypervolume_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+# --------------------------------------------------------------------------------------------
+# Greedy hypervolume subset selection (mpct_hv_select, include/mpct.h)
+HVSEL_FIELDS = ("n_picked", "pos", "index", "gain", "covered", "hv", "ties", "n_covered_all")
+
+
+@dataclass
+class HvSelectResult:
+    """Greedy forward selection on the coverage count of ``hypervolume``'s sample points: round r picks the
+    member that covers the most points no earlier pick covers.  The arrays hold ``n_pick`` slots; the slots
+    from ``n_picked`` on hold the end-of-selection fill (pos, index -1; gain, ties 0)."""
+    n_picked: int                   # rounds that picked a member
+    pos: np.ndarray                 # (K,) int32 position in members of round r's pick
+    index: np.ndarray               # (K,) int32 the candidate, members[pos]
+    gain: np.ndarray                # (K,) int64 points newly covered by round r's pick
+    covered: np.ndarray             # (K,) int64 running sum of gain
+    hv: np.ndarray                  # (K,) covered / n_samples * volume
+    ties: np.ndarray                # (K,) int32 entries that held round r's largest gain; 1: the pick was forced
+    n_covered_all: int              # points covered by any member: hypervolume's n_covered
+    n_samples: int
+    lo: np.ndarray                  # (k,) the box
+    ref: np.ndarray
+    volume: float
+
+    @property
+    def picked(self) -> np.ndarray:
+        """(n_picked,) the picked candidates in pick order"""
+        return self.index[:self.n_picked]
+
+    @property
+    def share(self) -> np.ndarray:
+        """(K,) covered / n_covered_all: the part of the front's coverage the first r + 1 picks hold"""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.covered / np.float64(self.n_covered_all)
+
+    def cut(self, name: str) -> np.ndarray:
+        """the array ``name`` cut to n_picked"""
+        return getattr(self, name)[:self.n_picked]
+
+
+def hv_select(costs, n_pick: int, members=None, lo=None, ref=None, n_samples: int = 1 << 20, seed: int = 0,
+              device: int = -1) -> HvSelectResult:
+    """mpct_hv_select: ``n_pick`` rounds of greedy forward selection among the rows ``members`` of the (C, k) cost
+    table (None: all rows; -1 entries are skipped) on the coverage count of ``hypervolume``'s sample points in
+    the box [lo, ref] (None: ``default_box``), on the GPU."""
+    a = _pareto_costs(costs)
+    Cn, k = a.shape
+    mem = None if members is None else np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+    M = Cn if mem is None else mem.size
+    lo, ref = default_box(a, mem, lo, ref)
+    K = max(int(n_pick), 0)
+    i32 = {f: np.zeros(K, dtype=np.int32) for f in ("pos", "index", "ties")}
+    i64 = {f: np.zeros(K, dtype=np.int64) for f in ("gain", "covered")}
+    hv = np.zeros(K, dtype=np.float64)
+    npk, nall = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    p64 = lambda x: x.ctypes.data_as(_lib.c_int64_p)
+    r = _lib.MpctHvSelectResult(p64(npk), _ip(i32["pos"]), _ip(i32["index"]), p64(i64["gain"]), p64(i64["covered"]),
+                                _dp(hv), _ip(i32["ties"]), p64(nall))
+    rc = _lib.load().mpct_hv_select(a.ctypes.data, Cn, k, mem.ctypes.data if mem is not None else None, M,
+                                    lo.ctypes.data, ref.ctypes.data, int(n_samples), int(seed) & (2 ** 64 - 1),
+                                    int(n_pick), int(device), C.byref(r))
+    if rc != 0:
+        raise MpctError("mpct_hv_select failed (%d): %s" % (rc, _lib.last_error()))
+    return HvSelectResult(n_picked=int(npk[0]), pos=i32["pos"], index=i32["index"], gain=i64["gain"],
+                          covered=i64["covered"], hv=hv, ties=i32["ties"], n_covered_all=int(nall[0]),
+                          n_samples=int(n_samples), lo=lo, ref=ref, volume=box_volume(lo, ref))
+
+
+def hv_select_device(costs, n_pick: int, out: dict, lo, ref, members=None, n_samples: int = 1 << 20, seed: int = 0):
+    """mpct_hv_select_device: tensors as for ``hypervolume_device``.  The results are written into the tensors of
+    ``out`` (keys n_picked, n_covered_all [1], gain, covered [n_pick]: int64; pos, index, ties [n_pick]: int32;
+    hv [n_pick]: float64; any may be absent).  Enqueued on the current torch stream of the tensor's device and
+    not synchronised."""
+    import torch
+
+    if costs.dtype != torch.float64 or costs.dim() != 2 or not costs.is_contiguous():
+        raise ValueError("costs must be a contiguous float64 tensor [C, k]")
+    k = costs.shape[1]
+    for name, t in (("lo", lo), ("ref", ref)):
+        if t.dtype != torch.float64 or t.shape != (k,) or not t.is_contiguous() or t.device != costs.device:
+            raise ValueError("%s must be a contiguous float64 tensor [k] on the costs' device" % name)
+    if members is not None and (members.dtype != torch.int32 or members.dim() != 1 or not members.is_contiguous()
+                                or members.device != costs.device):
+        raise ValueError("members must be a contiguous int32 tensor [M] on the costs' device")
+    M = costs.shape[0] if members is None else members.shape[0]
+    for f in ("pos", "index", "gain", "covered", "hv", "ties"):
+        if out.get(f) is not None and out[f].numel() < int(n_pick):
+            raise ValueError("out[%r] holds fewer than n_pick entries" % f)
+    ctype = dict(pos=_lib.c_int32_p, index=_lib.c_int32_p, ties=_lib.c_int32_p, hv=_lib.c_double_p)
+    r = _lib.MpctHvSelectResult(*[_tptr(out.get(f), ctype.get(f, _lib.c_int64_p)) for f in HVSEL_FIELDS])
+    stream = torch.cuda.current_stream(costs.device).cuda_stream
+    with torch.cuda.device(costs.device):
+        rc = _lib.load().mpct_hv_select_device(C.c_void_p(costs.data_ptr()), costs.shape[0], k,
+                                               C.c_void_p(members.data_ptr()) if members is not None else None, M,
+                                               C.c_void_p(lo.data_ptr()), C.c_void_p(ref.data_ptr()), int(n_samples),
+                                               int(seed) & (2 ** 64 - 1), int(n_pick), C.byref(r), C.c_void_p(stream))
+    if rc != 0:
+        raise MpctError("mpct_hv_select_device failed (%d): %s" % (rc, _lib.last_error()))
 
 
 # --------------------------------------------------------------------------------------------
@@ -1031,6 +1143,12 @@ class RobustIndexResult:
         n_samples and seed."""
         costs = self.costs(stat, names, max_failed)
         return pareto(costs, device=device).hypervolume(costs, device=device, **kw)
+
+    def select(self, n_pick: int, stat="hi", names=None, max_failed: int = 0, device: int = -1, **kw):
+        """``ParetoResult.select`` on the front of the table ``costs`` returns; ``kw`` are hv_select's lo, ref,
+        n_samples and seed."""
+        costs = self.costs(stat, names, max_failed)
+        return pareto(costs, device=device).select(costs, n_pick, device=device, **kw)
 
 
 def _field_ids(sc, fields):
