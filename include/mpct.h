@@ -32,7 +32,8 @@
  *     mpct_eval_robust_indices, mpct_eval_robust_indices_device), and the hypervolume of a front with its
  *     members' exclusive contributions (mpct_hv_result, mpct_hypervolume_device, mpct_hypervolume), and
  *     the greedy selection of the members that carry a front (mpct_hv_select_result,
- *     mpct_hv_select_device, mpct_hv_select).
+ *     mpct_hv_select_device, mpct_hv_select), and the exact hypervolume and contributions for up to three
+ *     objectives (mpct_hvx_result, mpct_hypervolume_exact_device, mpct_hypervolume_exact).
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -736,6 +737,74 @@ int32_t mpct_hv_select_device(const double* costs, int64_t C, int32_t k, const i
 int32_t mpct_hv_select(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
                        const double* lo, const double* ref, int64_t n_samples, uint64_t seed, int32_t n_pick,
                        int32_t device, const mpct_hv_select_result* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Exact hypervolume and exclusive contributions for at most three objectives, on the device
+ * (hypervolume_exact.hip).  mpct_hypervolume's estimate has a standard error of about 1e-3 of
+ * the box at 2^20 points and reads every contribution below 1/N of the box as 0.  For k <= 3 a sweep gives
+ * the volume and every contribution with rounding error only, in O(M^2) work and with no sample count.
+ *
+ * costs, C, members, M, lo and ref are mpct_hypervolume's: costs is [C][k] row-major, members NULL means
+ * candidates 0 .. C-1 with M = C, an entry -1 is SKIPPED (the -1-padded front of mpct_pareto goes in as it
+ * is with M = C), a duplicated index is a separate entry, and an entry outside [0, C) is MPCT_EINVAL for
+ * mpct_hypervolume_exact and skipped by mpct_hypervolume_exact_device.  1 <= k <= MPCT_HVX_MAX_OBJ,
+ * 0 <= C <= MPCT_PARETO_MAX_C, 0 <= M <= MPCT_HVX_MAX_M.
+ *
+ * An entry whose row holds a NaN is INACTIVE.  Every other entry a is clipped to the box, b_j = max(a_j, lo_j)
+ * (-INFINITY clips to lo_j; -0.0 equals +0.0), and is inactive when b_j >= ref_j for some j (+INFINITY, or a
+ * member on or past a reference face).  Every other entry is ACTIVE and owns the box [b, ref).
+ *
+ *   hv[0]        the Lebesgue measure of the union of the active boxes: what mpct_hypervolume estimates
+ *   excl[m]      the measure of the part of entry m's box that lies in no other active entry's box; +0.0 for
+ *                an inactive entry and for each of two entries with equal clipped vectors
+ *   n_active[0]  the number of active entries
+ * Any of the three pointers may be NULL, not all of them.  M = 0, or no active entry: hv = +0.0, n_active = 0.
+ *
+ * ARITHMETIC, part of the contract.  IEEE doubles, every operation rounded (no fused multiply-add).  Every term
+ * that enters a sum is a product of non-negative differences of clipped coordinates; no volume is obtained by
+ * subtraction.  With T = M*M + 8, vol the box volume of mpct_hypervolume and HV, EXCL_m the values in exact
+ * arithmetic on the doubles given:  |hv - HV| <= T * 2^-53 * vol  and  |excl[m] - EXCL_m| <= T * 2^-53 * vol.
+ * excl[m] is exactly +0.0 where EXCL_m is 0.  Where every difference, product and partial sum is representable
+ * (small integer coordinates, scaled by a power of two or not) every result is exact.  A repeated call is bitwise
+ * identical; no result depends on C, on where the rows sit in costs, or on the launch geometry; a permutation
+ * of members permutes excl bitwise and leaves hv and n_active bitwise unchanged (the order of every sum is a
+ * function of the sorted clipped values alone).
+ *
+ * Argument errors, in this order and before any device is touched:
+ *   MPCT_EINVAL  k < 1
+ *   MPCT_ERANGE  k > MPCT_HVX_MAX_OBJ
+ *   MPCT_EINVAL  C < 0 or M < 0
+ *   MPCT_ERANGE  C > MPCT_PARETO_MAX_C
+ *   MPCT_ERANGE  M > MPCT_HVX_MAX_M
+ *   MPCT_EINVAL  costs NULL (with M > 0)
+ *   MPCT_EINVAL  members NULL with M != C
+ *   MPCT_EINVAL  lo or ref NULL
+ *   MPCT_EINVAL  out NULL, or all three of its pointers NULL
+ *   MPCT_EINVAL  (mpct_hypervolume_exact only) a value of lo or ref not finite, or lo[j] >= ref[j]
+ *   MPCT_EINVAL  (mpct_hypervolume_exact only) an entry of members below -1 or >= C
+ * The last two read the caller's arrays, which only the host entry can do: mpct_hypervolume_exact_device
+ * writes hv = NaN and excl = NaN for such a box (n_active = 0) and skips such an entry. */
+#define MPCT_HVX_MAX_OBJ 3
+#define MPCT_HVX_MAX_M   65536
+typedef struct mpct_hvx_result {
+  double*  hv;        /* [1] volume of the box dominated by any member            */
+  double*  excl;      /* [M] volume dominated by members[m] and by no other entry */
+  int64_t* n_active;  /* [1] entries whose clipped box has positive volume        */
+} mpct_hvx_result;
+
+/* All pointers DEVICE pointers, lo, ref and the outputs included; enqueued on `stream` (NULL = default
+ * stream) and NOT synchronised: a fixed sequence of launches that depends on M and k only.  Scratch (at most
+ * 256 * M * 8 bytes, 128 MiB at M = MPCT_HVX_MAX_M) comes from hipMallocAsync / hipFreeAsync on that stream,
+ * so calls on different streams are independent. */
+int32_t mpct_hypervolume_exact_device(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                                      const double* lo, const double* ref, const mpct_hvx_result* out, void* stream);
+
+/* Host pointers (MATLAB and C callers); needs no scenario.  device: HIP ordinal, -1 = the current device
+ * (an ordinal out of range is MPCT_EINVAL).  Stages on a stream of its own and waits for that stream only;
+ * the calling thread's current device is unchanged on return.  M = 0 needs no device.  Without a device:
+ * MPCT_EDEVICE with a message. */
+int32_t mpct_hypervolume_exact(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                               const double* lo, const double* ref, int32_t device, const mpct_hvx_result* out);
 
 /* ---------------------------------------------------------------------------------------------
  * Closed-loop performance indices per simulation, reduced on the device from the trajectories

@@ -53,6 +53,12 @@
  *                                                    (scalars) and pos, index (1-BASED, 0 after the end of the
  *                                                    selection), gain, covered, hv, ties, share (n_pick x 1);
  *                                                    n_samples (2^20), seed (0) and device (-1) optional
+ *   X = mpct_mex('hypervolume_exact', costs, members, lo, ref, device)
+ *                                                    exact hypervolume and exclusive contributions for at most
+ *                                                    three columns (mpct_hypervolume_exact; no scenario needed):
+ *                                                    members as above; struct with hv, n_active (scalars) and
+ *                                                    excl (M x 1, the volume a member alone dominates); device
+ *                                                    (-1) optional
  *   I = mpct_mex('indices', y, u, r, params)         performance indices of stored trajectories (mpct_indices;
  *                                                    no scenario needed): y my x nit x S, u nu x nit x S,
  *                                                    r my x nit x nref; struct with iae, ise, itae, emax, t_emax,
@@ -681,6 +687,51 @@ static void cmd_hypervolume(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = H;
 }
 
+/* X = mpct_mex('hypervolume_exact', costs, members, lo, ref [, device]): the arguments of 'hypervolume' without
+ * the sample count and the seed; at most three columns, which is the library's to judge with the shapes and the
+ * box (its message is surfaced) */
+static void cmd_hypervolume_exact(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 5 || nrhs > 6)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: X = mpct_mex('hypervolume_exact', costs, members, lo, ref [, device])");
+  const mxArray* a = prhs[1];
+  if (!a || !mxIsNumeric(a) || mxIsComplex(a) || mxIsSparse(a) || mxGetNumberOfDimensions(a) != 2)
+    mexErrMsgIdAndTxt("mpct:arg", "'costs' must be a real full C x k matrix");
+  const long C = (long)mxGetM(a), k = (long)mxGetN(a);
+  if (k > 1000000) mexErrMsgIdAndTxt("mpct:arg", "'costs' has too many columns");
+  const int all = mxIsEmpty(prhs[2]);
+  const long M = all ? C : (long)mxGetNumberOfElements(prhs[2]);
+  const double dv = opt_integer(nrhs, prhs, 5, "device", -1.0, -1e6, 1e6);
+  double* mm = all ? NULL : doubles(prhs[2], M, "members");
+  int32_t* mem = all ? NULL : (int32_t*)mxMalloc((size_t)(M + 1) * sizeof(int32_t));
+  for (long m = 0; !all && m < M; ++m) {
+    if (mm[m] != floor(mm[m]) || mm[m] < 0.0 || mm[m] > 2147483647.0)
+      mexErrMsgIdAndTxt("mpct:arg", "'members' must hold 1-based row indices (0: skipped)");
+    mem[m] = (int32_t)mm[m] - 1;
+  }
+  double* lo = doubles(prhs[3], k, "lo");
+  double* ref = doubles(prhs[4], k, "ref");
+  double* cm = doubles(a, C * k, "costs");
+  double* rows = (double*)mxMalloc((size_t)(C * k + 1) * sizeof(double));
+  for (long c = 0; c < C; ++c)
+    for (long j = 0; j < k; ++j) rows[c * k + j] = cm[(size_t)j * C + c];
+  int64_t nact = 0;
+  double hv = 0.0;
+  mpct_hvx_result r;
+  r.hv = &hv;
+  r.excl = (double*)mxCalloc((size_t)(M + 1), sizeof(double));
+  r.n_active = &nact;
+  if (mpct_hypervolume_exact(rows, C, (int32_t)k, mem, M, lo, ref, (int32_t)dv, &r) != MPCT_OK)
+    lib_error("mpct:hypervolume_exact");
+  const char* names[3] = {"hv", "excl", "n_active"};
+  mxArray* X = mxCreateStructMatrix(1, 1, 3, names);
+  mxSetField(X, 0, "hv", mxCreateDoubleScalar(hv));
+  mxArray* e = mxCreateDoubleMatrix((mwSize)M, 1, mxREAL);
+  for (long m = 0; m < M; ++m) mxGetPr(e)[m] = r.excl[m];
+  mxSetField(X, 0, "excl", e);
+  mxSetField(X, 0, "n_active", mxCreateDoubleScalar((double)nact));
+  plhs[0] = X;
+}
+
 /* S = mpct_mex('hv_select', costs, members, lo, ref, n_pick [, n_samples, seed, device]): the arguments of
  * 'hypervolume' plus the number of rounds; members, and the outputs pos and index, are 1-BASED (0: a skipped
  * entry going in, a slot after the end of the selection coming out); the shapes, the box and n_pick are the
@@ -1112,6 +1163,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_hypervolume(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "hv_select")) {
     cmd_hv_select(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "hypervolume_exact")) {
+    cmd_hypervolume_exact(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "indices")) {
     cmd_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "eval_indices")) {

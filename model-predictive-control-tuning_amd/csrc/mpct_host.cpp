@@ -18,6 +18,7 @@
 #include "pareto.h"
 #include "hv_select.h"
 #include "hypervolume.h"
+#include "hypervolume_exact.h"
 #include "traj_indices.h"
 #include "draw_stats.h"
 
@@ -787,6 +788,106 @@ extern "C" int32_t mpct_hv_select(const double* costs, int64_t C, int32_t k, con
     const hipError_t se = hipStreamSynchronize(st);
     if (rc == MPCT_OK && se != hipSuccess)
       rc = fail(MPCT_EDEVICE, std::string("mpct_hv_select failed on the device: ") + hipGetErrorString(se));
+  }
+  if (blob) (void)hipFree(blob);
+  if (st) (void)hipStreamDestroy(st);
+  if (dev != cur) (void)hipSetDevice(cur);
+  return rc;
+}
+
+// ---- Exact hypervolume and contributions for k <= 3 (hypervolume_exact.hip).  The argument checks of both
+// entries, in the order include/mpct.h states, before any device is touched; nothing is dereferenced
+static int hvx_check(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M, const double* lo,
+                     const double* ref, const mpct_hvx_result* out) {
+  if (k < 1) return fail(MPCT_EINVAL, "k < 1");
+  if (k > MPCT_HVX_MAX_OBJ) return fail(MPCT_ERANGE, "k exceeds MPCT_HVX_MAX_OBJ (the exact hypervolume serves k <= 3)");
+  if (C < 0 || M < 0) return fail(MPCT_EINVAL, "C < 0 or M < 0");
+  if (C > MPCT_PARETO_MAX_C) return fail(MPCT_ERANGE, "C exceeds MPCT_PARETO_MAX_C");
+  if (M > MPCT_HVX_MAX_M) return fail(MPCT_ERANGE, "M exceeds MPCT_HVX_MAX_M");
+  const int rc = hv_check_inputs(costs, C, members, M, lo, ref);
+  if (rc) return rc;
+  if (!out || !(out->hv || out->excl || out->n_active)) return fail(MPCT_EINVAL, "no output pointer in mpct_hvx_result");
+  return MPCT_OK;
+}
+
+static int32_t hvx_launch(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M, const double* lo,
+                          const double* ref, const mpct_hvx_result* out, hipStream_t stream) {
+  std::string err;
+  const HvxOut ho{out->hv, out->excl, reinterpret_cast<long long*>(out->n_active)};
+  const int rc = hypervolume_exact_device(costs, C, k, members, M, lo, ref, ho, stream, &err);
+  if (rc) return fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err);
+  return MPCT_OK;
+}
+
+extern "C" int32_t mpct_hypervolume_exact_device(const double* costs, int64_t C, int32_t k, const int32_t* members,
+                                                 int64_t M, const double* lo, const double* ref,
+                                                 const mpct_hvx_result* out, void* stream) {
+  const int rc = hvx_check(costs, C, k, members, M, lo, ref, out);
+  if (rc) return rc;
+  return hvx_launch(costs, C, k, members, M, lo, ref, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_hypervolume_exact(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
+                                          const double* lo, const double* ref, int32_t device,
+                                          const mpct_hvx_result* out) {
+  int rc = hvx_check(costs, C, k, members, M, lo, ref, out);
+  if (rc) return rc;
+  for (int j = 0; j < k; ++j)
+    if (!std::isfinite(lo[j]) || !std::isfinite(ref[j]) || !(lo[j] < ref[j]))
+      return fail(MPCT_EINVAL, "the box needs finite lo and ref with lo[j] < ref[j]");
+  for (int64_t m = 0; members && m < M; ++m)
+    if (members[m] < -1 || members[m] >= C) return fail(MPCT_EINVAL, "an entry of members is below -1 or >= C");
+  if (M == 0) {  // nothing to stage
+    if (out->hv) out->hv[0] = 0.0;
+    if (out->n_active) out->n_active[0] = 0;
+    return MPCT_OK;
+  }
+  int cur = -1, cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
+    return fail(MPCT_EDEVICE, "no HIP device (mpct_hypervolume_exact needs a GPU)");
+  const int dev = device < 0 ? cur : device;
+  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
+  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
+  // one blob: costs | members | lo | ref | excl | hv, n_active; each 256-B aligned; a stream of this call's own
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t nc = al((size_t)C * k * sizeof(double)), nm = al((size_t)M * sizeof(int32_t)), nb = al((size_t)k * sizeof(double)),
+               ne = al((size_t)M * sizeof(double));
+  hipStream_t st = nullptr;
+  char* blob = nullptr;
+  rc = MPCT_OK;
+  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
+    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
+  } else if (hipMalloc(reinterpret_cast<void**>(&blob), nc + nm + 2 * nb + ne + 2 * 256) != hipSuccess) {
+    rc = fail(MPCT_ENOMEM, "hipMalloc failed (hypervolume_exact staging)");
+  } else {
+    double* dcosts = reinterpret_cast<double*>(blob);
+    int32_t* dmem = members ? reinterpret_cast<int32_t*>(blob + nc) : nullptr;
+    double* dlo = reinterpret_cast<double*>(blob + nc + nm);
+    double* dref = reinterpret_cast<double*>(blob + nc + nm + nb);
+    char* tail = blob + nc + nm + 2 * nb + ne;
+    mpct_hvx_result d{};
+    d.excl = out->excl ? reinterpret_cast<double*>(blob + nc + nm + 2 * nb) : nullptr;
+    d.hv = out->hv ? reinterpret_cast<double*>(tail) : nullptr;
+    d.n_active = out->n_active ? reinterpret_cast<int64_t*>(tail + 256) : nullptr;
+    bool ok = hipMemcpyAsync(dcosts, costs, (size_t)C * k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
+              (!dmem || hipMemcpyAsync(dmem, members, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, st) == hipSuccess) &&
+              hipMemcpyAsync(dlo, lo, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(dref, ref, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hypervolume_exact inputs)");
+    if (ok) {
+      rc = hvx_launch(dcosts, C, k, dmem, M, dlo, dref, &d, st);
+      ok = rc == MPCT_OK;
+    }
+    if (ok) {
+      ok = (!d.excl || hipMemcpyAsync(out->excl, d.excl, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.hv || hipMemcpyAsync(out->hv, d.hv, sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess) &&
+           (!d.n_active || hipMemcpyAsync(out->n_active, d.n_active, sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess);
+      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hypervolume_exact results)");
+    }
+    // this call's stream only, also after an error: the blob is freed below
+    const hipError_t se = hipStreamSynchronize(st);
+    if (rc == MPCT_OK && se != hipSuccess)
+      rc = fail(MPCT_EDEVICE, std::string("mpct_hypervolume_exact failed on the device: ") + hipGetErrorString(se));
   }
   if (blob) (void)hipFree(blob);
   if (st) (void)hipStreamDestroy(st);

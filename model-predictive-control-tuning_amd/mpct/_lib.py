@@ -99,6 +99,10 @@ class MpctHvSelectResult(C.Structure):
                 ("covered", c_int64_p), ("hv", c_double_p), ("ties", c_int32_p), ("n_covered_all", c_int64_p)]
 
 
+class MpctHvxResult(C.Structure):
+    _fields_ = [("hv", c_double_p), ("excl", c_double_p), ("n_active", c_int64_p)]
+
+
 class MpctIndexParams(C.Structure):
     _fields_ = [("t0", C.c_int32), ("band_rel", C.c_double), ("band_abs", C.c_double)]
 
@@ -138,6 +142,7 @@ EXPORTS = [
     "mpct_indices_device", "mpct_indices", "mpct_eval_indices", "mpct_eval_indices_device",
     "mpct_draw_stats_device", "mpct_draw_stats", "mpct_eval_robust_indices", "mpct_eval_robust_indices_device",
     "mpct_hypervolume_device", "mpct_hypervolume", "mpct_hv_select_device", "mpct_hv_select",
+    "mpct_hypervolume_exact_device", "mpct_hypervolume_exact",
 ]
 
 ABI_VERSION = 7
@@ -145,6 +150,7 @@ TAIL_MAX_LEVELS, TAIL_MAX_DRAWS = 8, 4096
 PARETO_MAX_OBJ, PARETO_MAX_C, PARETO_MAX_LAYERS = 16, 1048576, 64
 HV_MAX_SAMPLES, HV_BINS = 1073741824, 8
 HVSEL_MAX_PICKS = 1024
+HVX_MAX_OBJ, HVX_MAX_M = 3, 65536
 INDEX_MAX_ROWS, INDEX_SCRATCH_BYTES = 2147483647, 268435456
 STAT_F64, STAT_I32 = 0, 1
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
@@ -255,6 +261,11 @@ def load():
     lib.mpct_hv_select_device.restype = C.c_int32
     lib.mpct_hv_select.argtypes = hv_args + [C.c_int32, C.c_int32, C.POINTER(MpctHvSelectResult)]
     lib.mpct_hv_select.restype = C.c_int32
+    hvx_args = hv_args[:7]
+    lib.mpct_hypervolume_exact_device.argtypes = hvx_args + [C.POINTER(MpctHvxResult), C.c_void_p]
+    lib.mpct_hypervolume_exact_device.restype = C.c_int32
+    lib.mpct_hypervolume_exact.argtypes = hvx_args + [C.c_int32, C.POINTER(MpctHvxResult)]
+    lib.mpct_hypervolume_exact.restype = C.c_int32
     # the tile length and the largest grid of hvsel_gain_kernel, and the per-round event times of the next
     # call alone (a host float array and its length, at least n_pick; None: off): test / tool hooks
     lib.mpct_internal_hvsel_tuned.argtypes = [C.c_int32, C.c_int32]

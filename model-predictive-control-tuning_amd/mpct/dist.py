@@ -293,6 +293,113 @@ def hypervolume_candidates(costs: torch.Tensor, front=None, lo=None, ref=None, n
     return dict(hv=hv, n_covered=n_cov, n_samples=int(n_samples), excl=excl, depth_hist=hist, lo=lo, ref=ref)
 
 
+def _hypervolume_exact_torch(costs: torch.Tensor, members, lo: torch.Tensor, ref: torch.Tensor):
+    """The sweep of mpct_hypervolume_exact_device (include/mpct.h) as torch expressions on the
+    tensor's device: the CPU path of hypervolume_exact_candidates.  The same terms as the kernel, products of
+    non-negative differences of clipped coordinates, summed in another order: it agrees with the device within
+    the contract's bound, not bitwise.  Returns (hv, excl [M] float64, n_active)."""
+    dev, f64 = costs.device, torch.float64
+    n, k = costs.shape
+    idx = torch.arange(n, device=dev) if members is None else members.to(torch.int64)
+    M = idx.numel()
+    excl = torch.zeros(M, dtype=f64, device=dev)
+    ok = (idx >= 0) & (idx < n)
+    rows = costs[idx.clamp(0, max(n - 1, 0))] if n else torch.full((M, k), float("nan"), dtype=f64, device=dev)
+    L = torch.cat([lo, torch.zeros(3 - k, dtype=f64, device=dev)])
+    R = torch.cat([ref, torch.ones(3 - k, dtype=f64, device=dev)])
+    b = torch.cat([rows, torch.zeros(M, 3 - k, dtype=f64, device=dev)], dim=1)
+    nan = torch.isnan(b).any(dim=1)
+    b = torch.where(b > L, b, L.expand_as(b)) + 0.0
+    act = ok & ~nan & (b < R).all(dim=1)
+    pos = torch.nonzero(act).flatten()
+    na = int(pos.numel())
+    if na == 0:
+        return 0.0, excl, 0
+    b = b[pos]
+
+    def lexorder(keys):   # stable sorts from the last key to the first: the order (keys[0], keys[1], .., entry)
+        o = torch.arange(na, device=dev)
+        for key in reversed(keys):
+            o = o[torch.sort(key[o], stable=True).indices]
+        return o
+
+    ox = lexorder([b[:, 0], b[:, 1], b[:, 2]])
+    oz = lexorder([b[:, 2], b[:, 0], b[:, 1]])
+    zrank = torch.empty(na, dtype=torch.int64, device=dev)
+    zrank[oz] = torch.arange(na, device=dev)
+    xs, yx, zrx = b[ox, 0], b[ox, 1], zrank[ox]
+    zs = b[oz, 2]
+    dx = torch.cat([xs[1:], R[0:1]]) - xs
+    z1 = torch.cat([zs[1:], R[2:3]])
+    inf = torch.full((na,), float("inf"), dtype=f64, device=dev)
+    none = torch.full((na,), -1, dtype=torch.int64, device=dev)
+    lane = torch.arange(na, device=dev)
+    hv = torch.zeros((), dtype=f64, device=dev)
+    part = torch.zeros(na, dtype=f64, device=dev)   # per entry in x order
+    for s in torch.nonzero(z1 > zs).flatten().tolist():
+        dz = z1[s] - zs[s]
+        on = zrx <= s
+        m1, h, m2 = torch.where(on, yx, inf), torch.where(on, lane, none), inf.clone()
+        d = 1
+        while d < na:   # inclusive scan of (m1, holder, m2), the left side winning a tie
+            a1 = torch.cat([inf[:d], m1[:-d]])
+            ha = torch.cat([none[:d], h[:-d]])
+            a2 = torch.cat([inf[:d], m2[:-d]])
+            left = a1 <= m1
+            m2 = torch.where(left, torch.minimum(a2, m1), torch.minimum(m2, a1))
+            m1, h = torch.where(left, a1, m1), torch.where(left, ha, h)
+            d *= 2
+        any_ = m1 < inf
+        zero = torch.zeros_like(dx)
+        hv = hv + dz * torch.where(any_, dx * (R[1] - m1), zero).sum()
+        te = torch.where(any_, dx * (torch.minimum(m2, R[1:2]) - m1), zero)
+        part.index_add_(0, h.clamp(min=0), dz * te)
+    excl[pos[ox]] = part
+    return float(hv), excl, na
+
+
+def hypervolume_exact_candidates(costs: torch.Tensor, front=None, lo=None, ref=None, C: int | None = None) -> dict:
+    """Exact hypervolume of the members ``front`` (indices into the gathered cost records, e.g.
+    pareto_candidates' front; -1 entries are skipped; None: every record) inside the box [lo, ref], for at most
+    three objectives, and every member's exclusive contribution (contract: mpct_hypervolume_exact_device in
+    include/mpct.h).  Returns a dict: hv (float), n_active (int), excl [M] float64 on the costs' device, lo and
+    ref [k] float64 there too.  ``lo`` / ``ref`` None: mpct.engine.default_box on the host.  GPU tensors go
+    through mpct_hypervolume_exact_device on the current stream; CPU tensors (the gloo tests) through a torch
+    restatement of the sweep, which sums the same non-negative terms in another order: the two paths agree
+    within the contract's bound, (M^2 + 8) 2^-53 vol, not bitwise."""
+    from . import engine
+
+    if C is not None:
+        costs = costs[:C]
+    if costs.dim() == 1:
+        costs = costs[:, None]
+    c = costs.to(torch.float64).contiguous()
+    n, k = c.shape
+    if not 1 <= k <= 3:
+        raise ValueError("k must be 1 .. 3: the exact hypervolume serves at most three objectives")
+    mem = None if front is None else torch.as_tensor(front).to(device=c.device, dtype=torch.int32).contiguous().flatten()
+    M = n if mem is None else mem.numel()
+    if M > 65536:
+        raise ValueError("at most 65536 members")
+    if lo is None or ref is None or not torch.is_tensor(lo) or not torch.is_tensor(ref):
+        lo, ref = engine.default_box(c.cpu().numpy(), None if mem is None else mem.cpu().numpy(),
+                                     lo.cpu().numpy() if torch.is_tensor(lo) else lo,
+                                     ref.cpu().numpy() if torch.is_tensor(ref) else ref)
+    lo = torch.as_tensor(lo, dtype=torch.float64).to(c.device).contiguous()
+    ref = torch.as_tensor(ref, dtype=torch.float64).to(c.device).contiguous()
+    if not (bool(torch.isfinite(lo).all()) and bool(torch.isfinite(ref).all()) and bool((lo < ref).all())):
+        raise ValueError("the box needs finite lo and ref with lo < ref")
+    if c.is_cuda:
+        out = dict(hv=torch.empty(1, dtype=torch.float64, device=c.device),
+                   excl=torch.empty(M, dtype=torch.float64, device=c.device),
+                   n_active=torch.empty(1, dtype=torch.int64, device=c.device))
+        engine.hypervolume_exact_device(c, out, lo, ref, members=mem)
+        hv, excl, na = float(out["hv"].item()), out["excl"], int(out["n_active"].item())
+    else:
+        hv, excl, na = _hypervolume_exact_torch(c, mem, lo, ref)
+    return dict(hv=hv, n_active=na, excl=excl, lo=lo, ref=ref)
+
+
 def _hv_select_torch(costs: torch.Tensor, members, lo: torch.Tensor, ref: torch.Tensor, n_samples: int, seed: int,
                      n_pick: int, chunk: int = 4096, mchunk: int = 2048) -> dict:
     """The contract of mpct_hv_select_device (include/mpct.h) as chunked torch expressions in int64 arithmetic,

@@ -421,6 +421,12 @@ class RobustResult:
         costs = self._cost_table(stat, max_failed, columns)
         return pareto(costs, device=device).hypervolume(costs, device=device, **kw)
 
+    def hypervolume_exact(self, stat: str = "worst", max_failed: int = 0, columns=(), device: int = -1, **kw):
+        """``hypervolume_exact`` of the front of the cost table ``pareto`` analyses (at most three columns);
+        ``kw`` are hypervolume_exact's lo and ref."""
+        costs = self._cost_table(stat, max_failed, columns)
+        return pareto(costs, device=device).hypervolume_exact(costs, device=device, **kw)
+
     def select(self, n_pick: int, stat: str = "worst", max_failed: int = 0, columns=(), device: int = -1, **kw):
         """``ParetoResult.select`` on the front of the cost table ``pareto`` analyses: the candidate indices of the
         ``n_pick`` members that carry it, in pick order; ``kw`` are hv_select's lo, ref, n_samples and seed."""
@@ -551,6 +557,11 @@ class ParetoResult:
     def hypervolume(self, costs, **kw):
         """``hypervolume`` of this front: ``costs`` is the table the front was computed from."""
         return hypervolume(costs, members=self.front, **kw)
+
+    def hypervolume_exact(self, costs, **kw):
+        """``hypervolume_exact`` of this front (at most three objectives): ``costs`` is the table the front was
+        computed from."""
+        return hypervolume_exact(costs, members=self.front, **kw)
 
     def select(self, costs, n_pick: int, **kw):
         """The candidate indices of the ``n_pick`` members that carry this front (fewer when the selection ends
@@ -709,6 +720,83 @@ def hypervolume_device(costs, out: dict, lo, ref, members=None, n_samples: int =
                                                  int(seed) & (2 ** 64 - 1), C.byref(r), C.c_void_p(stream))
     if rc != 0:
         raise MpctError("mpct_hypervolume_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+# --------------------------------------------------------------------------------------------
+# Exact hypervolume and contributions for at most three objectives (mpct_hypervolume_exact, include/mpct.h;
+# DESIGN.md §19)
+@dataclass
+class HvExactResult:
+    """The volume of the box [lo, ref] the members dominate and the volume each member alone dominates, by a
+    sweep with rounding error only: at most (M^2 + 8) 2^-53 vol on each value."""
+    hv: float                       # volume of the union of the members' boxes
+    excl: np.ndarray                # (M,) float64 volume member m alone dominates; +0.0: redundant, inactive or duplicated
+    n_active: int                   # members with a box of positive volume
+    vol: float                      # of the box
+    lo: np.ndarray                  # (k,) the box
+    ref: np.ndarray
+    members: np.ndarray | None = None   # (M,) the candidates excl refers to (-1: skipped); None: all, in order
+
+    def contribution(self) -> np.ndarray:
+        """(M,) each member's share of the hypervolume, excl / hv (zeros when hv is 0)"""
+        return self.excl / self.hv if self.hv > 0.0 else np.zeros_like(self.excl)
+
+
+def hypervolume_exact(costs, members=None, lo=None, ref=None, device: int = -1) -> HvExactResult:
+    """mpct_hypervolume_exact: the exact hypervolume the rows ``members`` of the (C, k) cost table, k <= 3,
+    dominate inside the box [lo, ref] (None: all rows; -1 entries are skipped, so a -1-padded front may be
+    passed), with every member's exclusive contribution, computed by a sweep on the GPU.  ``lo`` / ``ref`` None:
+    ``default_box``.  More than three columns raise MpctError (MPCT_ERANGE): there is no fall-back to the
+    Monte-Carlo estimate of ``hypervolume``."""
+    a = _pareto_costs(costs)
+    Cn, k = a.shape
+    mem = None if members is None else np.ascontiguousarray(members, dtype=np.int32).reshape(-1)
+    M = Cn if mem is None else mem.size
+    if k > _lib.HVX_MAX_OBJ:   # the library's error, before a default box is computed for nothing
+        lo_, ref_ = np.zeros(k), np.ones(k)
+    else:
+        lo_, ref_ = default_box(a, mem, lo, ref)
+    excl = np.zeros(M, dtype=np.float64)
+    hv = np.zeros(1, dtype=np.float64)
+    nact = np.zeros(1, dtype=np.int64)
+    r = _lib.MpctHvxResult(_dp(hv), _dp(excl) if M else None, nact.ctypes.data_as(_lib.c_int64_p))
+    rc = _lib.load().mpct_hypervolume_exact(a.ctypes.data, Cn, k, mem.ctypes.data if mem is not None else None, M,
+                                            lo_.ctypes.data, ref_.ctypes.data, int(device), C.byref(r))
+    if rc != 0:
+        raise MpctError("mpct_hypervolume_exact failed (%d): %s" % (rc, _lib.last_error()))
+    return HvExactResult(hv=float(hv[0]), excl=excl, n_active=int(nact[0]), vol=box_volume(lo_, ref_), lo=lo_, ref=ref_,
+                         members=None if mem is None else mem.copy())
+
+
+def hypervolume_exact_device(costs, out: dict, lo, ref, members=None):
+    """mpct_hypervolume_exact_device: ``costs`` is a float64 CUDA (HIP) tensor [C, k], k <= 3, ``members`` an
+    int32 tensor [M] or None (all rows), ``lo`` and ``ref`` float64 tensors [k] on the same device.  The results
+    are written into the tensors of ``out`` (keys hv [1], excl [M]: float64; n_active [1]: int64; any may be
+    absent).  Enqueued on the current torch stream of the tensor's device and not synchronised."""
+    import torch
+
+    if costs.dtype != torch.float64 or costs.dim() != 2 or not costs.is_contiguous():
+        raise ValueError("costs must be a contiguous float64 tensor [C, k]")
+    k = costs.shape[1]
+    for name, t in (("lo", lo), ("ref", ref)):
+        if t.dtype != torch.float64 or t.shape != (k,) or not t.is_contiguous() or t.device != costs.device:
+            raise ValueError("%s must be a contiguous float64 tensor [k] on the costs' device" % name)
+    if members is not None and (members.dtype != torch.int32 or members.dim() != 1 or not members.is_contiguous()
+                                or members.device != costs.device):
+        raise ValueError("members must be a contiguous int32 tensor [M] on the costs' device")
+    M = costs.shape[0] if members is None else members.shape[0]
+    if out.get("excl") is not None and out["excl"].numel() < M:
+        raise ValueError("out['excl'] holds fewer than M entries")
+    r = _lib.MpctHvxResult(_tptr(out.get("hv"), _lib.c_double_p), _tptr(out.get("excl"), _lib.c_double_p),
+                           _tptr(out.get("n_active"), _lib.c_int64_p))
+    stream = torch.cuda.current_stream(costs.device).cuda_stream
+    with torch.cuda.device(costs.device):
+        rc = _lib.load().mpct_hypervolume_exact_device(C.c_void_p(costs.data_ptr()), costs.shape[0], k,
+                                                       C.c_void_p(members.data_ptr()) if members is not None else None, M,
+                                                       C.c_void_p(lo.data_ptr()), C.c_void_p(ref.data_ptr()), C.byref(r),
+                                                       C.c_void_p(stream))
+    if rc != 0:
+        raise MpctError("mpct_hypervolume_exact_device failed (%d): %s" % (rc, _lib.last_error()))
 
 
 # --------------------------------------------------------------------------------------------
@@ -1143,6 +1231,12 @@ class RobustIndexResult:
         n_samples and seed."""
         costs = self.costs(stat, names, max_failed)
         return pareto(costs, device=device).hypervolume(costs, device=device, **kw)
+
+    def hypervolume_exact(self, stat="hi", names=None, max_failed: int = 0, device: int = -1, **kw):
+        """``hypervolume_exact`` of the front of the table ``costs`` returns (at most three columns); ``kw`` are
+        hypervolume_exact's lo and ref."""
+        costs = self.costs(stat, names, max_failed)
+        return pareto(costs, device=device).hypervolume_exact(costs, device=device, **kw)
 
     def select(self, n_pick: int, stat="hi", names=None, max_failed: int = 0, device: int = -1, **kw):
         """``ParetoResult.select`` on the front of the table ``costs`` returns; ``kw`` are hv_select's lo, ref,
