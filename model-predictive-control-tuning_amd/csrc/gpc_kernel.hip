@@ -551,7 +551,7 @@ namespace mpct {
 long long small_lds_bytes(const DevScenario& sc, int M);  // gpc_small.hip
 int launch_small(const DevScenario& sc, long long C, int nref, const int* N2, const int* Nu, const double* delta,
                  const double* lambda, const double* r, const DevOpts& o, const DevResult& out, const int* perm,
-                 int first, hipStream_t stream, std::string* err);
+                 int first, long long slot0, long long nslot, bool wide, hipStream_t stream, std::string* err);
 long long dtc_small_lds_bytes(const DevScenario& sc, int M);  // dtc_small.hip
 int launch_dtc_small(const DevScenario& sc, int cls, long long C, int nref, const int* N2, const int* Nu,
                      const double* delta, const double* lambda, const double* r, const double* v, const DevOpts& o,
@@ -630,7 +630,7 @@ std::string closed_loop_instance(const DevScenario& sc, int maxM, bool ext) {
 int launch_closed_loop(const DevScenario& sc, long long C, int nref, const int* N2, const int* Nu,
                        const double* delta, const double* lambda, const double* r,
                        const double* v, const DevOpts& o, const DevResult& out, int maxM,
-                       WorkOrder* wo, LaunchFan* fan, hipStream_t stream, std::string* err) {
+                       WorkOrder* wo, LaunchFan* fan, long long wide, int ncu, hipStream_t stream, std::string* err) {
   if (maxM > 64) {
     *err = "nu*nu_max > 64";
     return -4;
@@ -657,7 +657,15 @@ int launch_closed_loop(const DevScenario& sc, long long C, int nref, const int* 
   }
   int rc = prefilled ? 0 : prefill_results(lo, C * nref, sc.my, sc.nu, stream, err);
   if (rc) return rc;
-  FanScope fs(top_class(maxM) > 16 ? fan : nullptr, stream);
+  // the wide split: the first H slots of an ordered, cost-only launch on a small scenario
+  // run on gpc_small_wide_kernel on the caller's stream, the rest on gpc_small_kernel on the fan's
+  // last auxiliary stream, which no class launch uses (classes 16, 32, 64 take streams 0..2).  Both
+  // are class launch 0: the class launches above M = 16 keep their indices, streams and `first`
+  const bool ext = o.open_loop || o.want_traj;
+  const long long S = C * nref;
+  long long H = wide_slots(S, ncu, perm && sc.small && !ext && sc.nu <= 16 && fan && fan->ready, wide);
+  FanScope fs(top_class(maxM) > 16 || H > 0 ? fan : nullptr, stream);
+  if (!fs.fan) H = 0;
   int k = 0, mlo = 0;
   for (int cls = 16; cls <= top_class(maxM) && rc == 0; cls *= 2) {
     if (sc.nu > cls) {  // no simulation fits this class
@@ -666,9 +674,14 @@ int launch_closed_loop(const DevScenario& sc, long long C, int nref, const int* 
     }
     const hipStream_t st = fs.stream(k);
     const int first = k == 0;
-    const bool ext = o.open_loop || o.want_traj;
     if (diag_drop_launch(k)) rc = 0;
-    else if (cls == 16 && sc.small && !ext) rc = launch_small(sc, C, nref, N2, Nu, delta, lambda, r, o, lo, perm, first, st, err);
+    else if (cls == 16 && sc.small && !ext) {
+      // every slot is in one of the two ranges, so each skipped / bad-horizon status has one writer
+      if (H > 0) rc = launch_small(sc, C, nref, N2, Nu, delta, lambda, r, o, lo, perm, first, 0, H, true, st, err);
+      if (rc == 0 && H < S)
+        rc = launch_small(sc, C, nref, N2, Nu, delta, lambda, r, o, lo, perm, first, H, S - H, false,
+                          H > 0 ? fs.stream(kFanAux) : st, err);
+    }
     else if (cls <= 32 && sc.small_dtc && !ext)
       rc = launch_dtc_small(sc, cls, C, nref, N2, Nu, delta, lambda, r, v, o, lo, perm, mlo, first, st, err);
     else if (cls == 16) rc = launch_t<16>(sc, C, nref, N2, Nu, delta, lambda, r, v, o, lo, perm, mlo, first, st, err);

@@ -72,13 +72,18 @@ constexpr int kBS = 16;
 // the lane id as an opaque value, re-derived at every use: the step loop's register budget cannot
 // hold the dozens of lane-derived addresses and predicates the compiler would otherwise hoist out
 // of it (three waves per SIMD = 168 VGPRs)
+// W (gpc_small_wide_kernel, 256 VGPRs): the plain lane id, so that the compiler hoists what it
+// can now afford to keep; every helper below passes W on and defaults to the opaque copy
+template <bool W = false>
 __device__ __forceinline__ int qlane() {
   int l = threadIdx.x;
-  asm volatile("" : "+v"(l));
+  if constexpr (!W) asm volatile("" : "+v"(l));
   return l;
 }
-__device__ __forceinline__ int q16_i() { return qlane() & 15; }
-__device__ __forceinline__ int q16_b() { return qlane() >> 4; }
+template <bool W = false>
+__device__ __forceinline__ int q16_i() { return qlane<W>() & 15; }
+template <bool W = false>
+__device__ __forceinline__ int q16_b() { return qlane<W>() >> 4; }
 
 // entry r (wave-uniform) of a lane's 4 registers.  The four values are passed by value: a
 // selection between loads through a reference would be folded (in the callee, before inlining)
@@ -113,8 +118,9 @@ __device__ __forceinline__ double cvec_at(const d4v& c, int k) {
 }
 
 // B(i, 4b..4b+3) of lane (i, b)
+template <bool W = false>
 __device__ __forceinline__ void b_row4(const double* sB, d4v& x) {
-  const double2* p = reinterpret_cast<const double2*>(sB + q16_i() * kBS + 4 * q16_b());
+  const double2* p = reinterpret_cast<const double2*>(sB + q16_i<W>() * kBS + 4 * q16_b<W>());
   const double2 u = p[0], v = p[1];
   x[0] = u.x;
   x[1] = u.y;
@@ -124,8 +130,10 @@ __device__ __forceinline__ void b_row4(const double* sB, d4v& x) {
 
 // lane (i, b) receives lane (i, b + 1) / (i, b - 1): the rare Givens rotation across a register
 // block boundary (columns 4b + 3 and 4b + 4)
-__device__ __forceinline__ double rows_down(double v) { return __shfl(v, qlane() + 16, 64); }
-__device__ __forceinline__ double rows_up(double v) { return __shfl(v, qlane() - 16, 64); }
+template <bool W = false>
+__device__ __forceinline__ double rows_down(double v) { return __shfl(v, qlane<W>() + 16, 64); }
+template <bool W = false>
+__device__ __forceinline__ double rows_up(double v) { return __shfl(v, qlane<W>() - 16, 64); }
 
 // columns (jj, jj + 1) of J <- (c x_jj + s x_jj+1, -s x_jj + c x_jj+1).  jj is wave-uniform: a
 // scalar switch picks the register pair (a branch-free form with selects on every register took 9
@@ -137,8 +145,9 @@ __device__ __forceinline__ void rot_pair(double& a, double& c, bool on, double c
     c = -sn * a0 + cs * c0;
   }
 }
+template <bool W = false>
 __device__ __forceinline__ void rb_rotate_cols(d4v& x, int jj, double cs, double sn) {
-  const int b = q16_b(), b0 = jj >> 2;
+  const int b = q16_b<W>(), b0 = jj >> 2;
   const bool on = b == b0;
   switch (jj & 3) {
     case 0: {
@@ -163,7 +172,7 @@ __device__ __forceinline__ void rb_rotate_cols(d4v& x, int jj, double cs, double
       break;
     }
     default: {  // columns 4 b0 + 3 and 4 (b0 + 1): across two register blocks
-      const double nx0 = rows_down(x[0]), pv3 = rows_up(x[3]);
+      const double nx0 = rows_down<W>(x[0]), pv3 = rows_up<W>(x[3]);
       if (on) x[3] = cs * x[3] + sn * nx0;
       if (b == b0 + 1) x[0] = -sn * pv3 + cs * x[0];
       break;
@@ -172,15 +181,17 @@ __device__ __forceinline__ void rb_rotate_cols(d4v& x, int jj, double cs, double
 }
 
 // box-constraint active flags on the replicated rows: bit kind of row m = p >> 2
-struct BoxMark16 {
+template <bool W>
+struct BoxMark16T {
   template <class St>
   __device__ __forceinline__ void operator()(St& S, int p, bool on) const {
-    if (q16_i() == (p >> 2)) {
+    if (q16_i<W>() == (p >> 2)) {
       if (on) S.act |= 1u << (p & 3);
       else S.act &= ~(1u << (p & 3));
     }
   }
 };
+using BoxMark16 = BoxMark16T<false>;
 
 // entry (i, k), k >= i, of the upper-triangular R^-1 in LDS: row-major M x M, or (PACKED) its
 // upper triangle row by row (M (M + 1) / 2 doubles)
@@ -191,9 +202,9 @@ __device__ __forceinline__ int rinv_idx(int i, int k, int M) {
 
 // J <- R^-1 (upper, in LDS), B <- 0 (rows i < M: B has M rows of stride kBS; lanes i >= M only
 // ever read their own rows, whose products no QP row uses)
-template <bool PACKED>
+template <bool PACKED, bool W = false>
 __device__ __forceinline__ void gi16_load_rinv(GIState<16>& S, RegFactors& F, const double* sRi, int M) {
-  const int i = q16_i(), b = q16_b();
+  const int i = q16_i<W>(), b = q16_b<W>();
   FOR4(r, {
     const int k = 4 * b + r;
     F.J[r] = (i < M && k < M && k >= i) ? sRi[rinv_idx<PACKED>(i, k, M)] : 0.0;
@@ -210,10 +221,11 @@ __device__ __forceinline__ void gi16_load_rinv(GIState<16>& S, RegFactors& F, co
 // d = J'n_p for constraint p (rows j0..mp of J, sign sg) -> column vector.  A one-row normal (the
 // rate rows, kinds 0/1) is row j0 of J itself: fetched by ds_bpermute (8 instructions) instead of
 // the 16-lane sum of the masked rows (48), the same value
+template <bool W = false>
 __device__ __forceinline__ void gi16_dvec(const RegFactors& F, int j0, int mp, double sg, d4v& d) {
-  const int i = q16_i();
+  const int i = q16_i<W>();
   if (j0 == mp) {
-    const int src = j0 + 16 * q16_b();
+    const int src = j0 + 16 * q16_b<W>();
     FOR4(r, d[r] = __shfl(F.J[r], src, kWave););
   } else {
     const bool in = i >= j0 && i <= mp;
@@ -226,9 +238,10 @@ __device__ __forceinline__ void gi16_dvec(const RegFactors& F, int j0, int mp, d
 // the products an iteration needs from d (column vector), q = active-set size, Bl = the lane's
 // B(i, 4b..4b+3):  z = J(:,q:)d(q:), jq = J(:,q), rk = B d(0:q) (row vectors), dn2 = |d|^2,
 // beta = |d(q:)|^2
+template <bool W = false>
 __device__ __forceinline__ void gi16_products(const RegFactors& F, const d4v& Bl, const d4v& d, int q,
                                               double& z, double& jq, double& rk, double& dn2, double& beta) {
-  const int b = q16_b();
+  const int b = q16_b<W>();
   double za = 0.0, ra = 0.0, s1 = 0.0, s2 = 0.0;
   FOR4(r, {
     const bool tail = 4 * b + r >= q;
@@ -252,11 +265,11 @@ __device__ __forceinline__ void gi16_products(const RegFactors& F, const d4v& Bl
 
 // append constraint p: Householder on J(:,q:) mapping d(q:) to alpha e_q, B's column q and R_A's
 // column q (LDS), the multiplier upm and the id
-template <class Mark>
+template <bool W = false, class Mark>
 __device__ __forceinline__ void gi16_add(GIState<16>& S, RegFactors& F, double* sRA, int M, int p,
                                          const d4v& d, double beta, double z, double jq, double rk,
                                          double upm, const Mark& mark) {
-  const int lane = qlane(), i = lane & 15, b = lane >> 4;
+  const int lane = qlane<W>(), i = lane & 15, b = lane >> 4;
   const int q = S.q;
   const double dq = cvec_at(d, q);
   const double nrm = beta * rsq_nr(beta);  // beta > 0 on an add
@@ -291,10 +304,10 @@ __device__ __forceinline__ void gi16_add(GIState<16>& S, RegFactors& F, double* 
 // remove active constraint kd: R_A loses column kd and is re-triangularised by Givens rotations
 // (LDS, lanes = columns), applied to J's columns in registers and to B's columns in LDS (lanes =
 // rows); B then loses row kd
-template <class Mark>
+template <bool W = false, class Mark>
 __device__ __forceinline__ void gi16_drop(GIState<16>& S, RegFactors& F, double* sRA, int M, int kd,
                                           const Mark& mark) {
-  const int lane = qlane(), i = lane & 15;
+  const int lane = qlane<W>(), i = lane & 15;
   const int q = S.q;
   double* sB = F.sB;
   const int idk = __builtin_amdgcn_readlane(S.ww, kd);
@@ -336,7 +349,7 @@ __device__ __forceinline__ void gi16_drop(GIState<16>& S, RegFactors& F, double*
         sB[lane * kBS + jj] = cs * b0 + sn * b1;
         sB[lane * kBS + jj + 1] = -sn * b0 + cs * b1;
       }
-      rb_rotate_cols(F.J, jj, cs, sn);
+      rb_rotate_cols<W>(F.J, jj, cs, sn);
       S.nrot += 1;
     }
     lds_sync();
@@ -354,7 +367,7 @@ __device__ __forceinline__ void gi16_drop(GIState<16>& S, RegFactors& F, double*
 // up_row, the row's constraint data rc (both replicated over the four row blocks); the optimal
 // moves come back in xout (row vector, registers; xu itself when it is feasible).  rebuild: the
 // J rebuild interval in units of M rotations (gpc_qp.h); PACKED: R^-1's layout (rinv_idx)
-template <bool PACKED = false, class PAcc = void, bool BLDS = false>
+template <bool PACKED = false, class PAcc = void, bool BLDS = false, bool W = false>
 __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, int Nu,
                                        const RowCons& rc, double up_row, double xu, double tol, int maxit,
                                        int* st, GIState<16>& S, RegFactors& F, int rebuild, double& xout
@@ -362,7 +375,7 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
                                        , PAcc& pacc, unsigned long long& pprev
 #endif
                                        ) {
-  const int lane = qlane(), i = lane & 15;
+  const int lane = qlane<W>(), i = lane & 15;
   const bool row = i < M;
   if (!row) up_row = 0.0;
   const int rl = rc.l;
@@ -407,9 +420,9 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
     }
     if (!row) s[0] = s[1] = s[2] = s[3] = INFINITY;
   };
-  const BoxMark16 mark{};
+  const BoxMark16T<W> mark{};
   auto add = [&](int p, const d4v& d, double beta, double z, double jq, double rk, double upm)
-                 __attribute__((always_inline)) { gi16_add(S, F, sRA, M, p, d, beta, z, jq, rk, upm, mark); };
+                 __attribute__((always_inline)) { gi16_add<W>(S, F, sRA, M, p, d, beta, z, jq, rk, upm, mark); };
   int it = 0;
   double xm = xu;
   PSTAMP(PROF_QCHECK);
@@ -431,7 +444,7 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
 #ifdef MPCT_PROFILE
         pacc[PROF_QWREADD] += (unsigned long long)qq * kProfCount;
 #endif
-        gi16_load_rinv<PACKED>(S, F, sRi, M);
+        gi16_load_rinv<PACKED, W>(S, F, sRi, M);
         S.q = 0;
         for (int v = 0; v < qq; ++v) {
           const int p = __builtin_amdgcn_readlane(S.ww, v);
@@ -440,10 +453,10 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
           gi_normal(p, rc, j0, mp, sg);
           d4v Bl, d;
           lds_sync();
-          b_row4(F.sB, Bl);
-          gi16_dvec(F, j0, mp, sg, d);
+          b_row4<W>(F.sB, Bl);
+          gi16_dvec<W>(F, j0, mp, sg, d);
           double z, jq, rk, dn2, beta;
-          gi16_products(F, Bl, d, v, z, jq, rk, dn2, beta);
+          gi16_products<W>(F, Bl, d, v, z, jq, rk, dn2, beta);
           const double uk = S.uw;
           add(p, d, beta, z, jq, rk, 0.0);
           if (i == v) S.uw = uk;
@@ -459,7 +472,7 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
       // from QP row m (ds_bpermute; no LDS buffer), once: a drop shifts c with the ids
       double c;
       {
-        const int src = (S.ww >= 0 ? S.ww >> 2 : 0) + 16 * q16_b();
+        const int src = (S.ww >= 0 ? S.ww >> 2 : 0) + 16 * q16_b<W>();
         const double g0 = __shfl(s[0], src, kWave), g1 = __shfl(s[1], src, kWave);
         const double g2 = __shfl(s[2], src, kWave), g3 = __shfl(s[3], src, kWave);
         c = i < S.q ? -sel4v_v(g0, g1, g2, g3, S.ww & 3) : 0.0;
@@ -472,10 +485,10 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
           break;
         }
         d4v Bl, w;
-        b_row4(F.sB, Bl);
+        b_row4<W>(F.sB, Bl);
         FOR4(r, w[r] = i < q ? Bl[r] * c : 0.0;);
         row16_sum4(w);
-        const int b = q16_b();
+        const int b = q16_b<W>();
         double xa = 0.0, la = 0.0;
         FOR4(r, {
           if (4 * b + r < q) {
@@ -499,7 +512,7 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
         if (!(S.diag & kDiagSkipWarmDrop))
 #endif
         {
-          gi16_drop(S, F, sRA, M, kd, mark);
+          gi16_drop<W>(S, F, sRA, M, kd, mark);
           {  // c follows the ids: entries kd + 1 .. q - 1 move down one lane
             const double cn = lane_next<16>(c);
             if (i >= kd && i < q - 1) c = cn;
@@ -543,7 +556,7 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
       *st |= MPCT_ST_QP_MAXITER_;
       break;
     }
-    if (!S.jinit) gi16_load_rinv<PACKED>(S, F, sRi, M);
+    if (!S.jinit) gi16_load_rinv<PACKED, W>(S, F, sRi, M);
     const int p = bid;
     int j0, mp;
     double sgp;
@@ -554,10 +567,10 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
     for (;;) {
       ++it;
       d4v Bl, d;
-      b_row4(F.sB, Bl);  // issues under d's reduction
-      gi16_dvec(F, j0, mp, sgp, d);
+      b_row4<W>(F.sB, Bl);  // issues under d's reduction
+      gi16_dvec<W>(F, j0, mp, sgp, d);
       double zm, jq, rk, dn2, beta;
-      gi16_products(F, Bl, d, S.q, zm, jq, rk, dn2, beta);
+      gi16_products<W>(F, Bl, d, S.q, zm, jq, rk, dn2, beta);
       PSTAMP(PROF_QD);
       // dual step over active constraints with r_w > 0
       double t1 = INFINITY;
@@ -594,7 +607,7 @@ __device__ __forceinline__ int gi_qp16(const double* sRi, double* sRA, int M, in
 #ifdef MPCT_PROFILE
       pacc[PROF_QROT] += (unsigned long long)(S.q - 1 - kdrop) * kProfCount;
 #endif
-      gi16_drop(S, F, sRA, M, kdrop, mark);
+      gi16_drop<W>(S, F, sRA, M, kdrop, mark);
       PSTAMP(PROF_QDROP);
       if (it >= maxit) {  // flagged here; the outer loop then passes through its check once more and ends there
         *st |= MPCT_ST_QP_MAXITER_;

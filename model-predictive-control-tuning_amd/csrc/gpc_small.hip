@@ -42,6 +42,24 @@
 #include "gpc_prologue.h"
 #include "gpc_record.h"
 
+// what the wide instance spends its registers on; each measured alone
+#ifndef MPCT_WIDE_BREG
+#define MPCT_WIDE_BREG 1  // the QP rows' MV bounds in VGPRs
+#endif
+#ifndef MPCT_WIDE_AREG
+#define MPCT_WIDE_AREG 1  // the lane's A row segment in VGPRs
+#endif
+// plain lane ids: hoisted predicates and addresses.  Not in the diagnostic build, which must equal the
+// release library bit for bit (tests/test_qp_caps.py): with plain lane ids its extra branch around the
+// warm start's drop changes which products the compiler contracts into FMAs (416 v_fma_f64 against 410)
+#ifndef MPCT_WIDE_PLAIN
+#ifdef MPCT_DIAG
+#define MPCT_WIDE_PLAIN 0
+#else
+#define MPCT_WIDE_PLAIN 1
+#endif
+#endif
+
 namespace mpct {
 
 // LDS layout of one simulation (doubles, 16-byte aligned pieces)
@@ -67,30 +85,35 @@ __host__ __device__ inline SmallLayout small_layout(const DevScenario& sc, int M
 
 // opaque lane id: predicates derived from it are recomputed where used instead of being hoisted
 // into SGPR-pair masks that the loop would have to keep live (and spill)
+// (WIDE, gpc_small_wide_kernel: the plain lane id; 256 VGPRs hold what the compiler then hoists)
+template <bool WIDE>
 __device__ __forceinline__ int sm_lane() {
   int l = threadIdx.x;
-  asm volatile("" : "+v"(l));
+  if constexpr (!WIDE) asm volatile("" : "+v"(l));
   return l;
 }
 
-// four waves per SIMD: 128 VGPRs (no spill since round 6: the QP rows' bounds live in LDS) and 10 KB of
-// LDS, so 16 workgroups fit a CU and the metric's 4096 simulations run in one round.  Against three
-// waves: bitwise the same results, 3.11-3.19 against 3.38-3.46 ms at 8192 candidates, the same
-// 2.21-2.24 ms at 4096 (profiles/r04b_small_ab.txt)
-__global__ void __launch_bounds__(64, 4)
-    gpc_small_kernel(const DevScenario sc, long long C, int nref, const int* __restrict__ N2v,
+// One body, two instances.  gpc_small_kernel is the body at WIDE = false.
+// gpc_small_wide_kernel (WIDE = true) runs the first slots of an ordered launch, the heaviest
+// simulations, at two waves per SIMD and up to 256 VGPRs: same LDS layout, same arithmetic in the
+// same order, bitwise the same results.  Each launch covers the slots slot0 .. slot0 + nslot - 1
+template <bool WIDE>
+__device__ __forceinline__ void gpc_small_body(const DevScenario& sc, long long C, int nref, const int* __restrict__ N2v,
                      const int* __restrict__ Nuv, const double* __restrict__ deltav,
                      const double* __restrict__ lambdav, const double* __restrict__ rv,
-                     const int* __restrict__ perm, const DevOpts o, const DevResult out, int first) {
+                     const int* __restrict__ perm, const DevOpts& o, const DevResult& out, int first,
+                     long long slot0, long long nslot) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int lane = threadIdx.x;
-  const long long slot = blockIdx.x;
   const long long S = C * nref;
+  if ((long long)blockIdx.x >= nslot) return;
+  const long long slot = slot0 + blockIdx.x;
   if (slot >= S) return;
   const long long cs = slot / nref;
   const int kref = (int)(slot - cs * nref);
   const long long c = perm ? (long long)perm[cs] : cs;
   const long long sim = c * nref + kref;
+  constexpr bool kWideBReg = WIDE && MPCT_WIDE_BREG, kWideAReg = WIDE && MPCT_WIDE_AREG, kPlain = WIDE && MPCT_WIDE_PLAIN;
   const int my = sc.my, nu = sc.nu, nit = sc.nit;
   const int N2 = N2v[c], Nu = Nuv[c];
   const int M = nu * Nu;
@@ -157,8 +180,15 @@ __global__ void __launch_bounds__(64, 4)
   rcn.n = qm < M ? qm / Nu : 0;
   rcn.l = qm < M ? qm - rcn.n * Nu : 0;
   // the row's MV bounds stay in LDS (gpc_qp16.h BLDS), stored before the loop's first lds_sync
+  // (WIDE: in eight VGPRs instead, gi_qp16<.., BLDS = false>; the LDS table is written all the same)
   if (lane < 4 * nu) lds[L.bnd + lane] = sc.bnd[(lane & 3) * nu + (lane >> 2)];
   rcn.bnd = lds + L.bnd + 4 * rcn.n;
+  if constexpr (kWideBReg) {
+    rcn.dmin = sc.bnd[0 * nu + rcn.n];
+    rcn.dmax = sc.bnd[1 * nu + rcn.n];
+    rcn.umin = sc.bnd[2 * nu + rcn.n];
+    rcn.umax = sc.bnd[3 * nu + rcn.n];
+  }
   const double tol = o.feas_tol;
   const int maxit = o.max_qp_iter > 0 ? o.max_qp_iter : 8 * M + 16;
   const int ink0 = sc.ink0;
@@ -180,6 +210,22 @@ __global__ void __launch_bounds__(64, 4)
   double uprev = 0.0;                                 // lane n < nu: u_n(t - 1)
   double j1 = 0.0, j22 = 0.0;
   double r_t = psr[0], yr_t = psy[0];
+  // WIDE: the lane's A row segment (8 doubles, 12 on quarter 0) stays in registers across the loop
+  // instead of six ds_read_b128 per step
+  double ar[kSmY];
+#pragma unroll
+  for (int p = 0; p < kSmY; ++p) ar[p] = 0.0;
+  if constexpr (kWideAReg) {
+    lds_sync();  // A of the prologue
+    if (qm < M) {
+#pragma unroll
+      for (int p = 0; p < kSmR; ++p) ar[p] = lds[aoff + p];
+      if (lane < 16) {
+#pragma unroll
+        for (int p = kSmR; p < kSmY; ++p) ar[p] = lds[aoff + p];
+      }
+    }
+  }
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): per-lane constants land before the loop
 
   for (int t = 0; t < nit; ++t) {
@@ -192,11 +238,11 @@ __global__ void __launch_bounds__(64, 4)
     const double ye = row4_sum(pcoef * hv);  // y_e(t) on lane e of every row
     double yi = ye + dppd<kQx1>(ye);
     yi += dppd<kQx2>(yi);  // y_i(t) on every lane of quad i
-    if (sm_lane() < 4 * my) lds[L.hist + kSmEOff + sm_lane() * ke + (t & (ke - 1))] = ye;
+    if (sm_lane<kPlain>() < 4 * my) lds[L.hist + kSmEOff + sm_lane<kPlain>() * ke + (t & (ke - 1))] = ye;
     PSTAMP(PROF_PLANT);
     // ---- y update and costs (lane 4 i): x = [y - r, nabla y, .., nabla^na y] (difference basis)
     {
-      const int l = sm_lane();
+      const int l = sm_lane<kPlain>();
       if ((l & ~12) == 0 && (l >> 2) < my) {
         // nabla^1,2 y(t-1) are the state's own entries of the last step (read before they are
         // overwritten); y(t-1) stays in a register
@@ -223,18 +269,33 @@ __global__ void __launch_bounds__(64, 4)
     double xu;
     {
       const int h = (1 - t) & (kSmR - 1);  // ring window start: age-0 move
-      const int xo = xoff + (sm_lane() >= 16 ? h : 0);
+      const int xo = xoff + (sm_lane<kPlain>() >= 16 ? h : 0);
       const double2* av = reinterpret_cast<const double2*>(lds + aoff);
       const double* xv = lds + xo;
       double a0 = 0.0, a1 = 0.0;
-      if ((sm_lane() & 15) < M) {  // A has M rows
+      if constexpr (kWideAReg) {  // the same FMAs in the same order (rows >= M hold zeros: a0 = a1 = +0)
+        if (qm < M) {
+#pragma unroll
+          for (int p = 0; p < kSmR / 2; ++p) {
+            a0 = fma(ar[2 * p], xv[2 * p], a0);
+            a1 = fma(ar[2 * p + 1], xv[2 * p + 1], a1);
+          }
+          if (lane < 16) {
+#pragma unroll
+            for (int p = kSmR / 2; p < kSmY / 2; ++p) {
+              a0 = fma(ar[2 * p], xv[2 * p], a0);
+              a1 = fma(ar[2 * p + 1], xv[2 * p + 1], a1);
+            }
+          }
+        }
+      } else if ((sm_lane<kPlain>() & 15) < M) {  // A has M rows
 #pragma unroll
         for (int p = 0; p < kSmR / 2; ++p) {
           const double2 a = av[p];
           a0 = fma(a.x, xv[2 * p], a0);
           a1 = fma(a.y, xv[2 * p + 1], a1);
         }
-        if (sm_lane() < 16) {
+        if (sm_lane<kPlain>() < 16) {
 #pragma unroll
           for (int p = kSmR / 2; p < kSmY / 2; ++p) {
             const double2 a = av[p];
@@ -249,7 +310,7 @@ __global__ void __launch_bounds__(64, 4)
     // ---- QP (gpc_qp16.h): u(t-1) of the row's MV from lane n
     double xq;
     const double up_row = __shfl(uprev, rcn.n, kWave);
-    iters += gi_qp16<true, PAccT, true>(lds + L.rinv, lds + L.ra, M, Nu, rcn, up_row, xu, tol, maxit, &st, gis, rf,
+    iters += gi_qp16<true, PAccT, !kWideBReg, kPlain>(lds + L.rinv, lds + L.ra, M, Nu, rcn, up_row, xu, tol, maxit, &st, gis, rf,
                      kGiRebuild16, xq
 #ifdef MPCT_PROFILE
                      , pacc, pprev
@@ -258,7 +319,7 @@ __global__ void __launch_bounds__(64, 4)
     PSTAMP(PROF_QP);
     // ---- u update (lane n < nu): first move of MV n, plant input ring, past-control ring
     {
-      const int l = sm_lane();
+      const int l = sm_lane<kPlain>();
       const double du = __shfl(xq, l < nu ? l * Nu : 0, kWave);
       if (l < nu) {
         const double un = uprev + du;
@@ -287,6 +348,29 @@ __global__ void __launch_bounds__(64, 4)
   put_record(out, slot, S, sim, my, nu, lane, j1o, NAN, j22o, NAN, st | (nf ? MPCT_ST_NONFINITE_ : 0), iters);
 }
 
+// four waves per SIMD: 128 VGPRs (no spill since round 6: the QP rows' bounds live in LDS) and 10 KB of
+// LDS, so 16 workgroups fit a CU and the metric's 4096 simulations run in one round.  Against three
+// waves: bitwise the same results, 3.11-3.19 against 3.38-3.46 ms at 8192 candidates, the same
+// 2.21-2.24 ms at 4096 (profiles/r04b_small_ab.txt)
+__global__ void __launch_bounds__(64, 4)
+    gpc_small_kernel(const DevScenario sc, long long C, int nref, const int* __restrict__ N2v,
+                     const int* __restrict__ Nuv, const double* __restrict__ deltav,
+                     const double* __restrict__ lambdav, const double* __restrict__ rv,
+                     const int* __restrict__ perm, const DevOpts o, const DevResult out, int first,
+                     long long slot0, long long nslot) {
+  gpc_small_body<false>(sc, C, nref, N2v, Nuv, deltav, lambdav, rv, perm, o, out, first, slot0, nslot);
+}
+
+// two waves per SIMD, up to 256 VGPRs: the heaviest slots of an ordered launch (launch_closed_loop)
+__global__ void __launch_bounds__(64, 2)
+    gpc_small_wide_kernel(const DevScenario sc, long long C, int nref, const int* __restrict__ N2v,
+                          const int* __restrict__ Nuv, const double* __restrict__ deltav,
+                          const double* __restrict__ lambdav, const double* __restrict__ rv,
+                          const int* __restrict__ perm, const DevOpts o, const DevResult out, int first,
+                          long long slot0, long long nslot) {
+  gpc_small_body<true>(sc, C, nref, N2v, Nuv, deltav, lambdav, rv, perm, o, out, first, slot0, nslot);
+}
+
 }  // namespace mpct
 
 // ------------------------------------------------------------------------------------------
@@ -299,14 +383,15 @@ long long small_lds_bytes(const DevScenario& sc, int M) { return (long long)smal
 
 // the M <= 16 class of a cost-only batch on a small scenario (launch_closed_loop); first: this
 // launch also writes the statuses of skipped / bad-horizon candidates
+// slots slot0 .. slot0 + nslot - 1 of the (ordered) batch, on the wide instance if `wide`
 int launch_small(const DevScenario& sc, long long C, int nref, const int* N2, const int* Nu, const double* delta,
                  const double* lambda, const double* r, const DevOpts& o, const DevResult& out, const int* perm,
-                 int first, hipStream_t stream, std::string* err) {
+                 int first, long long slot0, long long nslot, bool wide, hipStream_t stream, std::string* err) {
   const int nu_cls = sc.numax < 16 / sc.nu ? sc.numax : 16 / sc.nu;
   const long long lds = small_lds_bytes(sc, sc.nu * nu_cls);
-  const long long S = C * nref;
-  hipLaunchKernelGGL(gpc_small_kernel, dim3((unsigned)S), dim3(kWave), (size_t)lds, stream, sc, C, nref, N2, Nu,
-                     delta, lambda, r, perm, o, out, first);
+  if (nslot <= 0) return 0;
+  hipLaunchKernelGGL(wide ? gpc_small_wide_kernel : gpc_small_kernel, dim3((unsigned)nslot), dim3(kWave), (size_t)lds,
+                     stream, sc, C, nref, N2, Nu, delta, lambda, r, perm, o, out, first, slot0, nslot);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     *err = std::string("kernel launch failed: ") + hipGetErrorString(e);

@@ -18,6 +18,28 @@ struct WorkOrder {
   bool pending = false;  // `used` has been recorded
 };
 constexpr long long kOrderMinC = 256;  // at most one workgroup per CU: a single round, order is moot
+
+// The wide split of an ordered metric launch (launch_closed_loop): how many of the first
+// (heaviest) of S slots run on gpc_small_wide_kernel.  cap = 16 ncu is one round of gpc_small_kernel
+// (four waves per SIMD); a wide wave takes the registers of two.
+//   S <= cap / 2       every slot: all of them fit one round of the wide instance (one launch)
+//   S <= cap           as many as still fit the round beside the thin ones (cap - S), and at least
+//                      cap / 4: the lightest simulations end early enough to absorb that many
+//                      (profiles/r08_wide_split_ab.txt: 1024 and 2048 of 4096 best, 512 and 4096 behind)
+//   S > cap            none: several rounds are throughput-bound, and every H > 0 measured slower
+inline long long wide_slot_rule(long long S, int ncu) {
+  const long long cap = 16LL * ncu;
+  if (ncu <= 0 || S < kOrderMinC || S > cap) return 0;
+  if (2 * S <= cap) return S;
+  return cap - S > cap / 4 ? cap - S : cap / 4;
+}
+// H of one launch: none unless it is ordered (and small, cost-only, with a fan: the caller's
+// `eligible`); forced >= 0 (MPCT_WIDE_SLOTS) replaces the rule; never more than S
+inline long long wide_slots(long long S, int ncu, bool eligible, long long forced) {
+  if (!eligible) return 0;
+  const long long h = forced >= 0 ? forced : wide_slot_rule(S, ncu);
+  return h < S ? h : S;
+}
 constexpr int kGramM = 16;                              // QP size of the dispatch-key Gram tables
 constexpr int kGramOut = kGramM * kGramM + kGramM;      // doubles per output and (N2, Nu) block
 constexpr long long kGramMaxBytes = 64ll << 20;         // larger tables are not built

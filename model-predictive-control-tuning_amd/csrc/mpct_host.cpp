@@ -27,7 +27,7 @@ namespace mpct {
 int launch_closed_loop(const DevScenario& sc, long long C, int nref, const int* N2, const int* Nu,
                        const double* delta, const double* lambda, const double* r,
                        const double* v, const DevOpts& o, const DevResult& out, int maxM,
-                       WorkOrder* wo, LaunchFan* fan, hipStream_t stream, std::string* err);
+                       WorkOrder* wo, LaunchFan* fan, long long wide, int ncu, hipStream_t stream, std::string* err);
 long long lds_bytes_for(const DevScenario& sc, int N2, int Nu, bool ext);
 std::string closed_loop_instance(const DevScenario& sc, int maxM, bool ext);
 // defined in mdband_kernel.hip
@@ -96,6 +96,10 @@ static int32_t created(std::unique_ptr<mpct_scenario> s, const BuildError& err, 
   // qr_tables are not packed), so both row sources can be run and timed in one process
   const char* e = getenv("MPCT_NO_QR_TABLES");
   if (e && *e && atoi(e) != 0) s->qr_tables = 0;
+  // MPCT_WIDE_SLOTS=n at creation: this scenario's ordered metric launches run their first n slots on
+  // the wide instance (0: the single launch) instead of the rule's count, for A/B runs and tests
+  const char* w = getenv("MPCT_WIDE_SLOTS");
+  if (w && *w && atoll(w) >= 0) s->wide_slots = atoll(w);
   *out = s.release();
   g_err.clear();
   return MPCT_OK;
@@ -321,9 +325,13 @@ static int launch_batch(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* 
     rc = launch_nmpc(cx->ds, C, nref, N2, Nu, delta, lambda, r, dop, dr, stream, &cx->fan, &cx->order, &err);
   else if (s->mdband)
     rc = launch_mdband(cx->ds, C, nref, N2, Nu, delta, lambda, r, v, dop, dr, stream, &cx->fan, &err);
-  else
+  else {
+    if (cx->ncu == 0 &&
+        (hipDeviceGetAttribute(&cx->ncu, hipDeviceAttributeMultiprocessorCount, cx->dev) != hipSuccess || cx->ncu < 1))
+      cx->ncu = 0;
     rc = launch_closed_loop(cx->ds, C, nref, N2, Nu, delta, lambda, r, v, dop, dr, s->nu * s->numax, &cx->order, &cx->fan,
-                            stream, &err);
+                            s->wide_slots, cx->ncu, stream, &err);
+  }
   if (rc) return fail(rc, err);
 #ifdef MPCT_TIMELINE
   {

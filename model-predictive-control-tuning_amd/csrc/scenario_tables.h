@@ -75,6 +75,9 @@ struct mpct_scenario {
   // 0: no pre-factored prologue rows are packed (qr_tables), the prologue streams [G | Phi] as it
   // does for a scenario over kQrtMaxBytes (mpct_scenario_create: environment MPCT_NO_QR_TABLES)
   int qr_tables = 1;
+  // slots of an ordered metric launch that run on gpc_small_wide_kernel: -1 = the rule
+  // (mpct_dev.h wide_slot_rule), n >= 0 from the environment (MPCT_WIDE_SLOTS=n; 0: one launch)
+  long long wide_slots = -1;
   // device state, one context per device ordinal (created on first use, kept until destroy):
   // a scenario can be evaluated on several GPUs of one process (mpct_eval_batch_multi)
   std::vector<DevCtx*> ctx;
