@@ -1,7 +1,7 @@
 // nmpc_model.h — the Van de Vusse reactor (nmpc_vandevusse_state.m:43-82) as the NMPC kernels
 // integrate it: the model constants, the state derivative with its forward tangent, one sample of
-// fixed-step RK4 (oracle/nmpc_vdv.py rk4), and the Gauss-Newton globalisation constants.  Shared by
-// nmpc_kernel.hip (one simulation per wave) and nmpc_rows.hip (one simulation per 16-lane row).
+// fixed-step RK4 (oracle/nmpc_vdv.py rk4), the Gauss-Newton globalisation constants and the LDS layout.
+// Included by nmpc_kernel.hip (one simulation per wave) and by the test probe tests/device_units/nmpc_probe.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
