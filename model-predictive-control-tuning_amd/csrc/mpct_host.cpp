@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -84,6 +85,11 @@ static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
+}
+
+// the return of a launch wrapper whose device function reports 0, -2 (no memory) or another failure
+static int32_t launch_rc(int rc, const std::string& err) {
+  return rc ? fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err) : MPCT_OK;
 }
 
 extern "C" int32_t mpct_abi_version(void) { return MPCT_ABI_VERSION; }
@@ -406,10 +412,94 @@ extern "C" int32_t mpct_rank_device(const double* costs, int64_t C, int32_t k, c
   if (k < 1) return fail(MPCT_EINVAL, "k < 1");
   if (C > 0 && (!costs || !w || !perm)) return fail(MPCT_EINVAL, "null pointer");
   std::string err;
-  const int rc = rank_device(costs, C, k, w, perm, static_cast<hipStream_t>(stream), &err);
-  if (rc) return fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err);
-  return MPCT_OK;
+  return launch_rc(rank_device(costs, C, k, w, perm, static_cast<hipStream_t>(stream), &err), err);
 }
+
+// Host-pointer staging of one call of a scenario-free entry (mpct_pareto, mpct_hypervolume, mpct_hv_select,
+// mpct_hypervolume_exact, mpct_indices, mpct_draw_stats), the per-call counterpart of HostStage below: a
+// stream and one device blob of this call's own, so the call needs no context and waits for nothing else.
+// An entry reserves its slots before anything touches a device -- in(): a host array to upload, out(): a
+// buffer of the caller's to fill -- then open()s, launches on `st` with at<T>(slot) as the device addresses
+// and close()s with the launch's return code, whatever open() returned.
+// A slot with a NULL host pointer or no bytes reserves nothing and its device address is NULL: a result
+// field that is not asked for, members == NULL, alive == NULL and the trajectories mpct_indices has no use
+// for reach the launch as NULL.
+namespace {
+struct CallStage {
+  // the entry's words in the messages: "<entry> failed on the device", "hipMalloc failed (<staging>)",
+  // "hipMemcpyAsync failed (<inputs>)", "hipMemcpyAsync failed (<results>)"
+  const char *entry, *staging, *inputs, *results;
+  static constexpr int kMaxSlots = 16;  // mpct_indices, the widest entry: 3 trajectories and 13 fields
+  struct Slot {
+    void* host;  // NULL: nothing reserved
+    size_t bytes, off;
+    bool in;
+  } slots[kMaxSlots] = {};
+  int nslots = 0;
+  size_t off = 0;  // bytes reserved so far
+  hipStream_t st = nullptr;
+  char* blob = nullptr;
+  int cur = -1;           // the caller's device
+  bool switched = false;  // open() made another device current
+  bool staged = false;    // open() got its stream and blob: close() has work to wait for
+
+  // reserve a 256-B-aligned slot of the blob; its address holds after open()
+  int slot(const void* host, size_t bytes, bool in) {
+    assert(nslots < kMaxSlots);
+    Slot& s = slots[nslots];
+    if (host && bytes) {
+      s = Slot{const_cast<void*>(host), bytes, off, in};
+      off += (bytes + 255) & ~(size_t)255;
+    }
+    return nslots++;
+  }
+  int in(const void* host, size_t bytes) { return slot(host, bytes, true); }
+  int out(void* host, size_t bytes) { return slot(host, bytes, false); }
+  template <class T>
+  T* at(int i) const { return slots[i].host ? reinterpret_cast<T*>(blob + slots[i].off) : nullptr; }
+
+  // make `device` (< 0: the current one) current, create the stream and the blob, enqueue the H2D copies
+  int open(int device) {
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
+      return fail(MPCT_EDEVICE, std::string("no HIP device (") + entry + " needs a GPU)");
+    const int dev = device < 0 ? cur : device;
+    if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
+    if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
+    switched = dev != cur;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return fail(MPCT_EDEVICE, "hipStreamCreate failed");
+    if (hipMalloc(reinterpret_cast<void**>(&blob), off) != hipSuccess)
+      return fail(MPCT_ENOMEM, std::string("hipMalloc failed (") + staging + ")");
+    staged = true;
+    for (int i = 0; i < nslots; ++i) {
+      const Slot& s = slots[i];
+      if (s.host && s.in && hipMemcpyAsync(blob + s.off, s.host, s.bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(MPCT_EDEVICE, std::string("hipMemcpyAsync failed (") + inputs + ")");
+    }
+    return MPCT_OK;
+  }
+
+  // rc: what open() or the launch returned.  MPCT_OK: enqueue the D2H copies of the out() slots.  Always: wait
+  // for this call's stream, free what open() got and give the caller's device back.  The first error wins
+  int close(int rc) {
+    if (staged) {
+      for (int i = 0; rc == MPCT_OK && i < nslots; ++i) {
+        const Slot& s = slots[i];
+        if (s.host && !s.in && hipMemcpyAsync(s.host, blob + s.off, s.bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+          rc = fail(MPCT_EDEVICE, std::string("hipMemcpyAsync failed (") + results + ")");
+      }
+      // this call's stream only, also after an error: the blob is freed below
+      const hipError_t se = hipStreamSynchronize(st);
+      if (rc == MPCT_OK && se != hipSuccess)
+        rc = fail(MPCT_EDEVICE, std::string(entry) + " failed on the device: " + hipGetErrorString(se));
+    }
+    if (blob) (void)hipFree(blob);
+    if (st) (void)hipStreamDestroy(st);
+    if (switched) (void)hipSetDevice(cur);
+    return rc;
+  }
+};
+}  // namespace
 
 // ---- Pareto front, domination counts and layers (pareto.hip).  The argument checks of both entries,
 // in the order include/mpct.h states, before any device is touched
@@ -430,9 +520,7 @@ static int32_t pareto_launch(const double* costs, int64_t C, int32_t k, int32_t 
                              hipStream_t stream, int tile, int split) {
   std::string err;
   const ParetoOut po{out->dom_count, out->layer, out->front, out->n_front};
-  const int rc = pareto_device(costs, C, k, max_layers, po, stream, &err, tile, split);
-  if (rc) return fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err);
-  return MPCT_OK;
+  return launch_rc(pareto_device(costs, C, k, max_layers, po, stream, &err, tile, split), err);
 }
 
 extern "C" int32_t mpct_pareto_device(const double* costs, int64_t C, int32_t k, int32_t max_layers,
@@ -471,51 +559,21 @@ extern "C" int32_t mpct_pareto(const double* costs, int64_t C, int32_t k, int32_
     if (out->n_front) out->n_front[0] = 0;
     return MPCT_OK;
   }
-  int cur = -1, cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
-    return fail(MPCT_EDEVICE, "no HIP device (mpct_pareto needs a GPU)");
-  const int dev = device < 0 ? cur : device;
-  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
-  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
-  // one blob: costs | dom_count | layer | front | n_front, each 256-B aligned; a stream of this call's own
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t nc = al((size_t)C * k * sizeof(double)), ni = al((size_t)C * sizeof(int32_t));
-  hipStream_t st = nullptr;
-  char* blob = nullptr;
-  rc = MPCT_OK;
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
-  } else if (hipMalloc(reinterpret_cast<void**>(&blob), nc + 3 * ni + 256) != hipSuccess) {
-    rc = fail(MPCT_ENOMEM, "hipMalloc failed (Pareto staging)");
-  } else {
+  CallStage cs{"mpct_pareto", "Pareto staging", "costs", "Pareto results"};
+  const size_t bi = (size_t)C * sizeof(int32_t);
+  const int s_costs = cs.in(costs, (size_t)C * k * sizeof(double));
+  const int s_dom = cs.out(out->dom_count, bi), s_layer = cs.out(out->layer, bi), s_front = cs.out(out->front, bi),
+            s_nfront = cs.out(out->n_front, sizeof(int32_t));
+  rc = cs.open(device);
+  if (rc == MPCT_OK) {
     mpct_pareto_result d{};
-    d.dom_count = out->dom_count ? reinterpret_cast<int32_t*>(blob + nc) : nullptr;
-    d.layer = out->layer ? reinterpret_cast<int32_t*>(blob + nc + ni) : nullptr;
-    d.front = out->front ? reinterpret_cast<int32_t*>(blob + nc + 2 * ni) : nullptr;
-    d.n_front = out->n_front ? reinterpret_cast<int32_t*>(blob + nc + 3 * ni) : nullptr;
-    bool ok = hipMemcpyAsync(blob, costs, (size_t)C * k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (costs)");
-    if (ok) {
-      rc = pareto_launch(reinterpret_cast<const double*>(blob), C, k, max_layers, &d, st, 0, 0);
-      ok = rc == MPCT_OK;
-    }
-    if (ok) {
-      const size_t bi = (size_t)C * sizeof(int32_t);
-      ok = (!d.dom_count || hipMemcpyAsync(out->dom_count, d.dom_count, bi, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.layer || hipMemcpyAsync(out->layer, d.layer, bi, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.front || hipMemcpyAsync(out->front, d.front, bi, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.n_front || hipMemcpyAsync(out->n_front, d.n_front, sizeof(int32_t), hipMemcpyDeviceToHost, st) == hipSuccess);
-      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (Pareto results)");
-    }
-    // this call's stream only, also after an error: the blob is freed below
-    const hipError_t se = hipStreamSynchronize(st);
-    if (rc == MPCT_OK && se != hipSuccess)
-      rc = fail(MPCT_EDEVICE, std::string("mpct_pareto failed on the device: ") + hipGetErrorString(se));
+    d.dom_count = cs.at<int32_t>(s_dom);
+    d.layer = cs.at<int32_t>(s_layer);
+    d.front = cs.at<int32_t>(s_front);
+    d.n_front = cs.at<int32_t>(s_nfront);
+    rc = pareto_launch(cs.at<double>(s_costs), C, k, max_layers, &d, cs.st, 0, 0);
   }
-  if (blob) (void)hipFree(blob);
-  if (st) (void)hipStreamDestroy(st);
-  if (dev != cur) (void)hipSetDevice(cur);
-  return rc;
+  return cs.close(rc);
 }
 
 // ---- Hypervolume of a front and per-member contributions (hypervolume.hip).  The argument checks of both
@@ -548,6 +606,22 @@ static int hv_check(const double* costs, int64_t C, int32_t k, const int32_t* me
   return MPCT_OK;
 }
 
+// the checks that read the caller's arrays, which only the host entries can make: the box and the entries of
+// members (mpct_hypervolume, mpct_hv_select, mpct_hypervolume_exact).  *vol, where asked for: the box volume
+static int hv_check_box_members(int32_t k, const double* lo, const double* ref, const int32_t* members, int64_t M, int64_t C,
+                                double* vol = nullptr) {
+  double v = 1.0;
+  for (int j = 0; j < k; ++j) {
+    if (!std::isfinite(lo[j]) || !std::isfinite(ref[j]) || !(lo[j] < ref[j]))
+      return fail(MPCT_EINVAL, "the box needs finite lo and ref with lo[j] < ref[j]");
+    v *= ref[j] - lo[j];
+  }
+  for (int64_t m = 0; members && m < M; ++m)
+    if (members[m] < -1 || members[m] >= C) return fail(MPCT_EINVAL, "an entry of members is below -1 or >= C");
+  if (vol) *vol = v;
+  return MPCT_OK;
+}
+
 // tile length (128 or 256; 0: the default) and the largest grid in workgroups (0: the default) of
 // hv_count_kernel.  A test hook, not part of include/mpct.h: the tests reach the multi-tile and striding
 // paths at small shapes with it, tools/hv_bench.py runs its A/B with it
@@ -564,9 +638,7 @@ static int32_t hv_launch(const double* costs, int64_t C, int32_t k, const int32_
   std::string err;
   const HvOut ho{reinterpret_cast<long long*>(out->n_covered), reinterpret_cast<long long*>(out->excl),
                  reinterpret_cast<long long*>(out->depth_hist), out->hv};
-  const int rc = hypervolume_device(costs, C, k, members, M, lo, ref, N, seed, ho, stream, &err, g_hv_tile, g_hv_blocks);
-  if (rc) return fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err);
-  return MPCT_OK;
+  return launch_rc(hypervolume_device(costs, C, k, members, M, lo, ref, N, seed, ho, stream, &err, g_hv_tile, g_hv_blocks), err);
 }
 
 extern "C" int32_t mpct_hypervolume_device(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
@@ -583,72 +655,30 @@ extern "C" int32_t mpct_hypervolume(const double* costs, int64_t C, int32_t k, c
   int rc = hv_check(costs, C, k, members, M, lo, ref, n_samples, out);
   if (rc) return rc;
   double vol = 1.0;
-  for (int j = 0; j < k; ++j) {
-    if (!std::isfinite(lo[j]) || !std::isfinite(ref[j]) || !(lo[j] < ref[j]))
-      return fail(MPCT_EINVAL, "the box needs finite lo and ref with lo[j] < ref[j]");
-    vol *= ref[j] - lo[j];
-  }
-  for (int64_t m = 0; members && m < M; ++m)
-    if (members[m] < -1 || members[m] >= C) return fail(MPCT_EINVAL, "an entry of members is below -1 or >= C");
+  rc = hv_check_box_members(k, lo, ref, members, M, C, &vol);
+  if (rc) return rc;
   if (M == 0) {  // nothing to stage
     if (out->n_covered) out->n_covered[0] = 0;
     for (int b = 0; out->depth_hist && b < MPCT_HV_BINS; ++b) out->depth_hist[b] = b ? 0 : n_samples;
     if (out->hv) out->hv[0] = (0.0 / (double)n_samples) * vol;
     return MPCT_OK;
   }
-  int cur = -1, cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
-    return fail(MPCT_EDEVICE, "no HIP device (mpct_hypervolume needs a GPU)");
-  const int dev = device < 0 ? cur : device;
-  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
-  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
-  // one blob: costs | members | lo | ref | excl | n_covered, depth_hist, hv; each 256-B aligned; a stream of this call's own
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t nc = al((size_t)C * k * sizeof(double)), nm = al((size_t)M * sizeof(int32_t)), nb = al((size_t)k * sizeof(double)),
-               ne = al((size_t)M * sizeof(int64_t));
-  hipStream_t st = nullptr;
-  char* blob = nullptr;
-  rc = MPCT_OK;
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
-  } else if (hipMalloc(reinterpret_cast<void**>(&blob), nc + nm + 2 * nb + ne + 3 * 256) != hipSuccess) {
-    rc = fail(MPCT_ENOMEM, "hipMalloc failed (hypervolume staging)");
-  } else {
-    double* dcosts = reinterpret_cast<double*>(blob);
-    int32_t* dmem = members ? reinterpret_cast<int32_t*>(blob + nc) : nullptr;
-    double* dlo = reinterpret_cast<double*>(blob + nc + nm);
-    double* dref = reinterpret_cast<double*>(blob + nc + nm + nb);
-    char* tail = blob + nc + nm + 2 * nb + ne;
+  CallStage cs{"mpct_hypervolume", "hypervolume staging", "hypervolume inputs", "hypervolume results"};
+  const int s_costs = cs.in(costs, (size_t)C * k * sizeof(double)), s_mem = cs.in(members, (size_t)M * sizeof(int32_t)),
+            s_lo = cs.in(lo, (size_t)k * sizeof(double)), s_ref = cs.in(ref, (size_t)k * sizeof(double));
+  const int s_excl = cs.out(out->excl, (size_t)M * sizeof(int64_t)), s_ncov = cs.out(out->n_covered, sizeof(int64_t)),
+            s_hist = cs.out(out->depth_hist, MPCT_HV_BINS * sizeof(int64_t)), s_hv = cs.out(out->hv, sizeof(double));
+  rc = cs.open(device);
+  if (rc == MPCT_OK) {
     mpct_hv_result d{};
-    d.excl = out->excl ? reinterpret_cast<int64_t*>(blob + nc + nm + 2 * nb) : nullptr;
-    d.n_covered = out->n_covered ? reinterpret_cast<int64_t*>(tail) : nullptr;
-    d.depth_hist = out->depth_hist ? reinterpret_cast<int64_t*>(tail + 256) : nullptr;
-    d.hv = out->hv ? reinterpret_cast<double*>(tail + 512) : nullptr;
-    bool ok = hipMemcpyAsync(dcosts, costs, (size_t)C * k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-              (!dmem || hipMemcpyAsync(dmem, members, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, st) == hipSuccess) &&
-              hipMemcpyAsync(dlo, lo, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(dref, ref, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hypervolume inputs)");
-    if (ok) {
-      rc = hv_launch(dcosts, C, k, dmem, M, dlo, dref, n_samples, seed, &d, st);
-      ok = rc == MPCT_OK;
-    }
-    if (ok) {
-      ok = (!d.excl || hipMemcpyAsync(out->excl, d.excl, (size_t)M * sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.n_covered || hipMemcpyAsync(out->n_covered, d.n_covered, sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.depth_hist || hipMemcpyAsync(out->depth_hist, d.depth_hist, MPCT_HV_BINS * sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.hv || hipMemcpyAsync(out->hv, d.hv, sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess);
-      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hypervolume results)");
-    }
-    // this call's stream only, also after an error: the blob is freed below
-    const hipError_t se = hipStreamSynchronize(st);
-    if (rc == MPCT_OK && se != hipSuccess)
-      rc = fail(MPCT_EDEVICE, std::string("mpct_hypervolume failed on the device: ") + hipGetErrorString(se));
+    d.n_covered = cs.at<int64_t>(s_ncov);
+    d.excl = cs.at<int64_t>(s_excl);
+    d.depth_hist = cs.at<int64_t>(s_hist);
+    d.hv = cs.at<double>(s_hv);
+    rc = hv_launch(cs.at<double>(s_costs), C, k, cs.at<int32_t>(s_mem), M, cs.at<double>(s_lo), cs.at<double>(s_ref), n_samples,
+                   seed, &d, cs.st);
   }
-  if (blob) (void)hipFree(blob);
-  if (st) (void)hipStreamDestroy(st);
-  if (dev != cur) (void)hipSetDevice(cur);
-  return rc;
+  return cs.close(rc);
 }
 
 // ---- Greedy hypervolume subset selection (hv_select.hip).  The argument checks of both entries, in the
@@ -697,10 +727,9 @@ static int32_t hvsel_launch(const double* costs, int64_t C, int32_t k, const int
   float* round_ms = n_pick <= g_hvsel_round_n ? g_hvsel_round_ms : nullptr;  // never past the tool's array
   g_hvsel_round_ms = nullptr;                                                // one call only
   g_hvsel_round_n = 0;
-  const int rc = hv_select_device(costs, C, k, members, M, lo, ref, N, seed, n_pick, so, stream, &err, g_hvsel_tile,
-                                  g_hvsel_blocks, round_ms);
-  if (rc) return fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err);
-  return MPCT_OK;
+  return launch_rc(hv_select_device(costs, C, k, members, M, lo, ref, N, seed, n_pick, so, stream, &err, g_hvsel_tile,
+                                    g_hvsel_blocks, round_ms),
+                   err);
 }
 
 extern "C" int32_t mpct_hv_select_device(const double* costs, int64_t C, int32_t k, const int32_t* members, int64_t M,
@@ -717,13 +746,8 @@ extern "C" int32_t mpct_hv_select(const double* costs, int64_t C, int32_t k, con
   int rc = hvsel_check(costs, C, k, members, M, lo, ref, n_samples, n_pick, out);
   if (rc) return rc;
   double vol = 1.0;
-  for (int j = 0; j < k; ++j) {
-    if (!std::isfinite(lo[j]) || !std::isfinite(ref[j]) || !(lo[j] < ref[j]))
-      return fail(MPCT_EINVAL, "the box needs finite lo and ref with lo[j] < ref[j]");
-    vol *= ref[j] - lo[j];
-  }
-  for (int64_t m = 0; members && m < M; ++m)
-    if (members[m] < -1 || members[m] >= C) return fail(MPCT_EINVAL, "an entry of members is below -1 or >= C");
+  rc = hv_check_box_members(k, lo, ref, members, M, C, &vol);
+  if (rc) return rc;
   if (M == 0) {  // nothing to stage: the end-of-selection fill from slot 0
     if (out->n_picked) out->n_picked[0] = 0;
     if (out->n_covered_all) out->n_covered_all[0] = 0;
@@ -737,70 +761,28 @@ extern "C" int32_t mpct_hv_select(const double* costs, int64_t C, int32_t k, con
     }
     return MPCT_OK;
   }
-  int cur = -1, cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
-    return fail(MPCT_EDEVICE, "no HIP device (mpct_hv_select needs a GPU)");
-  const int dev = device < 0 ? cur : device;
-  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
-  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
-  // one blob: costs | members | lo | ref | pos, index, ties (int32 [K]) | gain, covered, hv (8 B [K]) |
-  // n_picked, n_covered_all; each 256-B aligned; a stream of this call's own
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t nc = al((size_t)C * k * sizeof(double)), nm = al((size_t)M * sizeof(int32_t)), nb = al((size_t)k * sizeof(double)),
-               n4 = al((size_t)n_pick * sizeof(int32_t)), n8 = al((size_t)n_pick * sizeof(int64_t));
-  hipStream_t st = nullptr;
-  char* blob = nullptr;
-  rc = MPCT_OK;
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
-  } else if (hipMalloc(reinterpret_cast<void**>(&blob), nc + nm + 2 * nb + 3 * n4 + 3 * n8 + 2 * 256) != hipSuccess) {
-    rc = fail(MPCT_ENOMEM, "hipMalloc failed (hv_select staging)");
-  } else {
-    double* dcosts = reinterpret_cast<double*>(blob);
-    int32_t* dmem = members ? reinterpret_cast<int32_t*>(blob + nc) : nullptr;
-    double* dlo = reinterpret_cast<double*>(blob + nc + nm);
-    double* dref = reinterpret_cast<double*>(blob + nc + nm + nb);
-    char* res = blob + nc + nm + 2 * nb;
+  CallStage cs{"mpct_hv_select", "hv_select staging", "hv_select inputs", "hv_select results"};
+  const size_t b4 = (size_t)n_pick * sizeof(int32_t), b8 = (size_t)n_pick * sizeof(int64_t);
+  const int s_costs = cs.in(costs, (size_t)C * k * sizeof(double)), s_mem = cs.in(members, (size_t)M * sizeof(int32_t)),
+            s_lo = cs.in(lo, (size_t)k * sizeof(double)), s_ref = cs.in(ref, (size_t)k * sizeof(double));
+  const int s_pos = cs.out(out->pos, b4), s_index = cs.out(out->index, b4), s_ties = cs.out(out->ties, b4),
+            s_gain = cs.out(out->gain, b8), s_covered = cs.out(out->covered, b8), s_hv = cs.out(out->hv, b8),
+            s_npicked = cs.out(out->n_picked, sizeof(int64_t)), s_nall = cs.out(out->n_covered_all, sizeof(int64_t));
+  rc = cs.open(device);
+  if (rc == MPCT_OK) {
     mpct_hv_select_result d{};
-    d.pos = out->pos ? reinterpret_cast<int32_t*>(res) : nullptr;
-    d.index = out->index ? reinterpret_cast<int32_t*>(res + n4) : nullptr;
-    d.ties = out->ties ? reinterpret_cast<int32_t*>(res + 2 * n4) : nullptr;
-    d.gain = out->gain ? reinterpret_cast<int64_t*>(res + 3 * n4) : nullptr;
-    d.covered = out->covered ? reinterpret_cast<int64_t*>(res + 3 * n4 + n8) : nullptr;
-    d.hv = out->hv ? reinterpret_cast<double*>(res + 3 * n4 + 2 * n8) : nullptr;
-    d.n_picked = out->n_picked ? reinterpret_cast<int64_t*>(res + 3 * n4 + 3 * n8) : nullptr;
-    d.n_covered_all = out->n_covered_all ? reinterpret_cast<int64_t*>(res + 3 * n4 + 3 * n8 + 256) : nullptr;
-    bool ok = hipMemcpyAsync(dcosts, costs, (size_t)C * k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-              (!dmem || hipMemcpyAsync(dmem, members, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, st) == hipSuccess) &&
-              hipMemcpyAsync(dlo, lo, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(dref, ref, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hv_select inputs)");
-    if (ok) {
-      rc = hvsel_launch(dcosts, C, k, dmem, M, dlo, dref, n_samples, seed, n_pick, &d, st);
-      ok = rc == MPCT_OK;
-    }
-    if (ok) {
-      const size_t b4 = (size_t)n_pick * sizeof(int32_t), b8 = (size_t)n_pick * sizeof(int64_t);
-      ok = (!d.pos || hipMemcpyAsync(out->pos, d.pos, b4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.index || hipMemcpyAsync(out->index, d.index, b4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.ties || hipMemcpyAsync(out->ties, d.ties, b4, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.gain || hipMemcpyAsync(out->gain, d.gain, b8, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.covered || hipMemcpyAsync(out->covered, d.covered, b8, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.hv || hipMemcpyAsync(out->hv, d.hv, b8, hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.n_picked || hipMemcpyAsync(out->n_picked, d.n_picked, sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.n_covered_all ||
-            hipMemcpyAsync(out->n_covered_all, d.n_covered_all, sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess);
-      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hv_select results)");
-    }
-    // this call's stream only, also after an error: the blob is freed below
-    const hipError_t se = hipStreamSynchronize(st);
-    if (rc == MPCT_OK && se != hipSuccess)
-      rc = fail(MPCT_EDEVICE, std::string("mpct_hv_select failed on the device: ") + hipGetErrorString(se));
+    d.n_picked = cs.at<int64_t>(s_npicked);
+    d.pos = cs.at<int32_t>(s_pos);
+    d.index = cs.at<int32_t>(s_index);
+    d.gain = cs.at<int64_t>(s_gain);
+    d.covered = cs.at<int64_t>(s_covered);
+    d.hv = cs.at<double>(s_hv);
+    d.ties = cs.at<int32_t>(s_ties);
+    d.n_covered_all = cs.at<int64_t>(s_nall);
+    rc = hvsel_launch(cs.at<double>(s_costs), C, k, cs.at<int32_t>(s_mem), M, cs.at<double>(s_lo), cs.at<double>(s_ref),
+                      n_samples, seed, n_pick, &d, cs.st);
   }
-  if (blob) (void)hipFree(blob);
-  if (st) (void)hipStreamDestroy(st);
-  if (dev != cur) (void)hipSetDevice(cur);
-  return rc;
+  return cs.close(rc);
 }
 
 // ---- Exact hypervolume and contributions for k <= 3 (hypervolume_exact.hip).  The argument checks of both
@@ -822,9 +804,7 @@ static int32_t hvx_launch(const double* costs, int64_t C, int32_t k, const int32
                           const double* ref, const mpct_hvx_result* out, hipStream_t stream) {
   std::string err;
   const HvxOut ho{out->hv, out->excl, reinterpret_cast<long long*>(out->n_active)};
-  const int rc = hypervolume_exact_device(costs, C, k, members, M, lo, ref, ho, stream, &err);
-  if (rc) return fail(rc == -2 ? MPCT_ENOMEM : MPCT_EDEVICE, err);
-  return MPCT_OK;
+  return launch_rc(hypervolume_exact_device(costs, C, k, members, M, lo, ref, ho, stream, &err), err);
 }
 
 extern "C" int32_t mpct_hypervolume_exact_device(const double* costs, int64_t C, int32_t k, const int32_t* members,
@@ -840,67 +820,27 @@ extern "C" int32_t mpct_hypervolume_exact(const double* costs, int64_t C, int32_
                                           const mpct_hvx_result* out) {
   int rc = hvx_check(costs, C, k, members, M, lo, ref, out);
   if (rc) return rc;
-  for (int j = 0; j < k; ++j)
-    if (!std::isfinite(lo[j]) || !std::isfinite(ref[j]) || !(lo[j] < ref[j]))
-      return fail(MPCT_EINVAL, "the box needs finite lo and ref with lo[j] < ref[j]");
-  for (int64_t m = 0; members && m < M; ++m)
-    if (members[m] < -1 || members[m] >= C) return fail(MPCT_EINVAL, "an entry of members is below -1 or >= C");
+  rc = hv_check_box_members(k, lo, ref, members, M, C);
+  if (rc) return rc;
   if (M == 0) {  // nothing to stage
     if (out->hv) out->hv[0] = 0.0;
     if (out->n_active) out->n_active[0] = 0;
     return MPCT_OK;
   }
-  int cur = -1, cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
-    return fail(MPCT_EDEVICE, "no HIP device (mpct_hypervolume_exact needs a GPU)");
-  const int dev = device < 0 ? cur : device;
-  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
-  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
-  // one blob: costs | members | lo | ref | excl | hv, n_active; each 256-B aligned; a stream of this call's own
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t nc = al((size_t)C * k * sizeof(double)), nm = al((size_t)M * sizeof(int32_t)), nb = al((size_t)k * sizeof(double)),
-               ne = al((size_t)M * sizeof(double));
-  hipStream_t st = nullptr;
-  char* blob = nullptr;
-  rc = MPCT_OK;
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
-  } else if (hipMalloc(reinterpret_cast<void**>(&blob), nc + nm + 2 * nb + ne + 2 * 256) != hipSuccess) {
-    rc = fail(MPCT_ENOMEM, "hipMalloc failed (hypervolume_exact staging)");
-  } else {
-    double* dcosts = reinterpret_cast<double*>(blob);
-    int32_t* dmem = members ? reinterpret_cast<int32_t*>(blob + nc) : nullptr;
-    double* dlo = reinterpret_cast<double*>(blob + nc + nm);
-    double* dref = reinterpret_cast<double*>(blob + nc + nm + nb);
-    char* tail = blob + nc + nm + 2 * nb + ne;
+  CallStage cs{"mpct_hypervolume_exact", "hypervolume_exact staging", "hypervolume_exact inputs", "hypervolume_exact results"};
+  const int s_costs = cs.in(costs, (size_t)C * k * sizeof(double)), s_mem = cs.in(members, (size_t)M * sizeof(int32_t)),
+            s_lo = cs.in(lo, (size_t)k * sizeof(double)), s_ref = cs.in(ref, (size_t)k * sizeof(double));
+  const int s_excl = cs.out(out->excl, (size_t)M * sizeof(double)), s_hv = cs.out(out->hv, sizeof(double)),
+            s_nactive = cs.out(out->n_active, sizeof(int64_t));
+  rc = cs.open(device);
+  if (rc == MPCT_OK) {
     mpct_hvx_result d{};
-    d.excl = out->excl ? reinterpret_cast<double*>(blob + nc + nm + 2 * nb) : nullptr;
-    d.hv = out->hv ? reinterpret_cast<double*>(tail) : nullptr;
-    d.n_active = out->n_active ? reinterpret_cast<int64_t*>(tail + 256) : nullptr;
-    bool ok = hipMemcpyAsync(dcosts, costs, (size_t)C * k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-              (!dmem || hipMemcpyAsync(dmem, members, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, st) == hipSuccess) &&
-              hipMemcpyAsync(dlo, lo, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(dref, ref, (size_t)k * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
-    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hypervolume_exact inputs)");
-    if (ok) {
-      rc = hvx_launch(dcosts, C, k, dmem, M, dlo, dref, &d, st);
-      ok = rc == MPCT_OK;
-    }
-    if (ok) {
-      ok = (!d.excl || hipMemcpyAsync(out->excl, d.excl, (size_t)M * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.hv || hipMemcpyAsync(out->hv, d.hv, sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess) &&
-           (!d.n_active || hipMemcpyAsync(out->n_active, d.n_active, sizeof(int64_t), hipMemcpyDeviceToHost, st) == hipSuccess);
-      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (hypervolume_exact results)");
-    }
-    // this call's stream only, also after an error: the blob is freed below
-    const hipError_t se = hipStreamSynchronize(st);
-    if (rc == MPCT_OK && se != hipSuccess)
-      rc = fail(MPCT_EDEVICE, std::string("mpct_hypervolume_exact failed on the device: ") + hipGetErrorString(se));
+    d.hv = cs.at<double>(s_hv);
+    d.excl = cs.at<double>(s_excl);
+    d.n_active = cs.at<int64_t>(s_nactive);
+    rc = hvx_launch(cs.at<double>(s_costs), C, k, cs.at<int32_t>(s_mem), M, cs.at<double>(s_lo), cs.at<double>(s_ref), &d, cs.st);
   }
-  if (blob) (void)hipFree(blob);
-  if (st) (void)hipStreamDestroy(st);
-  if (dev != cur) (void)hipSetDevice(cur);
-  return rc;
+  return cs.close(rc);
 }
 
 // Host-pointer staging of one call on the context's own stream, shared by eval_host and
@@ -1479,67 +1419,36 @@ extern "C" int32_t mpct_indices(const double* y, const double* u, const double* 
   int rc = index_check(y, u, r, S, nref, my, nu, nit, params, out);
   if (rc) return rc;
   if (S == 0) return MPCT_OK;  // nothing to stage
-  int cur = -1, cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
-    return fail(MPCT_EDEVICE, "no HIP device (mpct_indices needs a GPU)");
-  const int dev = device < 0 ? cur : device;
-  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
-  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
-  // one blob: y | u | r | the thirteen fields, each 256-B aligned; a stream of this call's own
   const IndexOut ho = index_out(out);
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t yb = ho.any_y() ? (size_t)S * my * nit * 8 : 0, rb = ho.any_y() ? (size_t)nref * my * nit * 8 : 0;
-  const size_t ub = ho.any_u() ? (size_t)S * nu * nit * 8 : 0;
-  const size_t fy = al((size_t)S * my * 8), fu = al((size_t)S * nu * 8);
-  const size_t o_u = al(yb), o_r = o_u + al(ub), o_f = o_r + al(rb);
-  hipStream_t st = nullptr;
-  char* blob = nullptr;
-  rc = MPCT_OK;
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
-  } else if (hipMalloc(reinterpret_cast<void**>(&blob), o_f + 8 * fy + 5 * fu + 256) != hipSuccess) {
-    rc = fail(MPCT_ENOMEM, "hipMalloc failed (index staging)");
-  } else {
-    // the device slot of field k (0..7 output rows, 8..12 input rows), null where the caller asks for none
-    auto slot = [&](const void* want, int k) -> char* {
-      return want ? blob + o_f + (k < 8 ? k * fy : 8 * fy + (k - 8) * fu) : nullptr;
-    };
-    const IndexOut dv{(double*)slot(ho.iae, 0),   (double*)slot(ho.ise, 1),     (double*)slot(ho.itae, 2),
-                      (double*)slot(ho.emax, 3),  (int*)slot(ho.t_emax, 4),     (double*)slot(ho.over, 5),
-                      (double*)slot(ho.e_final, 6), (int*)slot(ho.settle, 7),   (double*)slot(ho.tv, 8),
-                      (double*)slot(ho.du2, 9),   (double*)slot(ho.dumax, 10),  (double*)slot(ho.u_lo, 11),
-                      (double*)slot(ho.u_hi, 12)};
-    auto h2d = [&](size_t o, const void* p, size_t b) {
-      return b == 0 || hipMemcpyAsync(blob + o, p, b, hipMemcpyHostToDevice, st) == hipSuccess;
-    };
-    bool ok = h2d(0, y, yb) && h2d(o_u, u, ub) && h2d(o_r, r, rb);
-    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (trajectories)");
-    if (ok) {
-      rc = index_launch(yb ? reinterpret_cast<const double*>(blob) : nullptr,
-                        ub ? reinterpret_cast<const double*>(blob + o_u) : nullptr,
-                        rb ? reinterpret_cast<const double*>(blob + o_r) : nullptr, S, nref, my, nu, nit, params, dv, st);
-      ok = rc == MPCT_OK;
-    }
-    if (ok) {
-      auto d2h = [&](void* dst, const void* src, size_t b) {
-        return !dst || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, st) == hipSuccess;
-      };
-      const size_t dy = (size_t)S * my * 8, iy = (size_t)S * my * 4, du = (size_t)S * nu * 8;
-      ok = d2h(ho.iae, dv.iae, dy) && d2h(ho.ise, dv.ise, dy) && d2h(ho.itae, dv.itae, dy) && d2h(ho.emax, dv.emax, dy) &&
-           d2h(ho.t_emax, dv.t_emax, iy) && d2h(ho.over, dv.over, dy) && d2h(ho.e_final, dv.e_final, dy) &&
-           d2h(ho.settle, dv.settle, iy) && d2h(ho.tv, dv.tv, du) && d2h(ho.du2, dv.du2, du) &&
-           d2h(ho.dumax, dv.dumax, du) && d2h(ho.u_lo, dv.u_lo, du) && d2h(ho.u_hi, dv.u_hi, du);
-      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (index records)");
-    }
-    // this call's stream only, also after an error: the blob is freed below
-    const hipError_t se = hipStreamSynchronize(st);
-    if (rc == MPCT_OK && se != hipSuccess)
-      rc = fail(MPCT_EDEVICE, std::string("mpct_indices failed on the device: ") + hipGetErrorString(se));
+  CallStage cs{"mpct_indices", "index staging", "trajectories", "index records"};
+  // y and r travel only behind an output-row field, u only behind an input-row field
+  const int s_y = cs.in(ho.any_y() ? y : nullptr, (size_t)S * my * nit * 8),
+            s_u = cs.in(ho.any_u() ? u : nullptr, (size_t)S * nu * nit * 8),
+            s_r = cs.in(ho.any_y() ? r : nullptr, (size_t)nref * my * nit * 8);
+  const size_t dy = (size_t)S * my * 8, iy = (size_t)S * my * 4, du = (size_t)S * nu * 8;
+  const int s_iae = cs.out(ho.iae, dy), s_ise = cs.out(ho.ise, dy), s_itae = cs.out(ho.itae, dy), s_emax = cs.out(ho.emax, dy),
+            s_temax = cs.out(ho.t_emax, iy), s_over = cs.out(ho.over, dy), s_efinal = cs.out(ho.e_final, dy),
+            s_settle = cs.out(ho.settle, iy), s_tv = cs.out(ho.tv, du), s_du2 = cs.out(ho.du2, du),
+            s_dumax = cs.out(ho.dumax, du), s_ulo = cs.out(ho.u_lo, du), s_uhi = cs.out(ho.u_hi, du);
+  rc = cs.open(device);
+  if (rc == MPCT_OK) {
+    IndexOut dv{};
+    dv.iae = cs.at<double>(s_iae);
+    dv.ise = cs.at<double>(s_ise);
+    dv.itae = cs.at<double>(s_itae);
+    dv.emax = cs.at<double>(s_emax);
+    dv.t_emax = cs.at<int>(s_temax);
+    dv.over = cs.at<double>(s_over);
+    dv.e_final = cs.at<double>(s_efinal);
+    dv.settle = cs.at<int>(s_settle);
+    dv.tv = cs.at<double>(s_tv);
+    dv.du2 = cs.at<double>(s_du2);
+    dv.dumax = cs.at<double>(s_dumax);
+    dv.u_lo = cs.at<double>(s_ulo);
+    dv.u_hi = cs.at<double>(s_uhi);
+    rc = index_launch(cs.at<double>(s_y), cs.at<double>(s_u), cs.at<double>(s_r), S, nref, my, nu, nit, params, dv, cs.st);
   }
-  if (blob) (void)hipFree(blob);
-  if (st) (void)hipStreamDestroy(st);
-  if (dev != cur) (void)hipSetDevice(cur);
-  return rc;
+  return cs.close(rc);
 }
 
 // the chunk budget of mpct_eval_indices(_device) in bytes of trajectory scratch; 0: MPCT_INDEX_SCRATCH_BYTES.
@@ -1757,57 +1666,28 @@ extern "C" int32_t mpct_draw_stats(const void* x, int32_t x_type, const int32_t*
   int rc = stats_check(x, x_type, C, D, m, nlev, levels, out);
   if (rc) return rc;
   if (C == 0) return MPCT_OK;  // nothing to stage
-  int cur = -1, cnt = 0;
-  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0 || hipGetDevice(&cur) != hipSuccess)
-    return fail(MPCT_EDEVICE, "no HIP device (mpct_draw_stats needs a GPU)");
-  const int dev = device < 0 ? cur : device;
-  if (dev >= cnt) return fail(MPCT_EINVAL, "device ordinal out of range");
-  if (dev != cur && hipSetDevice(dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
-  // one blob: x | alive | the nine fields, each 256-B aligned; a stream of this call's own
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t cols = (size_t)C * m, nl = (size_t)std::max(nlev, 1);
-  const size_t xb = (size_t)C * D * m * (x_type == MPCT_STAT_I32 ? 4 : 8), ab = alive ? (size_t)C * D * 4 : 0;
-  const size_t fb = al(cols * nl * 8);  // one field's slot, the largest of them
-  const size_t o_a = al(xb), o_f = o_a + al(ab);
-  hipStream_t st = nullptr;
-  char* blob = nullptr;
-  rc = MPCT_OK;
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
-    rc = fail(MPCT_EDEVICE, "hipStreamCreate failed");
-  } else if (hipMalloc(reinterpret_cast<void**>(&blob), o_f + 9 * fb + 256) != hipSuccess) {
-    rc = fail(MPCT_ENOMEM, "hipMalloc failed (draw statistics staging)");
-  } else {
-    auto slot = [&](const void* want, int k) -> char* { return want ? blob + o_f + k * fb : nullptr; };
-    const DrawStatsOut dv{(int32_t*)slot(out->n, 0),       (double*)slot(out->mean, 1), (double*)slot(out->lo, 2),
-                          (int32_t*)slot(out->lo_draw, 3), (double*)slot(out->hi, 4),   (int32_t*)slot(out->hi_draw, 5),
-                          (double*)slot(out->quantile, 6), (double*)slot(out->cvar, 7), (int32_t*)slot(out->q_draw, 8)};
-    bool ok = hipMemcpyAsync(blob, x, xb, hipMemcpyHostToDevice, st) == hipSuccess &&
-              (!ab || hipMemcpyAsync(blob + o_a, alive, ab, hipMemcpyHostToDevice, st) == hipSuccess);
-    if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (table)");
-    if (ok) {
-      rc = stats_launch(blob, x_type, ab ? reinterpret_cast<const int32_t*>(blob + o_a) : nullptr, C, D, m, nlev, levels,
-                        dv, m, 0, st);
-      ok = rc == MPCT_OK;
-    }
-    if (ok) {
-      auto d2h = [&](void* dst, const void* src, size_t b) {
-        return !dst || hipMemcpyAsync(dst, src, b, hipMemcpyDeviceToHost, st) == hipSuccess;
-      };
-      ok = d2h(out->n, dv.n, cols * 4) && d2h(out->mean, dv.mean, cols * 8) && d2h(out->lo, dv.lo, cols * 8) &&
-           d2h(out->lo_draw, dv.lo_draw, cols * 4) && d2h(out->hi, dv.hi, cols * 8) &&
-           d2h(out->hi_draw, dv.hi_draw, cols * 4) && d2h(out->quantile, dv.quantile, cols * nl * 8) &&
-           d2h(out->cvar, dv.cvar, cols * nl * 8) && d2h(out->q_draw, dv.q_draw, cols * nl * 4);
-      if (!ok) rc = fail(MPCT_EDEVICE, "hipMemcpyAsync failed (draw statistics)");
-    }
-    // this call's stream only, also after an error: the blob is freed below
-    const hipError_t se = hipStreamSynchronize(st);
-    if (rc == MPCT_OK && se != hipSuccess)
-      rc = fail(MPCT_EDEVICE, std::string("mpct_draw_stats failed on the device: ") + hipGetErrorString(se));
+  CallStage cs{"mpct_draw_stats", "draw statistics staging", "table", "draw statistics"};
+  // the per-level fields are asked for with nlev >= 1 only (stats_check); levels stays on the host
+  const size_t cols = (size_t)C * m, lev = cols * (size_t)nlev;
+  const int s_x = cs.in(x, (size_t)C * D * m * (x_type == MPCT_STAT_I32 ? 4 : 8)), s_alive = cs.in(alive, (size_t)C * D * 4);
+  const int s_n = cs.out(out->n, cols * 4), s_mean = cs.out(out->mean, cols * 8), s_lo = cs.out(out->lo, cols * 8),
+            s_lodraw = cs.out(out->lo_draw, cols * 4), s_hi = cs.out(out->hi, cols * 8), s_hidraw = cs.out(out->hi_draw, cols * 4),
+            s_quantile = cs.out(out->quantile, lev * 8), s_cvar = cs.out(out->cvar, lev * 8), s_qdraw = cs.out(out->q_draw, lev * 4);
+  rc = cs.open(device);
+  if (rc == MPCT_OK) {
+    DrawStatsOut dv{};
+    dv.n = cs.at<int32_t>(s_n);
+    dv.mean = cs.at<double>(s_mean);
+    dv.lo = cs.at<double>(s_lo);
+    dv.lo_draw = cs.at<int32_t>(s_lodraw);
+    dv.hi = cs.at<double>(s_hi);
+    dv.hi_draw = cs.at<int32_t>(s_hidraw);
+    dv.quantile = cs.at<double>(s_quantile);
+    dv.cvar = cs.at<double>(s_cvar);
+    dv.q_draw = cs.at<int32_t>(s_qdraw);
+    rc = stats_launch(cs.at<char>(s_x), x_type, cs.at<int32_t>(s_alive), C, D, m, nlev, levels, dv, m, 0, cs.st);
   }
-  if (blob) (void)hipFree(blob);
-  if (st) (void)hipStreamDestroy(st);
-  if (dev != cur) (void)hipSetDevice(cur);
-  return rc;
+  return cs.close(rc);
 }
 
 // width of index field id in a scenario's records, and whether it is an integer field
