@@ -45,6 +45,65 @@ long long nmpc_lds_bytes(int M, int N);
 
 using namespace mpct;
 
+static thread_local std::string g_err;
+
+static int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+
+// The batch arguments of the scenario-taking entries: C candidates (N2, Nu, delta [C][my], lambda [C][nu])
+// against nref signal sets r | v.  An entry builds one from its arguments, host or device pointers as it
+// takes them; HostStage::upload() turns a host one into its device-side twin.
+struct Batch {
+  int64_t C;
+  const int32_t *N2, *Nu;
+  const double *delta, *lambda;
+  int32_t nref;
+  const double *r, *v;
+  // the candidates [c0, c0 + n) against the same signals
+  Batch sub(int64_t c0, int64_t n, int my, int nu) const {
+    return Batch{n, N2 + c0, Nu + c0, delta + c0 * my, lambda + c0 * nu, nref, r, v};
+  }
+};
+
+// A grow-only device buffer that the calls of one context share across streams.  mark() records the event
+// behind the last launch that uses the buffer; acquire() orders the next call's stream after it before the
+// buffer is rewritten.  A regrow waits on the host for that event and then for `stream` before the old
+// buffer is freed.
+struct EventScratch {
+  void* buf = nullptr;
+  size_t bytes = 0;
+  hipEvent_t used = nullptr;
+  bool pending = false;
+
+  int acquire(size_t need, hipStream_t stream, const char* what, char** out) {
+    if (!used && hipEventCreateWithFlags(&used, hipEventDisableTiming) != hipSuccess)
+      return fail(MPCT_EDEVICE, "hipEventCreate failed");
+    if (need > bytes) {
+      if (pending) (void)hipEventSynchronize(used);
+      pending = false;
+      if (buf) {
+        (void)hipStreamSynchronize(stream);
+        (void)hipFree(buf);
+      }
+      buf = nullptr;
+      bytes = 0;
+      if (hipMalloc(&buf, need) != hipSuccess) return fail(MPCT_ENOMEM, std::string("hipMalloc(") + what + ") failed");
+      bytes = need;
+    }
+    if (pending && hipStreamWaitEvent(stream, used, 0) != hipSuccess) return fail(MPCT_EDEVICE, "hipStreamWaitEvent failed");
+    *out = static_cast<char*>(buf);
+    return MPCT_OK;
+  }
+  void mark(hipStream_t stream) { pending = hipEventRecord(used, stream) == hipSuccess; }
+  void release() {
+    if (pending) (void)hipEventSynchronize(used);
+    if (buf) (void)hipFree(buf);
+    if (used) (void)hipEventDestroy(used);
+  }
+};
+
 // Everything a scenario keeps on one device.  The host-pointer entries run on the library-owned
 // stream `stream` and synchronise only it (not the device), so other streams, host threads and
 // the contexts of other devices proceed concurrently.
@@ -63,29 +122,14 @@ struct DevCtx {
   hipStream_t stream = nullptr;
   LaunchFan fan;    // auxiliary streams of the class launches (band / NMPC kernels)
   WorkOrder order;  // dispatch-order sort buffers (GPC and NMPC kernels)
-  // robust scoring, device-pointer entry (grow only): per-simulation J1 / status of the generic
-  // path, candidate lists of the fused one.  robust_used is recorded after the launches that use
-  // the buffer; the next robust call's stream waits for it before rewriting
-  void* drobust = nullptr;
-  size_t drobust_bytes = 0;
-  hipEvent_t robust_used = nullptr;
-  bool robust_pending = false;
+  // robust scoring: per-simulation J1 / status of the generic path, candidate lists (and the tail's J1
+  // sample) of the fused one
+  EventScratch robust;
   int ncu = 0;  // compute units (grid of the fused robust kernel)
-  // mpct_eval_indices(_device): the trajectories y | u of one chunk of candidates (grow only, at most
-  // MPCT_INDEX_SCRATCH_BYTES or one candidate's).  index_used is recorded after the last kernel that
-  // reads the buffer; the next call's stream waits for it before rewriting
-  void* dindex = nullptr;
-  size_t dindex_bytes = 0;
-  hipEvent_t index_used = nullptr;
-  bool index_pending = false;
+  // the index entries: the trajectories y | u of one chunk of candidates (at most MPCT_INDEX_SCRATCH_BYTES or
+  // one candidate's) and, for the robust indices, the chunk's J1, status, alive and index records
+  EventScratch index;
 };
-
-static thread_local std::string g_err;
-
-static int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
 
 // the return of a launch wrapper whose device function reports 0, -2 (no memory) or another failure
 static int32_t launch_rc(int rc, const std::string& err) {
@@ -162,12 +206,8 @@ static void ctx_release(DevCtx* c) {
   if (c->dtab) (void)hipFree(c->dtab);
   if (c->dscratch) (void)hipFree(c->dscratch);
   if (c->dsig) (void)hipFree(c->dsig);
-  if (c->robust_pending) (void)hipEventSynchronize(c->robust_used);
-  if (c->drobust) (void)hipFree(c->drobust);
-  if (c->robust_used) (void)hipEventDestroy(c->robust_used);
-  if (c->index_pending) (void)hipEventSynchronize(c->index_used);
-  if (c->dindex) (void)hipFree(c->dindex);
-  if (c->index_used) (void)hipEventDestroy(c->index_used);
+  c->robust.release();
+  c->index.release();
   order_release(c->order);
   c->fan.release();
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -266,6 +306,11 @@ static int device_ctx(mpct_scenario* s, int want_dev, DevCtx** out, int occurren
   return MPCT_OK;
 }
 
+// the primary context of the device the call's options name
+static int ctx_for(mpct_scenario* s, const mpct_opts* opts, DevCtx** out) {
+  return device_ctx(s, opts ? opts->device : -1, out);
+}
+
 static DevOpts make_opts(const mpct_opts* o) {
   DevOpts d{};
   d.open_loop = o ? o->open_loop : 0;
@@ -280,14 +325,13 @@ static DevOpts make_opts(const mpct_opts* o) {
 }
 
 // the argument checks of the three eval entries; devlist_ok: mpct_eval_batch_multi's device list
-static int check_args(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* N2, const int32_t* Nu,
-                      const double* delta, const double* lambda, const double* r, const double* v,
-                      const mpct_opts* opts, const mpct_result* out, bool devlist_ok = true) {
+static int check_args(mpct_scenario* s, const Batch& b, const mpct_opts* opts, const mpct_result* out,
+                      bool devlist_ok = true) {
   if (!s) return fail(MPCT_EINVAL, "null scenario");
-  if (C < 0 || nref < 1) return fail(MPCT_EINVAL, "C < 0 or nref < 1");
-  if (C * (int64_t)nref > 0x7fffffffLL) return fail(MPCT_ERANGE, "too many simulations in one call");
-  if (C > 0 && (!N2 || !Nu || !delta || !lambda || !r)) return fail(MPCT_EINVAL, "null input pointer");
-  if (s->nd + s->nq > 0 && !v) return fail(MPCT_EINVAL, "v required when nd + nq > 0");
+  if (b.C < 0 || b.nref < 1) return fail(MPCT_EINVAL, "C < 0 or nref < 1");
+  if (b.C * (int64_t)b.nref > 0x7fffffffLL) return fail(MPCT_ERANGE, "too many simulations in one call");
+  if (b.C > 0 && (!b.N2 || !b.Nu || !b.delta || !b.lambda || !b.r)) return fail(MPCT_EINVAL, "null input pointer");
+  if (s->nd + s->nq > 0 && !b.v) return fail(MPCT_EINVAL, "v required when nd + nq > 0");
   if (!out) return fail(MPCT_EINVAL, "null result");
   if (!devlist_ok) return fail(MPCT_EINVAL, "ndev must be 1..64 with a device list");
   if (s->dtc && opts && opts->open_loop) return fail(MPCT_EINVAL, "DTC mode has no open-loop prediction");
@@ -298,23 +342,22 @@ static int check_args(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* 
 }
 
 // enqueue one batch with device pointers on `stream` (ctx's device is current)
-static int launch_batch(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2, const int32_t* Nu,
-                        const double* delta, const double* lambda, int32_t nref, const double* r, const double* v,
-                        const mpct_opts* opts, const mpct_result* out, hipStream_t stream) {
-  if (C == 0) return MPCT_OK;
+static int launch_batch(mpct_scenario* s, DevCtx* cx, const Batch& b, const mpct_opts* opts, const mpct_result* out,
+                        hipStream_t stream) {
+  if (b.C == 0) return MPCT_OK;
   DevOpts dop = make_opts(opts);
   DevResult dr{out->J1, out->j21, out->j22, out->Jnu, out->status, out->qp_iters,
                 out->y, out->u, out->ys, out->uopt, nullptr};
 #ifdef MPCT_PROFILE
   // diagnostic build: per-simulation section cycle sums, summarised on stderr
-  const long long S = C * nref;
+  const long long S = b.C * b.nref;
   unsigned long long* dprof = nullptr;
   (void)hipMalloc(&dprof, sizeof(unsigned long long) * S * PROF_N);
   dr.prof = dprof;
 #endif
 #ifdef MPCT_TIMELINE
   // diagnostic build: [slot][t0, t1, HW_ID << 32 | XCC_ID, sim] -> $MPCT_TIMELINE_OUT
-  const long long S = C * nref;
+  const long long S = b.C * b.nref;
   unsigned long long* dprof = nullptr;
   (void)hipMalloc(&dprof, sizeof(unsigned long long) * S * 4);
   (void)hipMemset(dprof, 0, sizeof(unsigned long long) * S * 4);
@@ -324,19 +367,19 @@ static int launch_batch(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* 
   int rc = 0;
   // no class launch writes the trajectories of a skipped or bad-horizon simulation: NaN, like its costs
   if (dop.want_traj)
-    rc = fill_unrun_trajectories(dr, C, nref, N2, Nu, cx->ds.n2max, cx->ds.numax, s->my, s->nu, s->nit,
+    rc = fill_unrun_trajectories(dr, b.C, b.nref, b.N2, b.Nu, cx->ds.n2max, cx->ds.numax, s->my, s->nu, s->nit,
                                  dop.open_loop != 0, stream, &err);
   if (rc) return fail(rc, err);
   if (s->nmpc)
-    rc = launch_nmpc(cx->ds, C, nref, N2, Nu, delta, lambda, r, dop, dr, stream, &cx->fan, &cx->order, &err);
+    rc = launch_nmpc(cx->ds, b.C, b.nref, b.N2, b.Nu, b.delta, b.lambda, b.r, dop, dr, stream, &cx->fan, &cx->order, &err);
   else if (s->mdband)
-    rc = launch_mdband(cx->ds, C, nref, N2, Nu, delta, lambda, r, v, dop, dr, stream, &cx->fan, &err);
+    rc = launch_mdband(cx->ds, b.C, b.nref, b.N2, b.Nu, b.delta, b.lambda, b.r, b.v, dop, dr, stream, &cx->fan, &err);
   else {
     if (cx->ncu == 0 &&
         (hipDeviceGetAttribute(&cx->ncu, hipDeviceAttributeMultiprocessorCount, cx->dev) != hipSuccess || cx->ncu < 1))
       cx->ncu = 0;
-    rc = launch_closed_loop(cx->ds, C, nref, N2, Nu, delta, lambda, r, v, dop, dr, s->nu * s->numax, &cx->order, &cx->fan,
-                            s->wide_slots, cx->ncu, stream, &err);
+    rc = launch_closed_loop(cx->ds, b.C, b.nref, b.N2, b.Nu, b.delta, b.lambda, b.r, b.v, dop, dr, s->nu * s->numax,
+                            &cx->order, &cx->fan, s->wide_slots, cx->ncu, stream, &err);
   }
   if (rc) return fail(rc, err);
 #ifdef MPCT_TIMELINE
@@ -398,12 +441,13 @@ extern "C" int32_t mpct_eval_batch_device(mpct_scenario* s, int64_t C, const int
                                           const double* delta, const double* lambda, int32_t nref,
                                           const double* r, const double* v, const mpct_opts* opts,
                                           mpct_result* out, void* stream) {
-  int rc = check_args(s, C, nref, N2, Nu, delta, lambda, r, v, opts, out);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_args(s, b, opts, out);
   if (rc) return rc;
   DevCtx* cx = nullptr;
-  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  rc = ctx_for(s, opts, &cx);
   if (rc) return rc;
-  return launch_batch(s, cx, C, N2, Nu, delta, lambda, nref, r, v, opts, out, static_cast<hipStream_t>(stream));
+  return launch_batch(s, cx, b, opts, out, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int32_t mpct_rank_device(const double* costs, int64_t C, int32_t k, const double* w, int32_t* perm,
@@ -843,36 +887,50 @@ extern "C" int32_t mpct_hypervolume_exact(const double* costs, int64_t C, int32_
   return cs.close(rc);
 }
 
-// Host-pointer staging of one call on the context's own stream, shared by eval_host and
-// mpct_eval_robust: the candidates go into the grow-only scratch blob, the signals r | v through
+// Host-pointer staging of one call on the context's own stream, shared by the scenario-taking host
+// entries: the candidates go into the grow-only scratch blob, the signals r | v through
 // the context's signal cache, the results come back from slots of the same blob.  An entry
-// reserves its result slots, calls upload(), launches on cx->stream, fetch()es and finish()es.
+// declares each result field once, before upload(): keep() for a field the launch always writes
+// (or writes when `on`), which is copied back where the caller gave a pointer, want() for a field
+// that exists only where the caller asked for it (CallStage's rule: no pointer, no bytes, and the
+// launch gets NULL).  Slots are numbered from 0 in the order they are declared.  After upload()
+// `dev` is the device-side batch and at<T>(slot) a field's device address; the entry launches on
+// `st` and finish()es, which enqueues the D2H copy of every declared field and waits.
 namespace {
 struct HostStage {
   DevCtx* cx;
   hipStream_t st;
-  int64_t C;
   int my, nu;
   size_t off = 0;
-  size_t o_N2, o_Nu, o_d, o_l;            // the candidates' slots
-  const double *r = nullptr, *v = nullptr;  // the signals on the device, after upload()
-  bool fetched = true;
+  size_t o_N2, o_Nu, o_d, o_l;  // the candidates' slots
+  Batch dev{};                  // the candidates and signals on the device, after upload()
+  static constexpr int kMaxSlots = 23;  // mpct_eval_indices, the widest entry: an mpct_result and 13 index fields
+  struct Slot {
+    void* host;  // NULL: nothing to copy back
+    size_t bytes, off;
+    bool on;  // false: nothing reserved, its device address is NULL
+  } slots[kMaxSlots] = {};
+  int nslots = 0;
 
-  HostStage(const mpct_scenario* s, DevCtx* c, int64_t ncand) : cx(c), st(c->stream), C(ncand), my(s->my), nu(s->nu) {
-    o_N2 = slot(C * 4), o_Nu = slot(C * 4), o_d = slot(C * my * 8), o_l = slot(C * nu * 8);
+  HostStage(const mpct_scenario* s, DevCtx* c, int64_t C) : cx(c), st(c->stream), my(s->my), nu(s->nu) {
+    o_N2 = reserve(C * 4), o_Nu = reserve(C * 4), o_d = reserve(C * my * 8), o_l = reserve(C * nu * 8);
   }
-  // reserve a 256-B-aligned slot of the blob; its address holds after upload()
-  size_t slot(size_t bytes) {
+  // reserve 256-B-aligned bytes of the blob; the address holds after upload()
+  size_t reserve(size_t bytes) {
     const size_t o = off;
     off += (bytes + 255) & ~(size_t)255;
     return o;
   }
+  int keep(void* host, size_t bytes, bool on = true) {
+    assert(nslots < kMaxSlots);
+    slots[nslots] = Slot{host, bytes, on ? reserve(bytes) : 0, on};
+    return nslots++;
+  }
+  int want(void* host, size_t bytes) { return keep(host, bytes, host != nullptr); }
   template <class T>
-  T* at(size_t o) const { return reinterpret_cast<T*>(static_cast<char*>(cx->dscratch) + o); }
-  const int32_t* N2() const { return at<int32_t>(o_N2); }
-  const int32_t* Nu() const { return at<int32_t>(o_Nu); }
-  const double* delta() const { return at<double>(o_d); }
-  const double* lambda() const { return at<double>(o_l); }
+  T* at(int i) const { return slots[i].on ? reinterpret_cast<T*>(static_cast<char*>(cx->dscratch) + slots[i].off) : nullptr; }
+  template <class T>
+  void bind(int i, T*& p) const { p = at<T>(i); }
 
   // `*buf` holds at least `bytes`: a regrow waits for the stream's work on the old buffer first
   int ensure(void** buf, size_t* have, size_t bytes, const char* what) {
@@ -889,35 +947,38 @@ struct HostStage {
   }
 
   // every slot reserved: size the blob and enqueue the H2D copies of the candidates and signals
-  int upload(const mpct_scenario* s, const int32_t* hN2, const int32_t* hNu, const double* hdelta, const double* hlambda,
-             int32_t nref, const double* hr, const double* hv) {
+  int upload(const mpct_scenario* s, const Batch& h) {
     int rc = ensure(&cx->dscratch, &cx->dscratch_bytes, off, "scratch");
     if (rc) return rc;
     // signals r | v: uploaded only when they differ from what the context's signal buffer holds
-    const size_t rb = (size_t)nref * my * s->nit * 8, vb = (size_t)nref * (s->nd + s->nq) * s->nit * 8;
+    const char *hr = reinterpret_cast<const char*>(h.r), *hv = reinterpret_cast<const char*>(h.v);
+    const size_t rb = (size_t)h.nref * my * s->nit * 8, vb = (size_t)h.nref * (s->nd + s->nq) * s->nit * 8;
     const bool same_sig = cx->sig_host.size() == rb + vb && std::memcmp(cx->sig_host.data(), hr, rb) == 0 &&
                           (vb == 0 || std::memcmp(cx->sig_host.data() + rb, hv, vb) == 0);
     if (!same_sig) {
       if (rb + vb > cx->dsig_bytes) cx->sig_host.clear();
       rc = ensure(&cx->dsig, &cx->dsig_bytes, rb + vb, "signals");
       if (rc) return rc;
-      cx->sig_host.assign(reinterpret_cast<const char*>(hr), reinterpret_cast<const char*>(hr) + rb);
-      if (vb) cx->sig_host.insert(cx->sig_host.end(), reinterpret_cast<const char*>(hv), reinterpret_cast<const char*>(hv) + vb);
+      cx->sig_host.assign(hr, hr + rb);
+      if (vb) cx->sig_host.insert(cx->sig_host.end(), hv, hv + vb);
     }
+    char* blob = static_cast<char*>(cx->dscratch);
+    const char* sig = static_cast<const char*>(cx->dsig);
+    dev = Batch{h.C, reinterpret_cast<int32_t*>(blob + o_N2), reinterpret_cast<int32_t*>(blob + o_Nu),
+                reinterpret_cast<double*>(blob + o_d), reinterpret_cast<double*>(blob + o_l), h.nref,
+                reinterpret_cast<const double*>(sig), vb ? reinterpret_cast<const double*>(sig + rb) : nullptr};
     auto h2d = [&](const void* dst, const void* p, size_t bytes) {
       return bytes == 0 || hipMemcpyAsync(const_cast<void*>(dst), p, bytes, hipMemcpyHostToDevice, st) == hipSuccess;
     };
     // the signals are copied from the context's own host copy (the caller's buffers may change
     // after the call returns; an earlier launch reading dsig is ordered before this copy on st)
-    if (!h2d(N2(), hN2, C * 4) || !h2d(Nu(), hNu, C * 4) || !h2d(delta(), hdelta, C * my * 8) ||
-        !h2d(lambda(), hlambda, C * nu * 8) || (!same_sig && !h2d(cx->dsig, cx->sig_host.data(), rb + vb))) {
+    if (!h2d(dev.N2, h.N2, h.C * 4) || !h2d(dev.Nu, h.Nu, h.C * 4) || !h2d(dev.delta, h.delta, h.C * my * 8) ||
+        !h2d(dev.lambda, h.lambda, h.C * nu * 8) || (!same_sig && !h2d(cx->dsig, cx->sig_host.data(), rb + vb))) {
       // copies enqueued before the failing one may still read the caller's buffers
       (void)hipStreamSynchronize(st);
       cx->sig_host.clear();
       return fail(MPCT_EDEVICE, "hipMemcpyAsync(inputs) failed");
     }
-    r = static_cast<const double*>(cx->dsig);
-    v = vb ? reinterpret_cast<const double*>(static_cast<const char*>(cx->dsig) + rb) : nullptr;
     return MPCT_OK;
   }
 
@@ -926,11 +987,14 @@ struct HostStage {
     (void)hipStreamSynchronize(st);
     return rc;
   }
-  // enqueue the D2H copy of slot o into the caller's dst (skipped when the caller passed none)
-  void fetch(void* dst, size_t o, size_t bytes) {
-    if (dst && bytes) fetched = hipMemcpyAsync(dst, at<char>(o), bytes, hipMemcpyDeviceToHost, st) == hipSuccess && fetched;
-  }
+  // enqueue the D2H copy of every declared field the caller gave a pointer for, then wait for the stream
   int finish() {
+    bool fetched = true;
+    for (int i = 0; i < nslots; ++i) {
+      const Slot& f = slots[i];
+      if (f.on && f.host && f.bytes)
+        fetched = hipMemcpyAsync(f.host, at<char>(i), f.bytes, hipMemcpyDeviceToHost, st) == hipSuccess && fetched;
+    }
     const hipError_t se = hipStreamSynchronize(st);
     if (se != hipSuccess) return fail(MPCT_EDEVICE, std::string("kernel execution failed: ") + hipGetErrorString(se));
     if (!fetched) return fail(MPCT_EDEVICE, "hipMemcpyAsync(results) failed");
@@ -939,55 +1003,56 @@ struct HostStage {
 };
 }  // namespace
 
+// the ten fields of an mpct_result in the struct's order, each with its elements per simulation
+template <class R, class F>
+static void each_field(R& res, int64_t my, int64_t nu, int64_t nit, F f) {
+  f(res.J1, my);
+  f(res.j21, my);
+  f(res.j22, my);
+  f(res.Jnu, nu);
+  f(res.status, 1);
+  f(res.qp_iters, 1);
+  f(res.y, my * nit);
+  f(res.u, nu * nit);
+  f(res.ys, my * nit);
+  f(res.uopt, nu * nit);
+}
+
 // host buffers in, host buffers out, on the context's own stream: H2D of the candidates and
 // signals, the launch, D2H of the results, then a wait on that stream only
-static int eval_host(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2, const int32_t* Nu,
-                     const double* delta, const double* lambda, int32_t nref, const double* r, const double* v,
-                     const mpct_opts* opts, mpct_result* out) {
+static int eval_host(mpct_scenario* s, DevCtx* cx, const Batch& b, const mpct_opts* opts, mpct_result* out) {
   if (hipSetDevice(cx->dev) != hipSuccess) return fail(MPCT_EDEVICE, "hipSetDevice failed");
-  if (C == 0) return MPCT_OK;
-  const int my = s->my, nu = s->nu, nit = s->nit;
-  const size_t S = (size_t)(C * nref), yb = S * my * nit * 8, ub = S * nu * nit * 8;
+  if (b.C == 0) return MPCT_OK;
+  const size_t S = (size_t)(b.C * b.nref);
   const bool traj = opts && opts->want_traj;
   const bool ol = traj && opts->open_loop;
-  HostStage hs(s, cx, C);
-  const size_t o_J1 = hs.slot(S * my * 8), o_j21 = hs.slot(S * my * 8), o_j22 = hs.slot(S * my * 8);
-  const size_t o_Jnu = hs.slot(S * nu * 8), o_st = hs.slot(S * 4), o_it = hs.slot(S * 8);
-  const size_t o_y = traj ? hs.slot(yb) : 0, o_u = traj ? hs.slot(ub) : 0;
-  const size_t o_ys = ol ? hs.slot(yb) : 0, o_uo = ol ? hs.slot(ub) : 0;
-  int rc = hs.upload(s, N2, Nu, delta, lambda, nref, r, v);
+  HostStage hs(s, cx, b.C);
+  // slots 0..9: the six cost fields always live on the device, y | u with want_traj, ys | uopt with open_loop too
+  int k = 0;
+  each_field(*out, s->my, s->nu, s->nit, [&](auto* host, int64_t w) {
+    hs.keep(host, S * w * sizeof(*host), k < 6 || (k < 8 ? traj : ol));
+    ++k;
+  });
+  int rc = hs.upload(s, b);
   if (rc) return rc;
   mpct_result dres{};
-  dres.J1 = hs.at<double>(o_J1);
-  dres.j21 = hs.at<double>(o_j21);
-  dres.j22 = hs.at<double>(o_j22);
-  dres.Jnu = hs.at<double>(o_Jnu);
-  dres.status = hs.at<int32_t>(o_st);
-  dres.qp_iters = hs.at<int64_t>(o_it);
-  if (traj) dres.y = hs.at<double>(o_y), dres.u = hs.at<double>(o_u);
-  if (ol) dres.ys = hs.at<double>(o_ys), dres.uopt = hs.at<double>(o_uo);
-  rc = launch_batch(s, cx, C, hs.N2(), hs.Nu(), hs.delta(), hs.lambda(), nref, hs.r, hs.v, opts, &dres, hs.st);
+  k = 0;
+  each_field(dres, s->my, s->nu, s->nit, [&](auto*& dev, int64_t) { hs.bind(k++, dev); });
+  rc = launch_batch(s, cx, hs.dev, opts, &dres, hs.st);
   if (rc) return hs.abandon(rc);
-  hs.fetch(out->J1, o_J1, S * my * 8);
-  hs.fetch(out->j21, o_j21, S * my * 8);
-  hs.fetch(out->j22, o_j22, S * my * 8);
-  hs.fetch(out->Jnu, o_Jnu, S * nu * 8);
-  hs.fetch(out->status, o_st, S * 4);
-  hs.fetch(out->qp_iters, o_it, S * 8);
-  if (traj) hs.fetch(out->y, o_y, yb), hs.fetch(out->u, o_u, ub);
-  if (ol) hs.fetch(out->ys, o_ys, yb), hs.fetch(out->uopt, o_uo, ub);
   return hs.finish();
 }
 
 extern "C" int32_t mpct_eval_batch(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
                                    const double* delta, const double* lambda, int32_t nref, const double* r,
                                    const double* v, const mpct_opts* opts, mpct_result* out) {
-  int rc = check_args(s, C, nref, N2, Nu, delta, lambda, r, v, opts, out);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_args(s, b, opts, out);
   if (rc) return rc;
   DevCtx* cx = nullptr;
-  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  rc = ctx_for(s, opts, &cx);
   if (rc) return rc;
-  return eval_host(s, cx, C, N2, Nu, delta, lambda, nref, r, v, opts, out);
+  return eval_host(s, cx, b, opts, out);
 }
 
 extern "C" int64_t mpct_shard_candidates(int64_t C, int32_t ndev, int32_t k, int64_t* idx, int64_t cap) {
@@ -1019,7 +1084,8 @@ extern "C" int32_t mpct_eval_batch_multi(mpct_scenario* s, int32_t ndev, const i
                                          const int32_t* N2, const int32_t* Nu, const double* delta,
                                          const double* lambda, int32_t nref, const double* r, const double* v,
                                          const mpct_opts* opts, mpct_result* out) {
-  int rc = check_args(s, C, nref, N2, Nu, delta, lambda, r, v, opts, out, ndev >= 1 && ndev <= 64 && devices);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_args(s, b, opts, out, ndev >= 1 && ndev <= 64 && devices);
   if (rc) return rc;
   int cur = -1, cnt = 0;
   if (hipGetDevice(&cur) != hipSuccess || hipGetDeviceCount(&cnt) != hipSuccess || cnt == 0)
@@ -1049,52 +1115,36 @@ extern "C" int32_t mpct_eval_batch_multi(mpct_scenario* s, int32_t ndev, const i
       return;
     }
     if (ndev == 1) {  // the identity split: no gather / scatter
-      rcs[k] = eval_host(s, cxs[k], C, N2, Nu, delta, lambda, nref, r, v, opts, out);
+      rcs[k] = eval_host(s, cxs[k], b, opts, out);
       if (rcs[k]) errs[k] = g_err;
       return;
     }
-    // gather this slot's candidates (k, k+ndev, ...) and give it packed result buffers
+    // gather this slot's candidates (k, k+ndev, ...) and give it a packed buffer per field the caller asked for
     std::vector<int32_t> n2(n), nuv(n);
     std::vector<double> dl((size_t)n * my), lm((size_t)n * nu);
     strided_copy(const_cast<int32_t*>(N2), n2.data(), n, ndev, k, 1, 1, false);
     strided_copy(const_cast<int32_t*>(Nu), nuv.data(), n, ndev, k, 1, 1, false);
     strided_copy(const_cast<double*>(delta), dl.data(), n, ndev, k, 1, my, false);
     strided_copy(const_cast<double*>(lambda), lm.data(), n, ndev, k, 1, nu, false);
-    const int64_t S = n * nref;
-    auto buf = [&](const void* want, int64_t w) { return want ? std::vector<double>((size_t)(S * w)) : std::vector<double>(); };
-    std::vector<double> J1 = buf(out->J1, my), j21 = buf(out->j21, my), j22 = buf(out->j22, my), Jnu = buf(out->Jnu, nu);
-    std::vector<double> y = buf(out->y, (int64_t)my * nit), u = buf(out->u, (int64_t)nu * nit);
-    std::vector<double> ys = buf(out->ys, (int64_t)my * nit), uo = buf(out->uopt, (int64_t)nu * nit);
-    std::vector<int32_t> stv(out->status ? (size_t)S : 0);
-    std::vector<int64_t> itv(out->qp_iters ? (size_t)S : 0);
-    auto p = [](std::vector<double>& x) { return x.empty() ? nullptr : x.data(); };
-    mpct_result o{};
-    o.J1 = p(J1);
-    o.j21 = p(j21);
-    o.j22 = p(j22);
-    o.Jnu = p(Jnu);
-    o.status = stv.empty() ? nullptr : stv.data();
-    o.qp_iters = itv.empty() ? nullptr : itv.data();
-    o.y = p(y);
-    o.u = p(u);
-    o.ys = p(ys);
-    o.uopt = p(uo);
-    rcs[k] = eval_host(s, cxs[k], n, n2.data(), nuv.data(), dl.data(), lm.data(), nref, r, v, opts, &o);
+    std::vector<std::vector<char>> packed(10);
+    mpct_result o = *out;
+    int f = 0;
+    each_field(o, my, nu, nit, [&](auto*& p, int64_t w) {
+      std::vector<char>& buf = packed[f++];
+      if (!p) return;
+      buf.resize(sizeof(*p) * (size_t)(n * nref * w));
+      p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(buf.data());
+    });
+    rcs[k] = eval_host(s, cxs[k], Batch{n, n2.data(), nuv.data(), dl.data(), lm.data(), nref, r, v}, opts, &o);
     if (rcs[k]) {
       errs[k] = g_err;  // g_err is thread-local: carry it to the caller
       return;
     }
     // scatter into the caller's order (slots write disjoint candidates)
-    strided_copy(out->J1, o.J1, n, ndev, k, nref, my, true);
-    strided_copy(out->j21, o.j21, n, ndev, k, nref, my, true);
-    strided_copy(out->j22, o.j22, n, ndev, k, nref, my, true);
-    strided_copy(out->Jnu, o.Jnu, n, ndev, k, nref, nu, true);
-    strided_copy(out->status, o.status, n, ndev, k, nref, 1, true);
-    strided_copy(out->qp_iters, o.qp_iters, n, ndev, k, nref, 1, true);
-    strided_copy(out->y, o.y, n, ndev, k, nref, (int64_t)my * nit, true);
-    strided_copy(out->u, o.u, n, ndev, k, nref, (int64_t)nu * nit, true);
-    strided_copy(out->ys, o.ys, n, ndev, k, nref, (int64_t)my * nit, true);
-    strided_copy(out->uopt, o.uopt, n, ndev, k, nref, (int64_t)nu * nit, true);
+    f = 0;
+    each_field(*out, my, nu, nit, [&](auto* p, int64_t w) {
+      strided_copy(p, reinterpret_cast<decltype(p)>(packed[f++].data()), n, ndev, k, nref, w, true);
+    });
   };
   if (ndev == 1) {
     shard(0);
@@ -1114,13 +1164,12 @@ extern "C" int32_t mpct_eval_batch_multi(mpct_scenario* s, int32_t ndev, const i
 // robust scoring over plant draws (include/mpct.h)
 
 // the argument checks of the robust entries, on top of check_args
-static int check_robust(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* N2, const int32_t* Nu,
-                        const double* delta, const double* lambda, const double* r, const double* v, double j_bound,
-                        const mpct_opts* opts, const mpct_robust_result* out, bool need_out = true) {
+static int check_robust(mpct_scenario* s, const Batch& b, double j_bound, const mpct_opts* opts,
+                        const mpct_robust_result* out, bool need_out = true) {
   if (!s) return fail(MPCT_EINVAL, "null scenario");
   if (opts && (opts->open_loop || opts->want_traj))
     return fail(MPCT_EINVAL, "robust scoring is cost-only: open_loop and want_traj must be 0");
-  if (nref < 1) return fail(MPCT_EINVAL, "nref < 1: robust scoring needs at least one draw");
+  if (b.nref < 1) return fail(MPCT_EINVAL, "nref < 1: robust scoring needs at least one draw");
   if (!(j_bound >= 0.0)) return fail(MPCT_EINVAL, "j_bound must be >= 0 (0 = 1e100, +inf allowed), not negative or NaN");
   if (need_out) {
     if (!out) return fail(MPCT_EINVAL, "null result");
@@ -1128,27 +1177,7 @@ static int check_robust(mpct_scenario* s, int64_t C, int32_t nref, const int32_t
       return fail(MPCT_EINVAL, "every output pointer of the robust result is NULL");
   }
   const mpct_result any{};
-  return check_args(s, C, nref, N2, Nu, delta, lambda, r, v, opts, &any);
-}
-
-// the scenario's robust scratch on this context, at least `bytes`; orders `stream` after the last
-// robust launches that used it
-static int robust_scratch(DevCtx* cx, size_t bytes, hipStream_t stream, char** out) {
-  if (!cx->robust_used && hipEventCreateWithFlags(&cx->robust_used, hipEventDisableTiming) != hipSuccess)
-    return fail(MPCT_EDEVICE, "hipEventCreate failed");
-  if (bytes > cx->drobust_bytes) {
-    if (cx->robust_pending) (void)hipEventSynchronize(cx->robust_used);
-    cx->robust_pending = false;
-    if (cx->drobust) (void)hipFree(cx->drobust);
-    cx->drobust = nullptr;
-    cx->drobust_bytes = 0;
-    if (hipMalloc(&cx->drobust, bytes) != hipSuccess) return fail(MPCT_ENOMEM, "hipMalloc(robust scratch) failed");
-    cx->drobust_bytes = bytes;
-  }
-  if (cx->robust_pending && hipStreamWaitEvent(stream, cx->robust_used, 0) != hipSuccess)
-    return fail(MPCT_EDEVICE, "hipStreamWaitEvent failed");
-  *out = static_cast<char*>(cx->drobust);
-  return MPCT_OK;
+  return check_args(s, b, opts, &any);
 }
 
 // the tail statistics a robust call adds (mpct_eval_robust_tail): the levels on the host, the
@@ -1161,10 +1190,8 @@ struct TailReq {
 
 // the argument checks the tail entries add, in the header's order; then check_robust's, then the
 // draw cap.  Nothing here touches a device
-static int check_tail(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* N2, const int32_t* Nu,
-                      const double* delta, const double* lambda, const double* r, const double* v, double j_bound,
-                      const mpct_opts* opts, int32_t nlev, const double* levels, const mpct_robust_result* out,
-                      const mpct_robust_tail* tail) {
+static int check_tail(mpct_scenario* s, const Batch& b, double j_bound, const mpct_opts* opts, int32_t nlev,
+                      const double* levels, const mpct_robust_result* out, const mpct_robust_tail* tail) {
   if (nlev < 1 || nlev > MPCT_TAIL_MAX_LEVELS) return fail(MPCT_EINVAL, "nlev must be 1 .. MPCT_TAIL_MAX_LEVELS (8)");
   if (!levels) return fail(MPCT_EINVAL, "null levels");
   for (int j = 0; j < nlev; ++j)
@@ -1172,19 +1199,19 @@ static int check_tail(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* 
   const bool any_tail = tail && (tail->quantile || tail->cvar || tail->q_draw);
   const bool any_out = out && (out->mean || out->worst || out->n_failed || out->worst_draw || out->status || out->J1);
   if (!any_tail && !any_out) return fail(MPCT_EINVAL, "every output pointer of the robust result and of the tail is NULL");
-  const int rc = check_robust(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, out, false);
+  const int rc = check_robust(s, b, j_bound, opts, out, false);
   if (rc) return rc;
-  if (nref > MPCT_TAIL_MAX_DRAWS) return fail(MPCT_ERANGE, "nref > MPCT_TAIL_MAX_DRAWS (4096): the tail kernel's LDS holds no more draws");
+  if (b.nref > MPCT_TAIL_MAX_DRAWS) return fail(MPCT_ERANGE, "nref > MPCT_TAIL_MAX_DRAWS (4096): the tail kernel's LDS holds no more draws");
   return MPCT_OK;
 }
 
 // enqueue one robust batch with device pointers on `stream` (ctx's device is current); with `tail`,
 // robust_tail_kernel follows on the same stream, on the J1 sample of the same launch
-static int launch_robust(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2, const int32_t* Nu,
-                         const double* delta, const double* lambda, int32_t nref, const double* r, const double* v,
-                         double j_bound, const mpct_opts* opts, const mpct_robust_result* out, hipStream_t stream,
-                         const TailReq* tail = nullptr) {
-  if (C == 0) return MPCT_OK;
+static int launch_robust(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
+                         const mpct_robust_result* out, hipStream_t stream, const TailReq* tail = nullptr) {
+  if (b.C == 0) return MPCT_OK;
+  const int64_t C = b.C;
+  const int32_t nref = b.nref;
   const double bound = j_bound == 0.0 ? kRobustDefaultBound : j_bound;
   const RobustOut ro{out->mean, out->worst, out->n_failed, out->worst_draw, out->status};
   const int64_t S = C * nref;
@@ -1198,15 +1225,16 @@ static int launch_robust(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t*
     // the candidate lists, and the J1 sample where a tail is asked for and the caller keeps none
     const size_t lb = (sizeof(int) * (size_t)(2 * C + 2) + 255) & ~(size_t)255;
     const bool own_j1 = tail && !out->J1;
-    rc = robust_scratch(cx, own_j1 ? lb + (size_t)S * s->my * 8 : sizeof(int) * (size_t)(2 * C + 2), stream, &scr);
+    rc = cx->robust.acquire(own_j1 ? lb + (size_t)S * s->my * 8 : sizeof(int) * (size_t)(2 * C + 2), stream,
+                            "robust scratch", &scr);
     if (rc) return rc;
     double* j1 = own_j1 ? reinterpret_cast<double*>(scr + lb) : out->J1;
     const int* perm = nullptr;
-    rc = order_candidates(kOrderGpc, s->my, s->nu, C, N2, Nu, delta, lambda, cx->order, &perm, stream, &err, &cx->ds,
-                          nref, r);
+    rc = order_candidates(kOrderGpc, s->my, s->nu, C, b.N2, b.Nu, b.delta, b.lambda, cx->order, &perm, stream, &err,
+                          &cx->ds, nref, b.r);
     if (rc == 0)
-      rc = launch_dtc_robust(cx->ds, C, nref, N2, Nu, delta, lambda, r, v, perm, reinterpret_cast<int*>(scr), bound, ro,
-                             j1, cx->ncu, &cx->fan, stream, &err);
+      rc = launch_dtc_robust(cx->ds, C, nref, b.N2, b.Nu, b.delta, b.lambda, b.r, b.v, perm, reinterpret_cast<int*>(scr),
+                             bound, ro, j1, cx->ncu, &cx->fan, stream, &err);
     if (perm) order_mark_used(cx->order, stream);
     // the fused kernel keeps no per-simulation status: a failed draw of it has a non-finite J1, and a
     // candidate that was never simulated an all-NaN sample (robust_classify_kernel)
@@ -1216,12 +1244,12 @@ static int launch_robust(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t*
   } else {
     // the per-simulation instance, unchanged, into the caller's J1 or the scenario's scratch
     const size_t jb = out->J1 ? 0 : ((size_t)S * s->my * 8 + 255) & ~(size_t)255;
-    rc = robust_scratch(cx, jb + (size_t)S * 4, stream, &scr);
+    rc = cx->robust.acquire(jb + (size_t)S * 4, stream, "robust scratch", &scr);
     if (rc) return rc;
     mpct_result per{};
     per.J1 = out->J1 ? out->J1 : reinterpret_cast<double*>(scr);
     per.status = reinterpret_cast<int32_t*>(scr + jb);
-    rc = launch_batch(s, cx, C, N2, Nu, delta, lambda, nref, r, v, opts, &per, stream);
+    rc = launch_batch(s, cx, b, opts, &per, stream);
     if (rc) return rc;
     rc = launch_robust_reduce(C, nref, s->my, bound, per.J1, per.status, ro, stream, &err);
     if (rc == 0 && tail)
@@ -1229,7 +1257,7 @@ static int launch_robust(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t*
                               &err);
     if (rc) return fail(rc, err);
   }
-  cx->robust_pending = hipEventRecord(cx->robust_used, stream) == hipSuccess;
+  cx->robust.mark(stream);
   return MPCT_OK;
 }
 
@@ -1237,12 +1265,13 @@ extern "C" int32_t mpct_eval_robust_device(mpct_scenario* s, int64_t C, const in
                                            const double* delta, const double* lambda, int32_t nref,
                                            const double* r, const double* v, double j_bound, const mpct_opts* opts,
                                            mpct_robust_result* out, void* stream) {
-  int rc = check_robust(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, out);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_robust(s, b, j_bound, opts, out);
   if (rc) return rc;
   DevCtx* cx = nullptr;
-  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  rc = ctx_for(s, opts, &cx);
   if (rc) return rc;
-  return launch_robust(s, cx, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, out, static_cast<hipStream_t>(stream));
+  return launch_robust(s, cx, b, j_bound, opts, out, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int32_t mpct_eval_robust_tail_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
@@ -1250,15 +1279,15 @@ extern "C" int32_t mpct_eval_robust_tail_device(mpct_scenario* s, int64_t C, con
                                                 const double* r, const double* v, double j_bound,
                                                 const mpct_opts* opts, int32_t nlev, const double* levels,
                                                 mpct_robust_result* out, mpct_robust_tail* tail, void* stream) {
-  int rc = check_tail(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, nlev, levels, out, tail);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_tail(s, b, j_bound, opts, nlev, levels, out, tail);
   if (rc) return rc;
   DevCtx* cx = nullptr;
-  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  rc = ctx_for(s, opts, &cx);
   if (rc) return rc;
   const mpct_robust_result base = out ? *out : mpct_robust_result{};
   const TailReq tq{nlev, levels, tail ? TailOut{tail->quantile, tail->cvar, tail->q_draw} : TailOut{}};
-  return launch_robust(s, cx, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, &base, static_cast<hipStream_t>(stream),
-                       &tq);
+  return launch_robust(s, cx, b, j_bound, opts, &base, static_cast<hipStream_t>(stream), &tq);
 }
 
 // Test hook, deliberately not declared in include/mpct.h: robust_tail_kernel alone, on per-simulation
@@ -1292,65 +1321,50 @@ extern "C" int32_t mpct_internal_robust_reduce(int64_t C, int32_t D, int32_t my,
 }
 
 // the host-pointer robust entries after their argument checks; nlev = 0: no tail
-static int eval_robust_host(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
-                            const double* lambda, int32_t nref, const double* r, const double* v, double j_bound,
-                            const mpct_opts* opts, const mpct_robust_result* out, int32_t nlev, const double* levels,
+static int eval_robust_host(mpct_scenario* s, const Batch& b, double j_bound, const mpct_opts* opts,
+                            const mpct_robust_result* out, int32_t nlev, const double* levels,
                             const mpct_robust_tail* tail) {
   DevCtx* cx = nullptr;
-  int rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  int rc = ctx_for(s, opts, &cx);
   if (rc) return rc;
-  if (C == 0) return MPCT_OK;
-  // host buffers in, host buffers out on the context's own stream, staged as eval_host does
-  const int my = s->my;
-  const size_t S = (size_t)(C * nref);
-  HostStage hs(s, cx, C);
-  const size_t o_mean = hs.slot(C * my * 8), o_worst = hs.slot(C * my * 8), o_nf = hs.slot(C * 4), o_wd = hs.slot(C * 4);
-  const size_t o_st = hs.slot(C * 4), o_J1 = out->J1 ? hs.slot(S * my * 8) : 0;
-  const size_t o_q = nlev ? hs.slot(C * nlev * 8) : 0, o_cv = nlev ? hs.slot(C * nlev * 8) : 0;
-  const size_t o_qd = nlev ? hs.slot(C * nlev * 4) : 0;
-  rc = hs.upload(s, N2, Nu, delta, lambda, nref, r, v);
+  if (b.C == 0) return MPCT_OK;
+  // host buffers in, host buffers out on the context's own stream, staged as eval_host does.  The record is
+  // always written on the device, the sample J1 where asked for, the tail arrays whenever there are levels
+  const size_t C = (size_t)b.C, S = C * b.nref, cm = C * s->my * 8, cl = C * nlev;
+  const mpct_robust_tail ht = tail ? *tail : mpct_robust_tail{};
+  HostStage hs(s, cx, b.C);
+  const int s_mean = hs.keep(out->mean, cm), s_worst = hs.keep(out->worst, cm), s_nf = hs.keep(out->n_failed, C * 4),
+            s_wd = hs.keep(out->worst_draw, C * 4), s_st = hs.keep(out->status, C * 4), s_J1 = hs.want(out->J1, S * s->my * 8);
+  const int s_q = hs.keep(ht.quantile, cl * 8, nlev > 0), s_cv = hs.keep(ht.cvar, cl * 8, nlev > 0),
+            s_qd = hs.keep(ht.q_draw, cl * 4, nlev > 0);
+  rc = hs.upload(s, b);
   if (rc) return rc;
-  mpct_robust_result dres{};
-  dres.mean = hs.at<double>(o_mean);
-  dres.worst = hs.at<double>(o_worst);
-  dres.n_failed = hs.at<int32_t>(o_nf);
-  dres.worst_draw = hs.at<int32_t>(o_wd);
-  dres.status = hs.at<int32_t>(o_st);
-  dres.J1 = out->J1 ? hs.at<double>(o_J1) : nullptr;
-  const TailReq tq{nlev, levels, nlev ? TailOut{hs.at<double>(o_q), hs.at<double>(o_cv), hs.at<int32_t>(o_qd)} : TailOut{}};
-  rc = launch_robust(s, cx, C, hs.N2(), hs.Nu(), hs.delta(), hs.lambda(), nref, hs.r, hs.v, j_bound, opts, &dres, hs.st,
-                     nlev ? &tq : nullptr);
+  const mpct_robust_result dres{hs.at<double>(s_mean), hs.at<double>(s_worst), hs.at<int32_t>(s_nf),
+                                hs.at<int32_t>(s_wd),  hs.at<int32_t>(s_st),   hs.at<double>(s_J1)};
+  const TailReq tq{nlev, levels, TailOut{hs.at<double>(s_q), hs.at<double>(s_cv), hs.at<int32_t>(s_qd)}};
+  rc = launch_robust(s, cx, hs.dev, j_bound, opts, &dres, hs.st, nlev ? &tq : nullptr);
   if (rc) return hs.abandon(rc);
-  hs.fetch(out->mean, o_mean, C * my * 8);
-  hs.fetch(out->worst, o_worst, C * my * 8);
-  hs.fetch(out->n_failed, o_nf, C * 4);
-  hs.fetch(out->worst_draw, o_wd, C * 4);
-  hs.fetch(out->status, o_st, C * 4);
-  hs.fetch(out->J1, o_J1, S * my * 8);
-  if (nlev && tail) {
-    hs.fetch(tail->quantile, o_q, C * nlev * 8);
-    hs.fetch(tail->cvar, o_cv, C * nlev * 8);
-    hs.fetch(tail->q_draw, o_qd, C * nlev * 4);
-  }
   return hs.finish();
 }
 
 extern "C" int32_t mpct_eval_robust(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
                                     const double* delta, const double* lambda, int32_t nref, const double* r,
                                     const double* v, double j_bound, const mpct_opts* opts, mpct_robust_result* out) {
-  const int rc = check_robust(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, out);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  const int rc = check_robust(s, b, j_bound, opts, out);
   if (rc) return rc;
-  return eval_robust_host(s, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, out, 0, nullptr, nullptr);
+  return eval_robust_host(s, b, j_bound, opts, out, 0, nullptr, nullptr);
 }
 
 extern "C" int32_t mpct_eval_robust_tail(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
                                          const double* delta, const double* lambda, int32_t nref, const double* r,
                                          const double* v, double j_bound, const mpct_opts* opts, int32_t nlev,
                                          const double* levels, mpct_robust_result* out, mpct_robust_tail* tail) {
-  const int rc = check_tail(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, nlev, levels, out, tail);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  const int rc = check_tail(s, b, j_bound, opts, nlev, levels, out, tail);
   if (rc) return rc;
   const mpct_robust_result base = out ? *out : mpct_robust_result{};
-  return eval_robust_host(s, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, &base, nlev, levels, tail);
+  return eval_robust_host(s, b, j_bound, opts, &base, nlev, levels, tail);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1460,81 +1474,65 @@ extern "C" int32_t mpct_internal_index_budget(int64_t bytes) {
   return MPCT_OK;
 }
 
+// the trajectories y | u of one candidate in bytes, and the candidates a chunk of the index entries takes: what
+// the budget holds, at least one
+static size_t traj_bytes(int32_t nref, int my, int nu, int nit) { return (size_t)nref * (my + nu) * nit * 8; }
+static int64_t index_chunk(int64_t C, int32_t nref, int my, int nu, int nit) {
+  const size_t budget = g_index_budget > 0 ? (size_t)g_index_budget : (size_t)MPCT_INDEX_SCRATCH_BYTES;
+  return std::min<int64_t>(C, std::max<int64_t>(1, (int64_t)(budget / traj_bytes(nref, my, nu, nit))));
+}
+
+// the caller's options for the closed loops of an index entry: closed loop, trajectories on
+static mpct_opts traj_opts(const mpct_opts* opts) {
+  mpct_opts o = opts ? *opts : mpct_opts{0, 0, 0, -1, 0.0};
+  o.open_loop = 0;
+  o.want_traj = 1;
+  return o;
+}
+
+// width of index field id in a scenario's records, and whether it is an integer field
+static int field_width(const mpct_scenario* s, int id) { return id < 8 ? s->my : s->nu; }
+static bool field_is_int(int id) { return id == MPCT_IX_T_EMAX || id == MPCT_IX_SETTLE; }
+
 // the argument checks of the two scoring entries, in the header's order; nothing here touches a device
-static int check_eval_indices(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* N2, const int32_t* Nu,
-                              const double* delta, const double* lambda, const double* r, const double* v,
-                              const mpct_opts* opts, const mpct_index_params* p, const mpct_result* res,
-                              const mpct_index_result* out) {
+static int check_eval_indices(mpct_scenario* s, const Batch& b, const mpct_opts* opts, const mpct_index_params* p,
+                              const mpct_result* res, const mpct_index_result* out) {
   if (!s) return fail(MPCT_EINVAL, "null scenario");
   if (!p) return fail(MPCT_EINVAL, "null params");
   if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the index entries are closed-loop only: open_loop must be 0");
   if (res && (res->y || res->u || res->ys || res->uopt))
     return fail(MPCT_EINVAL, "the trajectory pointers of res must be NULL: the trajectories stay on the device");
   const mpct_result any{};
-  const int rc = check_args(s, C, nref, N2, Nu, delta, lambda, r, v, opts, &any);
+  const int rc = check_args(s, b, opts, &any);
   if (rc) return rc;
-  return index_check_tail(C * nref, s->my, s->nu, s->nit, p, out, true, true);
-}
-
-// the context's trajectory scratch, at least `bytes`; orders `stream` after the last index call that
-// used it.  A regrow waits for that work before the old buffer is freed (HostStage::ensure's rule)
-static int index_scratch(DevCtx* cx, size_t bytes, hipStream_t stream, char** out) {
-  if (!cx->index_used && hipEventCreateWithFlags(&cx->index_used, hipEventDisableTiming) != hipSuccess)
-    return fail(MPCT_EDEVICE, "hipEventCreate failed");
-  if (bytes > cx->dindex_bytes) {
-    if (cx->index_pending) (void)hipEventSynchronize(cx->index_used);
-    cx->index_pending = false;
-    if (cx->dindex) {
-      (void)hipStreamSynchronize(stream);
-      (void)hipFree(cx->dindex);
-    }
-    cx->dindex = nullptr;
-    cx->dindex_bytes = 0;
-    if (hipMalloc(&cx->dindex, bytes) != hipSuccess) return fail(MPCT_ENOMEM, "hipMalloc(trajectory scratch) failed");
-    cx->dindex_bytes = bytes;
-  }
-  if (cx->index_pending && hipStreamWaitEvent(stream, cx->index_used, 0) != hipSuccess)
-    return fail(MPCT_EDEVICE, "hipStreamWaitEvent failed");
-  *out = static_cast<char*>(cx->dindex);
-  return MPCT_OK;
+  return index_check_tail(b.C * b.nref, s->my, s->nu, s->nit, p, out, true, true);
 }
 
 // enqueue one batch with device pointers on `stream` (ctx's device is current): chunks of whole
 // candidates through launch_batch into the trajectory scratch, each followed by the index kernel
-static int launch_indices(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2, const int32_t* Nu,
-                          const double* delta, const double* lambda, int32_t nref, const double* r, const double* v,
-                          const mpct_opts* opts, const mpct_index_params* p, const mpct_result* res,
-                          const mpct_index_result* out, hipStream_t stream) {
-  if (C == 0) return MPCT_OK;
+static int launch_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, const mpct_opts* opts, const mpct_index_params* p,
+                          const mpct_result* res, const mpct_index_result* out, hipStream_t stream) {
+  if (b.C == 0) return MPCT_OK;
   const int my = s->my, nu = s->nu, nit = s->nit;
-  const size_t per = (size_t)nref * (my + nu) * nit * 8;  // one candidate's trajectories
-  const size_t budget = g_index_budget > 0 ? (size_t)g_index_budget : (size_t)MPCT_INDEX_SCRATCH_BYTES;
-  const int64_t cc = std::min<int64_t>(C, std::max<int64_t>(1, (int64_t)(budget / per)));
+  const int32_t nref = b.nref;
+  const int64_t cc = index_chunk(b.C, nref, my, nu, nit);
   char* scr = nullptr;
-  int rc = index_scratch(cx, (size_t)cc * per, stream, &scr);
+  int rc = cx->index.acquire((size_t)cc * traj_bytes(nref, my, nu, nit), stream, "trajectory scratch", &scr);
   if (rc) return rc;
-  mpct_opts o = opts ? *opts : mpct_opts{0, 0, 0, -1, 0.0};
-  o.open_loop = 0;
-  o.want_traj = 1;
+  const mpct_opts o = traj_opts(opts);
   const IndexOut io = index_out(out);
-  const mpct_result none{};
-  const mpct_result& base = res ? *res : none;
-  for (int64_t c0 = 0; c0 < C && rc == MPCT_OK; c0 += cc) {
-    const int64_t n = std::min(cc, C - c0), s0 = c0 * nref;
-    mpct_result per_chunk{};
-    per_chunk.J1 = base.J1 ? base.J1 + s0 * my : nullptr;
-    per_chunk.j21 = base.j21 ? base.j21 + s0 * my : nullptr;
-    per_chunk.j22 = base.j22 ? base.j22 + s0 * my : nullptr;
-    per_chunk.Jnu = base.Jnu ? base.Jnu + s0 * nu : nullptr;
-    per_chunk.status = base.status ? base.status + s0 : nullptr;
-    per_chunk.qp_iters = base.qp_iters ? base.qp_iters + s0 : nullptr;
+  for (int64_t c0 = 0; c0 < b.C && rc == MPCT_OK; c0 += cc) {
+    const int64_t n = std::min(cc, b.C - c0), s0 = c0 * nref;
+    // the caller's cost fields from this chunk's first simulation on (its trajectory pointers are NULL)
+    mpct_result per_chunk = res ? *res : mpct_result{};
+    each_field(per_chunk, my, nu, nit, [&](auto*& f, int64_t w) { f = f ? f + s0 * w : nullptr; });
     per_chunk.y = reinterpret_cast<double*>(scr);
     per_chunk.u = per_chunk.y + (size_t)n * nref * my * nit;
-    rc = launch_batch(s, cx, n, N2 + c0, Nu + c0, delta + c0 * my, lambda + c0 * nu, nref, r, v, &o, &per_chunk, stream);
+    rc = launch_batch(s, cx, b.sub(c0, n, my, nu), &o, &per_chunk, stream);
     if (rc == MPCT_OK)
-      rc = index_launch(per_chunk.y, per_chunk.u, r, n * nref, nref, my, nu, nit, p, io.from(s0, my, nu), stream);
+      rc = index_launch(per_chunk.y, per_chunk.u, b.r, n * nref, nref, my, nu, nit, p, io.from(s0, my, nu), stream);
   }
-  cx->index_pending = hipEventRecord(cx->index_used, stream) == hipSuccess;
+  cx->index.mark(stream);
   return rc;
 }
 
@@ -1542,65 +1540,51 @@ extern "C" int32_t mpct_eval_indices_device(mpct_scenario* s, int64_t C, const i
                                             const double* delta, const double* lambda, int32_t nref, const double* r,
                                             const double* v, const mpct_opts* opts, const mpct_index_params* params,
                                             mpct_result* res, const mpct_index_result* out, void* stream) {
-  int rc = check_eval_indices(s, C, nref, N2, Nu, delta, lambda, r, v, opts, params, res, out);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_eval_indices(s, b, opts, params, res, out);
   if (rc) return rc;
   if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
   DevCtx* cx = nullptr;
-  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  rc = ctx_for(s, opts, &cx);
   if (rc) return rc;
-  return launch_indices(s, cx, C, N2, Nu, delta, lambda, nref, r, v, opts, params, res, out,
-                        static_cast<hipStream_t>(stream));
+  return launch_indices(s, cx, b, opts, params, res, out, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int32_t mpct_eval_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
                                      const double* lambda, int32_t nref, const double* r, const double* v,
                                      const mpct_opts* opts, const mpct_index_params* params, mpct_result* res,
                                      const mpct_index_result* out) {
-  int rc = check_eval_indices(s, C, nref, N2, Nu, delta, lambda, r, v, opts, params, res, out);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_eval_indices(s, b, opts, params, res, out);
   if (rc) return rc;
   if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
   DevCtx* cx = nullptr;
-  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  rc = ctx_for(s, opts, &cx);
   if (rc) return rc;
   // host buffers in, the records out on the context's own stream, staged as eval_host does
-  const int my = s->my, nu = s->nu;
   const size_t S = (size_t)(C * nref);
   HostStage hs(s, cx, C);
-  const size_t o_J1 = hs.slot(S * my * 8), o_j21 = hs.slot(S * my * 8), o_j22 = hs.slot(S * my * 8);
-  const size_t o_Jnu = hs.slot(S * nu * 8), o_st = hs.slot(S * 4), o_it = hs.slot(S * 8);
-  size_t o_f[13];
-  for (int k = 0; k < 13; ++k) o_f[k] = hs.slot(S * (k < 8 ? my : nu) * 8);
-  rc = hs.upload(s, N2, Nu, delta, lambda, nref, r, v);
+  // slots 0..9: with a `res` its six cost fields live on the device, its trajectories never; 10..22: the index
+  // fields that are asked for
+  mpct_result hres = res ? *res : mpct_result{};
+  int k = 0;
+  each_field(hres, s->my, s->nu, s->nit, [&](auto* host, int64_t w) {
+    hs.keep(host, S * w * sizeof(*host), res && k < 6);
+    ++k;
+  });
+  void* const host[13] = {out->iae,    out->ise, out->itae, out->emax,  out->t_emax, out->over, out->e_final,
+                          out->settle, out->tv,  out->du2,  out->dumax, out->u_lo,   out->u_hi};
+  for (int id = 0; id < 13; ++id) hs.want(host[id], S * field_width(s, id) * (field_is_int(id) ? 4 : 8));
+  rc = hs.upload(s, b);
   if (rc) return rc;
   mpct_result dres{};
-  if (res) {
-    dres.J1 = hs.at<double>(o_J1);
-    dres.j21 = hs.at<double>(o_j21);
-    dres.j22 = hs.at<double>(o_j22);
-    dres.Jnu = hs.at<double>(o_Jnu);
-    dres.status = hs.at<int32_t>(o_st);
-    dres.qp_iters = hs.at<int64_t>(o_it);
-  }
-  auto dd = [&](const void* want, int k) { return want ? hs.at<double>(o_f[k]) : nullptr; };
-  auto di = [&](const void* want, int k) { return want ? hs.at<int32_t>(o_f[k]) : nullptr; };
-  const mpct_index_result dout{dd(out->iae, 0),     dd(out->ise, 1),    dd(out->itae, 2), dd(out->emax, 3),
-                               di(out->t_emax, 4),  dd(out->over, 5),   dd(out->e_final, 6), di(out->settle, 7),
-                               dd(out->tv, 8),      dd(out->du2, 9),    dd(out->dumax, 10),  dd(out->u_lo, 11),
-                               dd(out->u_hi, 12)};
-  rc = launch_indices(s, cx, C, hs.N2(), hs.Nu(), hs.delta(), hs.lambda(), nref, hs.r, hs.v, opts, params,
-                      res ? &dres : nullptr, &dout, hs.st);
+  k = 0;
+  each_field(dres, s->my, s->nu, s->nit, [&](auto*& dev, int64_t) { hs.bind(k++, dev); });
+  auto dd = [&](int id) { return hs.at<double>(10 + id); };
+  auto di = [&](int id) { return hs.at<int32_t>(10 + id); };
+  const mpct_index_result dout{dd(0), dd(1), dd(2), dd(3), di(4), dd(5), dd(6), di(7), dd(8), dd(9), dd(10), dd(11), dd(12)};
+  rc = launch_indices(s, cx, hs.dev, opts, params, res ? &dres : nullptr, &dout, hs.st);
   if (rc) return hs.abandon(rc);
-  if (res) {
-    hs.fetch(res->J1, o_J1, S * my * 8);
-    hs.fetch(res->j21, o_j21, S * my * 8);
-    hs.fetch(res->j22, o_j22, S * my * 8);
-    hs.fetch(res->Jnu, o_Jnu, S * nu * 8);
-    hs.fetch(res->status, o_st, S * 4);
-    hs.fetch(res->qp_iters, o_it, S * 8);
-  }
-  void* const dst[13] = {out->iae, out->ise, out->itae, out->emax, out->t_emax, out->over, out->e_final,
-                         out->settle, out->tv, out->du2, out->dumax, out->u_lo, out->u_hi};
-  for (int k = 0; k < 13; ++k) hs.fetch(dst[k], o_f[k], S * (k < 8 ? my : nu) * ((k == 4 || k == 7) ? 4 : 8));
   return hs.finish();
 }
 
@@ -1690,16 +1674,10 @@ extern "C" int32_t mpct_draw_stats(const void* x, int32_t x_type, const int32_t*
   return cs.close(rc);
 }
 
-// width of index field id in a scenario's records, and whether it is an integer field
-static int field_width(const mpct_scenario* s, int id) { return id < 8 ? s->my : s->nu; }
-static bool field_is_int(int id) { return id == MPCT_IX_T_EMAX || id == MPCT_IX_SETTLE; }
-
 // the argument checks of the two robust index entries, in the header's order; nothing here touches a device
-static int check_robust_indices(mpct_scenario* s, int64_t C, int32_t nref, const int32_t* N2, const int32_t* Nu,
-                                const double* delta, const double* lambda, const double* r, const double* v,
-                                double j_bound, const mpct_opts* opts, const mpct_index_params* p, int32_t nsel,
-                                const int32_t* fields, int32_t nlev, const double* levels,
-                                const mpct_robust_result* base, const mpct_draw_stats_result* out) {
+static int check_robust_indices(mpct_scenario* s, const Batch& b, double j_bound, const mpct_opts* opts,
+                                const mpct_index_params* p, int32_t nsel, const int32_t* fields, int32_t nlev,
+                                const double* levels, const mpct_robust_result* base, const mpct_draw_stats_result* out) {
   if (!s) return fail(MPCT_EINVAL, "null scenario");
   if (!p) return fail(MPCT_EINVAL, "null params");
   if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the index entries are closed-loop only: open_loop must be 0");
@@ -1710,7 +1688,7 @@ static int check_robust_indices(mpct_scenario* s, int64_t C, int32_t nref, const
     if (seen & (1u << fields[q])) return fail(MPCT_EINVAL, "field id repeated");
     seen |= 1u << fields[q];
   }
-  if (nref < 1) return fail(MPCT_EINVAL, "nref < 1: the statistics need at least one draw");
+  if (b.nref < 1) return fail(MPCT_EINVAL, "nref < 1: the statistics need at least one draw");
   if (!(j_bound >= 0.0)) return fail(MPCT_EINVAL, "j_bound must be >= 0 (0 = 1e100, +inf allowed), not negative or NaN");
   int rc = stats_check_levels(nlev, levels);
   if (rc) return rc;
@@ -1720,12 +1698,12 @@ static int check_robust_indices(mpct_scenario* s, int64_t C, int32_t nref, const
   if (base && base->J1) return fail(MPCT_EINVAL, "base->J1 must be NULL: the sample lives per chunk");
   if (nlev == 0 && out && stats_out(out).any_level()) return fail(MPCT_EINVAL, "quantile, cvar and q_draw need nlev >= 1");
   const mpct_result any{};
-  rc = check_args(s, C, nref, N2, Nu, delta, lambda, r, v, opts, &any);
+  rc = check_args(s, b, opts, &any);
   if (rc) return rc;
   rc = index_check_params(s->nit, p);
   if (rc) return rc;
-  if (nref > MPCT_TAIL_MAX_DRAWS) return fail(MPCT_ERANGE, "nref > MPCT_TAIL_MAX_DRAWS (4096): the kernel's LDS holds no more draws");
-  if (C * nref * (int64_t)s->my > kIndexMaxRows || C * nref * (int64_t)s->nu > kIndexMaxRows)
+  if (b.nref > MPCT_TAIL_MAX_DRAWS) return fail(MPCT_ERANGE, "nref > MPCT_TAIL_MAX_DRAWS (4096): the kernel's LDS holds no more draws");
+  if (b.C * b.nref * (int64_t)s->my > kIndexMaxRows || b.C * b.nref * (int64_t)s->nu > kIndexMaxRows)
     return fail(MPCT_ERANGE, "C*nref*my or C*nref*nu exceeds MPCT_INDEX_MAX_ROWS");
   return MPCT_OK;
 }
@@ -1733,21 +1711,19 @@ static int check_robust_indices(mpct_scenario* s, int64_t C, int32_t nref, const
 // enqueue one batch with device pointers on `stream` (ctx's device is current).  Per chunk of whole
 // candidates: the closed loops with trajectories, J1 and status into the context's index scratch, the
 // selected index records, alive[c][k], then the statistics of each selected field and the base record
-static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, int64_t C, const int32_t* N2, const int32_t* Nu,
-                                 const double* delta, const double* lambda, int32_t nref, const double* r, const double* v,
-                                 double j_bound, const mpct_opts* opts, const mpct_index_params* p, int32_t nsel,
-                                 const int32_t* fields, int32_t nlev, const double* levels, const RobustOut& base,
-                                 const DrawStatsOut& out, hipStream_t stream) {
-  if (C == 0) return MPCT_OK;
+static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
+                                 const mpct_index_params* p, int32_t nsel, const int32_t* fields, int32_t nlev,
+                                 const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream) {
+  if (b.C == 0) return MPCT_OK;
   const int my = s->my, nu = s->nu, nit = s->nit;
+  const int64_t C = b.C;
+  const int32_t nref = b.nref;
   const double bound = j_bound == 0.0 ? kRobustDefaultBound : j_bound;
-  const size_t per = (size_t)nref * (my + nu) * nit * 8;  // one candidate's trajectories: launch_indices' chunking
-  const size_t budget = g_index_budget > 0 ? (size_t)g_index_budget : (size_t)MPCT_INDEX_SCRATCH_BYTES;
-  const int64_t cc = std::min<int64_t>(C, std::max<int64_t>(1, (int64_t)(budget / per)));
+  const int64_t cc = index_chunk(C, nref, my, nu, nit);  // launch_indices' chunking
   // the chunk's scratch: y | u | J1 | status | alive | the selected fields' records, each 256-B aligned
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  auto al = [](size_t n) { return (n + 255) & ~(size_t)255; };
   const size_t Sc = (size_t)cc * nref;
-  const size_t o_j1 = al((size_t)cc * per), o_st = o_j1 + al(Sc * my * 8), o_al = o_st + al(Sc * 4);
+  const size_t o_j1 = al((size_t)cc * traj_bytes(nref, my, nu, nit)), o_st = o_j1 + al(Sc * my * 8), o_al = o_st + al(Sc * 4);
   size_t o_f[13], off = o_al + al(Sc * 4);
   int W = 0;
   for (int q = 0; q < nsel; ++q) {
@@ -1756,11 +1732,9 @@ static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, int64_t C, const 
     W += field_width(s, fields[q]);
   }
   char* scr = nullptr;
-  int rc = index_scratch(cx, off, stream, &scr);
+  int rc = cx->index.acquire(off, stream, "trajectory scratch", &scr);
   if (rc) return rc;
-  mpct_opts o = opts ? *opts : mpct_opts{0, 0, 0, -1, 0.0};
-  o.open_loop = 0;
-  o.want_traj = 1;
+  const mpct_opts o = traj_opts(opts);
   void* rec[13] = {nullptr};
   for (int q = 0; q < nsel; ++q) rec[fields[q]] = scr + o_f[q];
   const IndexOut io{(double*)rec[0], (double*)rec[1], (double*)rec[2], (double*)rec[3],  (int*)rec[4],
@@ -1776,8 +1750,8 @@ static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, int64_t C, const 
     per_chunk.y = reinterpret_cast<double*>(scr);
     per_chunk.u = per_chunk.y + (size_t)n * nref * my * nit;
     int32_t* alive = reinterpret_cast<int32_t*>(scr + o_al);
-    rc = launch_batch(s, cx, n, N2 + c0, Nu + c0, delta + c0 * my, lambda + c0 * nu, nref, r, v, &o, &per_chunk, stream);
-    if (rc == MPCT_OK) rc = index_launch(per_chunk.y, per_chunk.u, r, n * nref, nref, my, nu, nit, p, io, stream);
+    rc = launch_batch(s, cx, b.sub(c0, n, my, nu), &o, &per_chunk, stream);
+    if (rc == MPCT_OK) rc = index_launch(per_chunk.y, per_chunk.u, b.r, n * nref, nref, my, nu, nit, p, io, stream);
     if (rc != MPCT_OK) break;
     int lrc = launch_draw_alive(n, nref, my, bound, per_chunk.J1, per_chunk.status, alive, stream, &err);
     if (lrc == 0 && any_base) {
@@ -1800,7 +1774,7 @@ static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, int64_t C, const 
       col += w;
     }
   }
-  cx->index_pending = hipEventRecord(cx->index_used, stream) == hipSuccess;
+  cx->index.mark(stream);
   return rc;
 }
 
@@ -1811,16 +1785,16 @@ extern "C" int32_t mpct_eval_robust_indices_device(mpct_scenario* s, int64_t C, 
                                                    const int32_t* fields, int32_t nlev, const double* levels,
                                                    mpct_robust_result* base, const mpct_draw_stats_result* out,
                                                    void* stream) {
-  int rc = check_robust_indices(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, params, nsel, fields, nlev, levels,
-                                base, out);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_robust_indices(s, b, j_bound, opts, params, nsel, fields, nlev, levels, base, out);
   if (rc) return rc;
   if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
   DevCtx* cx = nullptr;
-  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  rc = ctx_for(s, opts, &cx);
   if (rc) return rc;
   const RobustOut ro = base ? RobustOut{base->mean, base->worst, base->n_failed, base->worst_draw, base->status} : RobustOut{};
-  return launch_robust_indices(s, cx, C, N2, Nu, delta, lambda, nref, r, v, j_bound, opts, params, nsel, fields, nlev,
-                               levels, ro, out ? stats_out(out) : DrawStatsOut{}, static_cast<hipStream_t>(stream));
+  return launch_robust_indices(s, cx, b, j_bound, opts, params, nsel, fields, nlev, levels, ro,
+                               out ? stats_out(out) : DrawStatsOut{}, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int32_t mpct_eval_robust_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
@@ -1829,51 +1803,34 @@ extern "C" int32_t mpct_eval_robust_indices(mpct_scenario* s, int64_t C, const i
                                             const mpct_index_params* params, int32_t nsel, const int32_t* fields,
                                             int32_t nlev, const double* levels, mpct_robust_result* base,
                                             const mpct_draw_stats_result* out) {
-  int rc = check_robust_indices(s, C, nref, N2, Nu, delta, lambda, r, v, j_bound, opts, params, nsel, fields, nlev, levels,
-                                base, out);
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_robust_indices(s, b, j_bound, opts, params, nsel, fields, nlev, levels, base, out);
   if (rc) return rc;
   if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
   DevCtx* cx = nullptr;
-  rc = device_ctx(s, opts ? opts->device : -1, &cx);
+  rc = ctx_for(s, opts, &cx);
   if (rc) return rc;
-  // host buffers in, the records out on the context's own stream, staged as eval_host does
-  const int my = s->my;
+  // host buffers in, the records out on the context's own stream, staged as eval_host does: every field of
+  // base and out lives on the device only where it is asked for (the per-level ones only with nlev >= 1)
   size_t W = 0;
   for (int q = 0; q < nsel; ++q) W += field_width(s, fields[q]);
-  const size_t cols = (size_t)C * W, nl = (size_t)std::max(nlev, 1);
+  const size_t cm = (size_t)C * s->my * 8, cols = (size_t)C * W, lev = cols * (size_t)nlev;
   const mpct_robust_result hb = base ? *base : mpct_robust_result{};
   const mpct_draw_stats_result ho = out ? *out : mpct_draw_stats_result{};
   HostStage hs(s, cx, C);
-  const size_t o_mean = hs.slot(C * my * 8), o_worst = hs.slot(C * my * 8), o_nf = hs.slot(C * 4), o_wd = hs.slot(C * 4);
-  const size_t o_st = hs.slot(C * 4);
-  const size_t o_n = hs.slot(cols * 4), o_mn = hs.slot(cols * 8), o_lo = hs.slot(cols * 8), o_ld = hs.slot(cols * 4);
-  const size_t o_hi = hs.slot(cols * 8), o_hd = hs.slot(cols * 4), o_q = hs.slot(cols * nl * 8);
-  const size_t o_cv = hs.slot(cols * nl * 8), o_qd = hs.slot(cols * nl * 4);
-  rc = hs.upload(s, N2, Nu, delta, lambda, nref, r, v);
+  const int s_mean = hs.want(hb.mean, cm), s_worst = hs.want(hb.worst, cm), s_nf = hs.want(hb.n_failed, (size_t)C * 4),
+            s_wd = hs.want(hb.worst_draw, (size_t)C * 4), s_st = hs.want(hb.status, (size_t)C * 4);
+  const int s_n = hs.want(ho.n, cols * 4), s_mn = hs.want(ho.mean, cols * 8), s_lo = hs.want(ho.lo, cols * 8),
+            s_ld = hs.want(ho.lo_draw, cols * 4), s_hi = hs.want(ho.hi, cols * 8), s_hd = hs.want(ho.hi_draw, cols * 4),
+            s_q = hs.want(ho.quantile, lev * 8), s_cv = hs.want(ho.cvar, lev * 8), s_qd = hs.want(ho.q_draw, lev * 4);
+  rc = hs.upload(s, b);
   if (rc) return rc;
-  auto dd = [&](const void* want, size_t o) { return want ? hs.at<double>(o) : nullptr; };
-  auto di = [&](const void* want, size_t o) { return want ? hs.at<int32_t>(o) : nullptr; };
-  const RobustOut ro{dd(hb.mean, o_mean), dd(hb.worst, o_worst), di(hb.n_failed, o_nf), di(hb.worst_draw, o_wd),
-                     di(hb.status, o_st)};
-  const DrawStatsOut dv{di(ho.n, o_n),   dd(ho.mean, o_mn),    dd(ho.lo, o_lo),   di(ho.lo_draw, o_ld), dd(ho.hi, o_hi),
-                        di(ho.hi_draw, o_hd), dd(ho.quantile, o_q), dd(ho.cvar, o_cv), di(ho.q_draw, o_qd)};
-  rc = launch_robust_indices(s, cx, C, hs.N2(), hs.Nu(), hs.delta(), hs.lambda(), nref, hs.r, hs.v, j_bound, opts, params,
-                             nsel, fields, nlev, levels, ro, dv, hs.st);
+  const RobustOut ro{hs.at<double>(s_mean), hs.at<double>(s_worst), hs.at<int32_t>(s_nf), hs.at<int32_t>(s_wd),
+                     hs.at<int32_t>(s_st)};
+  const DrawStatsOut dv{hs.at<int32_t>(s_n),  hs.at<double>(s_mn), hs.at<double>(s_lo), hs.at<int32_t>(s_ld), hs.at<double>(s_hi),
+                        hs.at<int32_t>(s_hd), hs.at<double>(s_q),  hs.at<double>(s_cv), hs.at<int32_t>(s_qd)};
+  rc = launch_robust_indices(s, cx, hs.dev, j_bound, opts, params, nsel, fields, nlev, levels, ro, dv, hs.st);
   if (rc) return hs.abandon(rc);
-  hs.fetch(hb.mean, o_mean, C * my * 8);
-  hs.fetch(hb.worst, o_worst, C * my * 8);
-  hs.fetch(hb.n_failed, o_nf, C * 4);
-  hs.fetch(hb.worst_draw, o_wd, C * 4);
-  hs.fetch(hb.status, o_st, C * 4);
-  hs.fetch(ho.n, o_n, cols * 4);
-  hs.fetch(ho.mean, o_mn, cols * 8);
-  hs.fetch(ho.lo, o_lo, cols * 8);
-  hs.fetch(ho.lo_draw, o_ld, cols * 4);
-  hs.fetch(ho.hi, o_hi, cols * 8);
-  hs.fetch(ho.hi_draw, o_hd, cols * 4);
-  hs.fetch(ho.quantile, o_q, cols * nl * 8);
-  hs.fetch(ho.cvar, o_cv, cols * nl * 8);
-  hs.fetch(ho.q_draw, o_qd, cols * nl * 4);
   return hs.finish();
 }
 
