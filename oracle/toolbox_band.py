@@ -339,9 +339,10 @@ def band_qp(sc: BandScenario, G, f, rvec, u_prev, N2, Nu, q, wl, pin=None, with_
 
 
 def closedloop_band(sc: BandScenario, r, v, N2: int, Nu: int, delta, lam, nit: int,
-                    open_loop: bool = True, trace=None) -> CLResult:
+                    open_loop: bool = True, trace=None, xtrace=None) -> CLResult:
     """[y,u,t,ys,uopt] = closedloop_toolbox(mpc,r,v,N,Nu,delta,lambda,nit) restated for the
-    band-mode / measured-disturbance configuration.  r: my x nit, v: nd x nit."""
+    band-mode / measured-disturbance configuration.  r: my x nit, v: nd x nit.  trace / xtrace:
+    lists that receive every step's free response and QP solution [dU; eps]."""
     my, nu, nd, nin = sc.my, sc.nu, sc.nd, sc.nin
     r = np.asarray(r, dtype=float).reshape(my, nit)
     v = np.asarray(v, dtype=float).reshape(nd, nit)
@@ -391,6 +392,8 @@ def closedloop_band(sc: BandScenario, r, v, N2: int, Nu: int, delta, lam, nit: i
             trace.append(f.copy())
         x, it = band_qp(sc, G, f, r[:, t], u_prev, N2, Nu, wq, wl)
         iters += it
+        if xtrace is not None:
+            xtrace.append(x.copy())
         du = np.array([x[n * Nu] for n in range(nu)])
         DU[:, t] = du
         EPS[t] = x[M]

@@ -42,10 +42,11 @@ def _free(ba_m, nu, U, t, N2, u_hold, v_hold):
     return simulate(ba_m, Uf, t + N2 + 1)[:, t + 1:]
 
 
-def closedloop_band_bias(sc, plant, r, v, N2, Nu, delta, lam, nit):
+def closedloop_band_bias(sc, plant, r, v, N2, Nu, delta, lam, nit, trace=None, xtrace=None):
     """The closed loop of sc's controller (model sc.plant) on `plant` (my x nin entries) with the
     output-bias estimator.  r: my x nit, v: nd x nit.  Returns a CLResult (y, u, du_hist) with
-    .bias (my x nit)."""
+    .bias (my x nit).  trace / xtrace: lists that receive every step's biased free response and QP
+    solution [dU; eps]."""
     my, nu, nd, nin = sc.my, sc.nu, sc.nd, sc.nin
     r = np.asarray(r, dtype=float).reshape(my, nit)
     v = np.asarray(v, dtype=float).reshape(nd, nit)
@@ -65,6 +66,9 @@ def closedloop_band_bias(sc, plant, r, v, N2, Nu, delta, lam, nit):
         f = (_free(ba_m, nu, U, t, N2, u_prev, v[:, t]) + B[:, t][:, None]).reshape(-1)
         x, it = band_qp(sc, G, f, r[:, t], u_prev, N2, Nu, wq, wl)
         iters += it
+        if trace is not None:
+            trace.append(f.copy())
+            xtrace.append(x.copy())
         DU[:, t] = [x[n * Nu] for n in range(nu)]
         u_prev = u_prev + DU[:, t]
         U[:nu, t] = u_prev

@@ -6,11 +6,18 @@
 //   my*nu model entries, the same way
 //   du_min[nu] du_max[nu] u_min[nu] u_max[nu]
 // filled into an mpct_scenario_desc without CARIMA tables (the library derives them from the model).
+// A band scenario (mdband_kernel.hip; written by tests/band_family.py descriptor_text) starts with
+// the word `band` and its number of measured disturbances, has my*(nu+nd) entries per table and ends
+// with the output bands:
+//   band nd
+//   my nu nit n2_max nu_max ... u_max[nu]           (as above)
+//   y_min[my] y_max[my] ecr_min[my] ecr_max[my] rho
 #pragma once
 #include "scenario_tables.h"
 
 #include <cstdio>
 #include <iostream>
+#include <string>
 
 struct TextDescriptor {
   struct Entries {
@@ -42,16 +49,27 @@ struct TextDescriptor {
     return true;
   }
 
-  int my = 0, nu = 0, nit = 0, n2max = 0, numax = 0;
+  int my = 0, nu = 0, nit = 0, n2max = 0, numax = 0, nd = 0;
+  bool band = false;
   std::vector<int32_t> n1;
   Entries plant, model;
-  std::vector<double> dumin, dumax, umin, umax, yref;
+  std::vector<double> dumin, dumax, umin, umax, yref, ymin, ymax, ecrmin, ecrmax;
+  double rho = 0.0;
   mpct_scenario_desc d{};
 
   // false (with a message printed) on a malformed descriptor
   bool read() {
+    std::cin >> std::ws;
+    if (std::cin.peek() == 'b') {
+      std::string word;
+      if (!(std::cin >> word >> nd) || word != "band" || nd < 0) {
+        std::printf("malformed descriptor: band header\n");
+        return false;
+      }
+      band = true;
+    }
     if (!(std::cin >> my >> nu >> nit >> n2max >> numax) || my < 1 || my > mpct::kMaxOut || nu < 1 ||
-        nu > mpct::kMaxIn || nit < 1) {
+        nu + nd > mpct::kMaxIn || nit < 1) {
       std::printf("malformed descriptor: dims\n");
       return false;
     }
@@ -61,7 +79,7 @@ struct TextDescriptor {
         std::printf("malformed descriptor: n1\n");
         return false;
       }
-    if (!plant.read(my * nu) || !model.read(my * nu) || !read_vec(dumin, nu) || !read_vec(dumax, nu) ||
+    if (!plant.read(my * (nu + nd)) || !model.read(my * (nu + nd)) || !read_vec(dumin, nu) || !read_vec(dumax, nu) ||
         !read_vec(umin, nu) || !read_vec(umax, nu)) {
       std::printf("malformed descriptor: entries / bounds\n");
       return false;
@@ -83,6 +101,20 @@ struct TextDescriptor {
     d.u_min = umin.data();
     d.u_max = umax.data();
     d.yref = yref.data();
+    if (band) {
+      if (!read_vec(ymin, my) || !read_vec(ymax, my) || !read_vec(ecrmin, my) || !read_vec(ecrmax, my) ||
+          !(std::cin >> rho)) {
+        std::printf("malformed descriptor: bands\n");
+        return false;
+      }
+      d.nd = nd;
+      d.mdband = 1;
+      d.y_min = ymin.data();
+      d.y_max = ymax.data();
+      d.ecr_min = ecrmin.data();
+      d.ecr_max = ecrmax.data();
+      d.rho_ecr = rho;
+    }
     return true;
   }
 };
