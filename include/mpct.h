@@ -33,7 +33,10 @@
  *     members' exclusive contributions (mpct_hv_result, mpct_hypervolume_device, mpct_hypervolume), and
  *     the greedy selection of the members that carry a front (mpct_hv_select_result,
  *     mpct_hv_select_device, mpct_hv_select), and the exact hypervolume and contributions for up to three
- *     objectives (mpct_hvx_result, mpct_hypervolume_exact_device, mpct_hypervolume_exact).
+ *     objectives (mpct_hvx_result, mpct_hypervolume_exact_device, mpct_hypervolume_exact), and the limit
+ *     indices (mpct_limit_params, mpct_limit_result, mpct_limit_indices_device, mpct_limit_indices,
+ *     mpct_eval_limit_indices, mpct_eval_limit_indices_device, mpct_eval_robust_limit_indices,
+ *     mpct_eval_robust_limit_indices_device).
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -1045,6 +1048,172 @@ int32_t mpct_eval_robust_indices_device(mpct_scenario* s, int64_t C, const int32
                                         const mpct_index_params* params, int32_t nsel, const int32_t* fields,
                                         int32_t nlev, const double* levels, mpct_robust_result* base,
                                         const mpct_draw_stats_result* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Limit indices per simulation, reduced on the device from the trajectories (limit_indices.hip; DESIGN.md
+ * §20): the counterpart of the performance indices for bounds instead of a reference -- how far, how long and
+ * how late an output was outside its band [y_lo, y_hi] (zone control), and how much of a run the inputs spent
+ * at their amplitude bounds [u_lo, u_hi] or at their rate bounds [du_lo, du_hi] -- as columns for mpct_pareto
+ * or mpct_rank_device, without the trajectories leaving the device.
+ *
+ * Trajectories in mpct_result's layout: y[S][my][nit], u[S][nu][nit].  The indices cover the samples
+ * t = t0 .. nit-1.  Bounds are per channel: y_lo, y_hi [my]; u_lo, u_hi, du_lo, du_hi [nu]; a lower bound may be
+ * -inf and an upper bound +inf (no bound on that side).  Every subtraction below is rounded once.
+ *
+ * Output row (s, i), with m(t) = max(y_lo - y(t), y(t) - y_hi) and ex(t) = m(t) where m(t) > 0, else +0.0
+ * (that is fmax(fmax(y_lo - y, y - y_hi), 0.0) with a zero that is always +0.0):
+ *   viol      sum_t ex(t)
+ *   viol2     sum_t ex(t)*ex(t)
+ *   vmax      max_t ex(t);  t_vmax  the first t that attains it (t0 when ex is 0 throughout)
+ *   n_out     the number of samples with ex(t) > out_tol
+ *   t_in      the last sample with ex(t) > out_tol, plus one; t0 when there is none; nit = "still outside at
+ *             the last sample"
+ *   y_margin  min_t min(y(t) - y_lo, y_hi - y(t)): negative once the band is violated, +inf without a bound; a
+ *             zero margin is +0.0
+ * Input row (s, n), with du(t) = u(t) - u(t-1) for t = t0+1 .. nit-1; sample t is AT-LO when
+ * u(t) - u_lo <= sat_tol and AT-HI when u_hi - u(t) <= sat_tol:
+ *   n_lo, n_hi  the number of at-lo and of at-hi samples, t >= t0
+ *   n_rate      the number of samples t >= t0+1 with du(t) - du_lo <= sat_tol or du_hi - du(t) <= sat_tol
+ *   sat_run     the longest run of consecutive samples that are at-lo or at-hi (0 when there is none)
+ *   u_margin    min_t min(u(t) - u_lo, u_hi - u(t)), t >= t0; +inf without a bound; a zero margin is +0.0
+ *   du_margin   min_t min(du(t) - du_lo, du_hi - du(t)), t >= t0+1; +inf without a bound or over an empty range
+ *
+ * Row validity.  As for the performance indices: a row is VALID when every sample it reads in [t0, nit) is
+ * finite.  An invalid row gives NaN in every double field and -1 in every integer field; other rows are not
+ * affected; samples before t0 are never read.
+ *
+ * No contraction.  ex*ex is rounded to double before it is added: no fused multiply-add anywhere.
+ *
+ * Summation order (fixed), that of the performance indices.  Lane l = (t - t0) mod 64 accumulates its samples
+ * in ascending t, starting from 0.0; the 64 partials are combined as a pairwise tree in lane order, up to
+ * (p0..p31) + (p32..p63).  Counts, maxima, minima, t_vmax, t_in and sat_run are exact whatever the order, and
+ * sat_run is exact across the 64-sample blocks.  A repeated call is bitwise identical and a record does not
+ * depend on the simulation's place in the batch.
+ *
+ * The parameter struct and the six arrays it points to are HOST memory in every entry, the _device ones
+ * included, and are read before the call returns (they travel by value in the kernel argument).  In the two
+ * scenario-free entries a NULL array means no bound (-inf / +inf).
+ *
+ * Any result pointer may be NULL, but not all of them.  y may be NULL when no output-row field is requested,
+ * u when no input-row field is.  Only the requested arrays are written, and only their S rows.
+ *
+ * Argument errors, in this order and before any device is touched:
+ *   MPCT_EINVAL  params NULL; S < 0, my < 0, nu < 0 or nit < 1
+ *   MPCT_EINVAL  t0 < 0 or t0 >= nit
+ *   MPCT_ERANGE  my or nu > MPCT_LIMIT_MAX_CH (the bounds travel in the kernel argument)
+ *   MPCT_EINVAL  out_tol or sat_tol negative, infinite or NaN
+ *   MPCT_EINVAL  a bound that is NaN; a lower bound above its upper bound; a lower bound of +inf or an upper
+ *                bound of -inf
+ *   MPCT_EINVAL  out NULL, or all thirteen of its pointers NULL
+ *   MPCT_EINVAL  an output-row field with my < 1, or (S > 0) with y NULL; an input-row field with nu < 1, or
+ *                (S > 0) with u NULL
+ *   MPCT_ERANGE  S*my or S*nu > MPCT_INDEX_MAX_ROWS (one wave per row, four rows per workgroup)
+ * S = 0 is MPCT_OK and writes nothing. */
+#define MPCT_LIMIT_MAX_CH 32
+typedef struct mpct_limit_params {
+  int32_t t0;          /* first sample of the indices, 0 <= t0 < nit */
+  double out_tol;      /* an output sample counts as outside when ex > out_tol; finite and >= 0 */
+  double sat_tol;      /* an input sample counts as at a bound within sat_tol of it; finite and >= 0 */
+  const double* y_lo;  /* [my] HOST, or NULL */
+  const double* y_hi;  /* [my] */
+  const double* u_lo;  /* [nu] */
+  const double* u_hi;  /* [nu] */
+  const double* du_lo; /* [nu] */
+  const double* du_hi; /* [nu] */
+} mpct_limit_params;
+
+typedef struct mpct_limit_result {
+  double* viol;       /* [S*my] */
+  double* viol2;      /* [S*my] */
+  double* vmax;       /* [S*my] */
+  int32_t* t_vmax;    /* [S*my] */
+  int32_t* n_out;     /* [S*my] */
+  int32_t* t_in;      /* [S*my] */
+  double* y_margin;   /* [S*my] */
+  int32_t* n_lo;      /* [S*nu] */
+  int32_t* n_hi;      /* [S*nu] */
+  int32_t* n_rate;    /* [S*nu] */
+  int32_t* sat_run;   /* [S*nu] */
+  double* u_margin;   /* [S*nu] */
+  double* du_margin;  /* [S*nu] */
+} mpct_limit_result;
+
+/* the field ids of mpct_eval_robust_limit_indices, in the member order of mpct_limit_result */
+#define MPCT_LX_VIOL 0
+#define MPCT_LX_VIOL2 1
+#define MPCT_LX_VMAX 2
+#define MPCT_LX_T_VMAX 3
+#define MPCT_LX_N_OUT 4
+#define MPCT_LX_T_IN 5
+#define MPCT_LX_Y_MARGIN 6
+#define MPCT_LX_N_LO 7
+#define MPCT_LX_N_HI 8
+#define MPCT_LX_N_RATE 9
+#define MPCT_LX_SAT_RUN 10
+#define MPCT_LX_U_MARGIN 11
+#define MPCT_LX_DU_MARGIN 12
+
+/* y, u and the pointers of `out` DEVICE pointers (params and its arrays HOST); enqueued on `stream` (NULL =
+ * default stream) and NOT synchronised.  Needs no scenario and no scratch: one kernel launch. */
+int32_t mpct_limit_indices_device(const double* y, const double* u, int64_t S, int32_t my, int32_t nu, int32_t nit,
+                                  const mpct_limit_params* params, const mpct_limit_result* out, void* stream);
+
+/* Host pointers (MATLAB and C callers), for trajectories from any source.  device: HIP ordinal, -1 = the
+ * current device (an ordinal out of range is MPCT_EINVAL).  Stages on a stream of its own and waits for that
+ * stream only; y travels only behind an output-row field and u only behind an input-row field; the calling
+ * thread's current device is unchanged on return.  Without a device: MPCT_EDEVICE with a message. */
+int32_t mpct_limit_indices(const double* y, const double* u, int64_t S, int32_t my, int32_t nu, int32_t nit,
+                           const mpct_limit_params* params, int32_t device, const mpct_limit_result* out);
+
+/* Score a batch and return only the limit records (host pointers; arguments as mpct_eval_indices, whose
+ * chunking, scratch, `res` and `opts` rules hold unchanged): S = C*nref simulations, output rows [S*my], input
+ * rows [S*nu].  A NULL array of params takes the scenario's own bound: du_min, du_max, u_min and u_max of its
+ * descriptor (an NMPC scenario has u_min and u_max only), y_min and y_max of an mdband scenario; whatever the
+ * scenario does not hold is -inf / +inf.  Every record is bitwise independent of the chunk size.
+ * MPCT_EINVAL, in this order and before any device is touched: s NULL; params NULL; open_loop set; a
+ * trajectory pointer in res; then everything mpct_eval_batch rejects; then the checks of
+ * mpct_limit_indices_device from t0 on, the bounds as resolved.  C = 0 is MPCT_OK and writes nothing.  Without
+ * a device: MPCT_EDEVICE with a message. */
+int32_t mpct_eval_limit_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
+                                const double* lambda, int32_t nref, const double* r, const double* v,
+                                const mpct_opts* opts, const mpct_limit_params* params, mpct_result* res,
+                                const mpct_limit_result* out);
+
+/* Same, all pointers DEVICE pointers (res's and out's included; params and its arrays HOST), enqueued on
+ * `stream` (NULL = default stream) and NOT synchronised: the contract of mpct_eval_indices_device, whose
+ * scratch and stream-ordering rule it shares. */
+int32_t mpct_eval_limit_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                       const double* delta, const double* lambda, int32_t nref, const double* r,
+                                       const double* v, const mpct_opts* opts, const mpct_limit_params* params,
+                                       mpct_result* res, const mpct_limit_result* out, void* stream);
+
+/* Score C candidates x D = nref draws and return, per candidate, the statistics over the draws of the
+ * selected limit indices: the arguments and semantics of mpct_eval_robust_indices with mpct_limit_params in
+ * place of mpct_index_params (a NULL array: the scenario's own bound, as in mpct_eval_limit_indices) and
+ * `fields` drawn from MPCT_LX_VIOL .. MPCT_LX_DU_MARGIN.  The int32 fields enter the statistics as
+ * MPCT_STAT_I32, the others as MPCT_STAT_F64; an infinite margin (no bound) is a draw without a value, by the
+ * statistics' own rule.  Per chunk: the closed loops with trajectories, limit_indices_kernel for the selected
+ * fields only, the classify kernel, the statistics per field and the base record.
+ * Errors, in this order and before any device is touched: those of mpct_eval_robust_indices up to and
+ * including everything mpct_eval_batch rejects; then t0, the channel cap (MPCT_ERANGE), the tolerances and the
+ * resolved bounds as in mpct_limit_indices_device; then MPCT_ERANGE for nref > MPCT_TAIL_MAX_DRAWS, and for
+ * C*nref*my or C*nref*nu > MPCT_INDEX_MAX_ROWS.  C = 0 is MPCT_OK and writes nothing. */
+int32_t mpct_eval_robust_limit_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                       const double* delta, const double* lambda, int32_t nref, const double* r,
+                                       const double* v, double j_bound, const mpct_opts* opts,
+                                       const mpct_limit_params* params, int32_t nsel, const int32_t* fields,
+                                       int32_t nlev, const double* levels, mpct_robust_result* base,
+                                       const mpct_draw_stats_result* out);
+
+/* Same, all pointers DEVICE pointers except params with its arrays, fields and levels; enqueued on `stream`
+ * and NOT synchronised: the contract of mpct_eval_robust_indices_device. */
+int32_t mpct_eval_robust_limit_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                              const double* delta, const double* lambda, int32_t nref,
+                                              const double* r, const double* v, double j_bound,
+                                              const mpct_opts* opts, const mpct_limit_params* params, int32_t nsel,
+                                              const int32_t* fields, int32_t nlev, const double* levels,
+                                              mpct_robust_result* base, const mpct_draw_stats_result* out,
+                                              void* stream);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,12 @@
  *                                                    with n, mean, lo, lo_draw, hi, hi_draw (C x m) and levels
  *                                                    (1 x nlev), quantile, cvar, q_draw (C x m x nlev; [] without
  *                                                    levels); the draws are the library's 0-based k, -1: none
+ *   L = mpct_mex('limit_indices', y, u, params)      limit indices of stored trajectories (mpct_limit_indices): band
+ *                                                    violation per output, saturation and rate-limit use per input
+ *   L = mpct_mex('eval_limit_indices', h, N2, Nu, delta, lambda, r, v, params)
+ *                                                    the same for a scored batch, bounds of the scenario by default
+ *   T = mpct_mex('eval_robust_limit_indices', h, N2, Nu, delta, lambda, r, v, params)
+ *                                                    their statistics over the D pages of r
  *   T = mpct_mex('eval_robust_indices', h, N2, Nu, delta, lambda, r, v, params)
  *                                                    statistics of the performance indices over the D pages of r
  *                                                    (mpct_eval_robust_indices).  params (optional struct): fields
@@ -958,6 +964,140 @@ static void cmd_eval_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = R;
 }
 
+/* ---- limit indices (mpct_limit_indices, mpct_eval_limit_indices; include/mpct.h) */
+static const char* const kLimitNames[13] = {"viol", "viol2", "vmax", "t_vmax", "n_out", "t_in", "y_margin",
+                                            "n_lo", "n_hi", "n_rate", "sat_run", "u_margin", "du_margin"};
+static const char* const kLimitBounds[6] = {"y_lo", "y_hi", "u_lo", "u_hi", "du_lo", "du_hi"};
+static const int kLimitIsInt[13] = {0, 0, 0, 1, 1, 1, 0, 1, 1, 1, 1, 0, 0};
+
+/* params struct (all fields optional): t0 (0-based first sample, default 0), out_tol (0), sat_tol (0), device, and
+ * the bounds y_lo, y_hi (my values), u_lo, u_hi, du_lo, du_hi (nu values); an absent or empty bound stays NULL: no
+ * bound in 'limit_indices', the scenario's own in the scoring commands */
+static mpct_limit_params read_limit_params(const mxArray* o, double* device) {
+  mpct_limit_params p;
+  memset(&p, 0, sizeof p);
+  *device = -1.0;
+  if (!o || mxIsEmpty(o)) return p;
+  if (!mxIsStruct(o)) mexErrMsgIdAndTxt("mpct:arg", "params must be a struct (t0, out_tol, sat_tol, device, y_lo .. du_hi)");
+  const double t0 = fscalar(o, "t0", 0.0);
+  *device = fscalar(o, "device", -1.0);
+  if (t0 != floor(t0) || fabs(t0) > 2147483647.0) mexErrMsgIdAndTxt("mpct:arg", "'t0' must be an integer");
+  if (*device != floor(*device) || fabs(*device) > 1e6) mexErrMsgIdAndTxt("mpct:arg", "'device' must be an integer");
+  p.t0 = (int32_t)t0;
+  p.out_tol = fscalar(o, "out_tol", 0.0);
+  p.sat_tol = fscalar(o, "sat_tol", 0.0);
+  const double** dst[6] = {&p.y_lo, &p.y_hi, &p.u_lo, &p.u_hi, &p.du_lo, &p.du_hi};
+  for (int k = 0; k < 6; ++k) {
+    const mxArray* a = mxGetField(o, 0, kLimitBounds[k]);
+    if (a && !mxIsEmpty(a)) *dst[k] = doubles(a, -1, kLimitBounds[k]);
+  }
+  return p;
+}
+
+/* every bound that was given holds one value per channel: the library reads my / nu of them */
+static void check_limit_lengths(const mpct_limit_params* p, const mxArray* o, int my, int nu) {
+  const double* const given[6] = {p->y_lo, p->y_hi, p->u_lo, p->u_hi, p->du_lo, p->du_hi};
+  for (int k = 0; k < 6; ++k)
+    if (given[k] && (long)mxGetNumberOfElements(mxGetField(o, 0, kLimitBounds[k])) != (k < 2 ? my : nu))
+      mexErrMsgIdAndTxt("mpct:arg", "'%s' must hold %d values, one per channel", kLimitBounds[k], k < 2 ? my : nu);
+}
+
+/* the buffers of the record: output-row fields [S*my] when with_y, input-row fields [S*nu] when with_u */
+static mpct_limit_result limit_buffers(long S, int my, int nu, int with_y, int with_u) {
+  mpct_limit_result r;
+  memset(&r, 0, sizeof r);
+  void** slot[13] = {(void**)&r.viol, (void**)&r.viol2, (void**)&r.vmax,   (void**)&r.t_vmax,  (void**)&r.n_out,
+                     (void**)&r.t_in, (void**)&r.y_margin, (void**)&r.n_lo, (void**)&r.n_hi,   (void**)&r.n_rate,
+                     (void**)&r.sat_run, (void**)&r.u_margin, (void**)&r.du_margin};
+  for (int k = 0; k < 13; ++k)
+    if (k < 7 ? with_y : with_u)
+      *slot[k] = mxCalloc((size_t)(S * (k < 7 ? my : nu) + 1), kLimitIsInt[k] ? sizeof(int32_t) : sizeof(double));
+  return r;
+}
+
+/* the thirteen fields into struct R: S x my / S x nu, [] for a group that was not computed */
+static void set_limit_fields(mxArray* R, const mpct_limit_result* r, long S, int my, int nu) {
+  const void* v[13] = {r->viol, r->viol2, r->vmax,   r->t_vmax,  r->n_out,    r->t_in,     r->y_margin,
+                       r->n_lo, r->n_hi,  r->n_rate, r->sat_run, r->u_margin, r->du_margin};
+  for (int k = 0; k < 13; ++k) {
+    const int w = k < 7 ? my : nu;
+    mxArray* a;
+    if (!v[k]) a = mxCreateDoubleMatrix(0, 0, mxREAL);
+    else if (kLimitIsInt[k]) a = out_int_rows((const int32_t*)v[k], S, w);
+    else a = out_rows((const double*)v[k], S, w);
+    mxSetField(R, 0, kLimitNames[k], a);
+  }
+}
+
+/* L = mpct_mex('limit_indices', y, u [, params]): y my x nit x S, u nu x nit x S (the layouts 'eval' returns); y or u
+ * may be [] (its fields then come back []).  t0, t_vmax and t_in are the library's 0-based sample indices */
+static void cmd_limit_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 3 || nrhs > 4) mexErrMsgIdAndTxt("mpct:arg", "usage: L = mpct_mex('limit_indices', y, u [, params])");
+  int my, nity, nu, nitu;
+  long Sy, Su;
+  signal_dims(prhs[1], "y", &my, &nity, &Sy);
+  signal_dims(prhs[2], "u", &nu, &nitu, &Su);
+  const int with_y = Sy > 0, with_u = Su > 0;
+  if (!with_y && !with_u) mexErrMsgIdAndTxt("mpct:arg", "'y' and 'u' are both empty");
+  if (with_y && with_u && (Sy != Su || nity != nitu)) mexErrMsgIdAndTxt("mpct:arg", "'y' and 'u' must agree on nit and S");
+  const long S = with_y ? Sy : Su;
+  const int nit = with_y ? nity : nitu;
+  if (S > 2147483647L) mexErrMsgIdAndTxt("mpct:arg", "too many pages");
+  const mxArray* po = nrhs > 3 && !mxIsEmpty(prhs[3]) ? prhs[3] : NULL;
+  double device;
+  const mpct_limit_params p = read_limit_params(po, &device);
+  check_limit_lengths(&p, po, my, nu);
+  int pg = 0;
+  double* y = with_y ? signals(prhs[1], my, nit, &pg, "y") : NULL;
+  pg = 0;
+  double* u = with_u ? signals(prhs[2], nu, nit, &pg, "u") : NULL;
+  const mpct_limit_result res = limit_buffers(S, my, nu, with_y, with_u);
+  if (mpct_limit_indices(y, u, S, my, nu, nit, &p, (int32_t)device, &res) != MPCT_OK) lib_error("mpct:limit_indices");
+  mxArray* R = mxCreateStructMatrix(1, 1, 13, (const char**)kLimitNames);
+  set_limit_fields(R, &res, S, my, nu);
+  plhs[0] = R;
+}
+
+/* L = mpct_mex('eval_limit_indices', h, N2, Nu, delta, lambda, r [, v, params]): the thirteen fields (S x my, S x nu,
+ * simulation s = (c-1)*nref + k) plus J1, j22 (S x my), status and iters (S x 1) of the same launch */
+static void cmd_eval_limit_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 7 || nrhs > 9)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: L = mpct_mex('eval_limit_indices', h, N2, Nu, delta, lambda, r [, v, params])");
+  const batch_args b = read_batch(nrhs, prhs, 2);
+  const mxArray* po = nrhs > 8 && !mxIsEmpty(prhs[8]) ? prhs[8] : NULL;
+  double device;
+  const mpct_limit_params p = read_limit_params(po, &device);
+  mpct_opts o = read_opts(NULL);
+  o.device = (int32_t)device;
+  const long C = b.C, S = C * b.nref;
+  const int my = b.my, nu = b.nu;
+  check_limit_lengths(&p, po, my, nu);
+  const mpct_limit_result res = limit_buffers(S, my, nu, 1, 1);
+  mpct_result br;
+  memset(&br, 0, sizeof br);
+  br.J1 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
+  br.j22 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
+  br.status = (int32_t*)mxCalloc((size_t)(S + 1), sizeof(int32_t));
+  br.qp_iters = (int64_t*)mxCalloc((size_t)(S + 1), sizeof(int64_t));
+  if (mpct_eval_limit_indices(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, &o, &p, &br, &res) != MPCT_OK)
+    lib_error("mpct:eval_limit_indices");
+  const char* names[17];
+  for (int k = 0; k < 13; ++k) names[k] = kLimitNames[k];
+  names[13] = "J1";
+  names[14] = "j22";
+  names[15] = "status";
+  names[16] = "iters";
+  mxArray* R = mxCreateStructMatrix(1, 1, 17, names);
+  set_limit_fields(R, &res, S, my, nu);
+  mxSetField(R, 0, "J1", out_rows(br.J1, S, my));
+  mxSetField(R, 0, "j22", out_rows(br.j22, S, my));
+  mxSetField(R, 0, "status", out_int_rows(br.status, S, 1));
+  mxArray* it = mxCreateDoubleMatrix((mwSize)S, 1, mxREAL);
+  for (long k = 0; k < S; ++k) mxGetPr(it)[k] = (double)br.qp_iters[k];
+  mxSetField(R, 0, "iters", it);
+  plhs[0] = R;
+}
+
 /* ---- statistics over the draws (mpct_draw_stats, mpct_eval_robust_indices; include/mpct.h) */
 static const char* const kStatNames[10] = {"n", "mean", "lo", "lo_draw", "hi", "hi_draw", "levels", "quantile", "cvar", "q_draw"};
 
@@ -1064,13 +1204,21 @@ static void cmd_draw_stats(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   plhs[0] = T;
 }
 
-/* T = mpct_mex('eval_robust_indices', h, N2, Nu, delta, lambda, r [, v, params]) */
-static void cmd_eval_robust_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+/* T = mpct_mex('eval_robust_indices', h, N2, Nu, delta, lambda, r [, v, params]), and with limits = 1
+ * T = mpct_mex('eval_robust_limit_indices', ..): the same table for the limit indices (fields: MPCT_LX_* ids) */
+static void cmd_eval_robust_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[], int limits) {
   if (nrhs < 7 || nrhs > 9)
-    mexErrMsgIdAndTxt("mpct:arg", "usage: T = mpct_mex('eval_robust_indices', h, N2, Nu, delta, lambda, r [, v, params])");
+    mexErrMsgIdAndTxt("mpct:arg", "usage: T = mpct_mex('eval_robust_%sindices', h, N2, Nu, delta, lambda, r [, v, params])",
+                      limits ? "limit_" : "");
   const mxArray* po = nrhs > 8 && !mxIsEmpty(prhs[8]) ? prhs[8] : NULL;
+  const int ny_fields = limits ? 7 : 8; /* the ids below it are output-row fields */
   double device;
-  const mpct_index_params p = read_index_params(po, &device);
+  mpct_index_params p;
+  mpct_limit_params lp;
+  memset(&p, 0, sizeof p);
+  memset(&lp, 0, sizeof lp);
+  if (limits) lp = read_limit_params(po, &device);
+  else p = read_index_params(po, &device);
   int32_t all[13], *fields = all;
   long nsel = 13, nlev = 0;
   double* levels = NULL;
@@ -1092,7 +1240,7 @@ static void cmd_eval_robust_indices(mxArray* plhs[], int nrhs, const mxArray* pr
   const long C = b.C;
   const int my = b.my, nu = b.nu;
   int W = 0; /* .. but an id out of range must not size anything: it counts as one column */
-  for (long q = 0; q < nsel; ++q) W += (fields[q] >= 0 && fields[q] <= 12) ? (fields[q] < 8 ? my : nu) : 1;
+  for (long q = 0; q < nsel; ++q) W += (fields[q] >= 0 && fields[q] <= 12) ? (fields[q] < ny_fields ? my : nu) : 1;
   const mpct_draw_stats_result res = stats_buffers(C * W, nlev);
   mpct_robust_result base;
   memset(&base, 0, sizeof base);
@@ -1101,8 +1249,13 @@ static void cmd_eval_robust_indices(mxArray* plhs[], int nrhs, const mxArray* pr
   base.n_failed = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
   base.worst_draw = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
   base.status = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
-  if (mpct_eval_robust_indices(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, &p, (int32_t)nsel, fields,
-                               (int32_t)nlev, levels, &base, &res) != MPCT_OK)
+  if (limits) {
+    check_limit_lengths(&lp, po, my, nu);
+    if (mpct_eval_robust_limit_indices(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, &lp, (int32_t)nsel,
+                                       fields, (int32_t)nlev, levels, &base, &res) != MPCT_OK)
+      lib_error("mpct:eval_robust_limit_indices");
+  } else if (mpct_eval_robust_indices(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, &p, (int32_t)nsel,
+                                      fields, (int32_t)nlev, levels, &base, &res) != MPCT_OK)
     lib_error("mpct:eval_robust_indices");
   const char* names[17];
   names[0] = "field";
@@ -1118,7 +1271,7 @@ static void cmd_eval_robust_indices(mxArray* plhs[], int nrhs, const mxArray* pr
   mxArray* ca = mxCreateDoubleMatrix(1, (mwSize)W, mxREAL);
   int col = 0;
   for (long q = 0; q < nsel; ++q)
-    for (int i = 0; i < (fields[q] < 8 ? my : nu); ++i, ++col) {
+    for (int i = 0; i < (fields[q] < ny_fields ? my : nu); ++i, ++col) {
       mxGetPr(fa)[col] = fields[q];
       mxGetPr(ca)[col] = i + 1;
     }
@@ -1172,7 +1325,13 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   } else if (!strcmp(cmd, "draw_stats")) {
     cmd_draw_stats(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "eval_robust_indices")) {
-    cmd_eval_robust_indices(plhs, nrhs, prhs);
+    cmd_eval_robust_indices(plhs, nrhs, prhs, 0);
+  } else if (!strcmp(cmd, "limit_indices")) {
+    cmd_limit_indices(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "eval_limit_indices")) {
+    cmd_eval_limit_indices(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "eval_robust_limit_indices")) {
+    cmd_eval_robust_indices(plhs, nrhs, prhs, 1);
   } else if (!strcmp(cmd, "instance")) {
     if (nrhs < 2) mexErrMsgIdAndTxt("mpct:arg", "usage: name = mpct_mex('instance', h [, opts])");
     mpct_scenario* s = handle(prhs[1]);

@@ -21,6 +21,7 @@
 #include "hypervolume.h"
 #include "hypervolume_exact.h"
 #include "traj_indices.h"
+#include "limit_indices.h"
 #include "draw_stats.h"
 
 namespace mpct {
@@ -1509,9 +1510,11 @@ static int check_eval_indices(mpct_scenario* s, const Batch& b, const mpct_opts*
 }
 
 // enqueue one batch with device pointers on `stream` (ctx's device is current): chunks of whole
-// candidates through launch_batch into the trajectory scratch, each followed by the index kernel
-static int launch_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, const mpct_opts* opts, const mpct_index_params* p,
-                          const mpct_result* res, const mpct_index_result* out, hipStream_t stream) {
+// candidates through launch_batch into the trajectory scratch, each followed by the reduction kernel
+// records(y, u, n, s0): the chunk's trajectories, its n candidates, its first simulation
+template <class Records>
+static int walk_chunks(mpct_scenario* s, DevCtx* cx, const Batch& b, const mpct_opts* opts, const mpct_result* res,
+                       hipStream_t stream, Records records) {
   if (b.C == 0) return MPCT_OK;
   const int my = s->my, nu = s->nu, nit = s->nit;
   const int32_t nref = b.nref;
@@ -1520,7 +1523,6 @@ static int launch_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, const mp
   int rc = cx->index.acquire((size_t)cc * traj_bytes(nref, my, nu, nit), stream, "trajectory scratch", &scr);
   if (rc) return rc;
   const mpct_opts o = traj_opts(opts);
-  const IndexOut io = index_out(out);
   for (int64_t c0 = 0; c0 < b.C && rc == MPCT_OK; c0 += cc) {
     const int64_t n = std::min(cc, b.C - c0), s0 = c0 * nref;
     // the caller's cost fields from this chunk's first simulation on (its trajectory pointers are NULL)
@@ -1529,11 +1531,18 @@ static int launch_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, const mp
     per_chunk.y = reinterpret_cast<double*>(scr);
     per_chunk.u = per_chunk.y + (size_t)n * nref * my * nit;
     rc = launch_batch(s, cx, b.sub(c0, n, my, nu), &o, &per_chunk, stream);
-    if (rc == MPCT_OK)
-      rc = index_launch(per_chunk.y, per_chunk.u, b.r, n * nref, nref, my, nu, nit, p, io.from(s0, my, nu), stream);
+    if (rc == MPCT_OK) rc = records(per_chunk.y, per_chunk.u, n, s0);
   }
   cx->index.mark(stream);
   return rc;
+}
+
+static int launch_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, const mpct_opts* opts, const mpct_index_params* p,
+                          const mpct_result* res, const mpct_index_result* out, hipStream_t stream) {
+  const IndexOut io = index_out(out);
+  return walk_chunks(s, cx, b, opts, res, stream, [&](const double* y, const double* u, int64_t n, int64_t s0) {
+    return index_launch(y, u, b.r, n * b.nref, b.nref, s->my, s->nu, s->nit, p, io.from(s0, s->my, s->nu), stream);
+  });
 }
 
 extern "C" int32_t mpct_eval_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
@@ -1711,9 +1720,16 @@ static int check_robust_indices(mpct_scenario* s, const Batch& b, double j_bound
 // enqueue one batch with device pointers on `stream` (ctx's device is current).  Per chunk of whole
 // candidates: the closed loops with trajectories, J1 and status into the context's index scratch, the
 // selected index records, alive[c][k], then the statistics of each selected field and the base record
-static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
-                                 const mpct_index_params* p, int32_t nsel, const int32_t* fields, int32_t nlev,
-                                 const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream) {
+// (shared by the performance and the limit indices: ny_fields of the thirteen field ids are output-row
+// fields, int_mask has the bits of the int32 ones, records(rec, y, u, S) enqueues the chunk's reduction kernel
+// with rec[id] the selected fields' device records)
+template <class Records>
+static int walk_robust_chunks(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
+                              int ny_fields, unsigned int_mask, int32_t nsel, const int32_t* fields, int32_t nlev,
+                              const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream,
+                              Records records) {
+  auto field_width = [&](const mpct_scenario* sc, int id) { return id < ny_fields ? sc->my : sc->nu; };
+  auto field_is_int = [&](int id) { return (int_mask >> id & 1u) != 0; };
   if (b.C == 0) return MPCT_OK;
   const int my = s->my, nu = s->nu, nit = s->nit;
   const int64_t C = b.C;
@@ -1737,9 +1753,6 @@ static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, d
   const mpct_opts o = traj_opts(opts);
   void* rec[13] = {nullptr};
   for (int q = 0; q < nsel; ++q) rec[fields[q]] = scr + o_f[q];
-  const IndexOut io{(double*)rec[0], (double*)rec[1], (double*)rec[2], (double*)rec[3],  (int*)rec[4],
-                    (double*)rec[5], (double*)rec[6], (int*)rec[7],    (double*)rec[8],  (double*)rec[9],
-                    (double*)rec[10], (double*)rec[11], (double*)rec[12]};
   const bool any_base = base.mean || base.worst || base.n_failed || base.worst_draw || base.status;
   std::string err;
   for (int64_t c0 = 0; c0 < C && rc == MPCT_OK; c0 += cc) {
@@ -1751,7 +1764,7 @@ static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, d
     per_chunk.u = per_chunk.y + (size_t)n * nref * my * nit;
     int32_t* alive = reinterpret_cast<int32_t*>(scr + o_al);
     rc = launch_batch(s, cx, b.sub(c0, n, my, nu), &o, &per_chunk, stream);
-    if (rc == MPCT_OK) rc = index_launch(per_chunk.y, per_chunk.u, b.r, n * nref, nref, my, nu, nit, p, io, stream);
+    if (rc == MPCT_OK) rc = records(rec, per_chunk.y, per_chunk.u, n * nref);
     if (rc != MPCT_OK) break;
     int lrc = launch_draw_alive(n, nref, my, bound, per_chunk.J1, per_chunk.status, alive, stream, &err);
     if (lrc == 0 && any_base) {
@@ -1778,6 +1791,20 @@ static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, d
   return rc;
 }
 
+static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
+                                 const mpct_index_params* p, int32_t nsel, const int32_t* fields, int32_t nlev,
+                                 const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream) {
+  const unsigned ints = 1u << MPCT_IX_T_EMAX | 1u << MPCT_IX_SETTLE;
+  return walk_robust_chunks(
+      s, cx, b, j_bound, opts, 8, ints, nsel, fields, nlev, levels, base, out, stream,
+      [&](void* const* rec, const double* y, const double* u, int64_t S) {
+        const IndexOut io{(double*)rec[0], (double*)rec[1], (double*)rec[2], (double*)rec[3],  (int*)rec[4],
+                          (double*)rec[5], (double*)rec[6], (int*)rec[7],    (double*)rec[8],  (double*)rec[9],
+                          (double*)rec[10], (double*)rec[11], (double*)rec[12]};
+        return index_launch(y, u, b.r, S, b.nref, s->my, s->nu, s->nit, p, io, stream);
+      });
+}
+
 extern "C" int32_t mpct_eval_robust_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
                                                    const double* delta, const double* lambda, int32_t nref,
                                                    const double* r, const double* v, double j_bound,
@@ -1797,6 +1824,32 @@ extern "C" int32_t mpct_eval_robust_indices_device(mpct_scenario* s, int64_t C, 
                                out ? stats_out(out) : DrawStatsOut{}, static_cast<hipStream_t>(stream));
 }
 
+// host buffers in, the statistics of W columns out on the context's own stream, staged as eval_host does:
+// every field of base and out lives on the device only where it is asked for (the per-level ones only with
+// nlev >= 1).  launch(hs, ro, dv) enqueues the walk on hs.st with the device-side batch hs.dev
+template <class Launch>
+static int robust_stats_host(mpct_scenario* s, DevCtx* cx, const Batch& b, size_t W, int32_t nlev,
+                             const mpct_robust_result* base, const mpct_draw_stats_result* out, Launch launch) {
+  const size_t C = (size_t)b.C, cm = C * s->my * 8, cols = C * W, lev = cols * (size_t)nlev;
+  const mpct_robust_result hb = base ? *base : mpct_robust_result{};
+  const mpct_draw_stats_result ho = out ? *out : mpct_draw_stats_result{};
+  HostStage hs(s, cx, b.C);
+  const int s_mean = hs.want(hb.mean, cm), s_worst = hs.want(hb.worst, cm), s_nf = hs.want(hb.n_failed, C * 4),
+            s_wd = hs.want(hb.worst_draw, C * 4), s_st = hs.want(hb.status, C * 4);
+  const int s_n = hs.want(ho.n, cols * 4), s_mn = hs.want(ho.mean, cols * 8), s_lo = hs.want(ho.lo, cols * 8),
+            s_ld = hs.want(ho.lo_draw, cols * 4), s_hi = hs.want(ho.hi, cols * 8), s_hd = hs.want(ho.hi_draw, cols * 4),
+            s_q = hs.want(ho.quantile, lev * 8), s_cv = hs.want(ho.cvar, lev * 8), s_qd = hs.want(ho.q_draw, lev * 4);
+  int rc = hs.upload(s, b);
+  if (rc) return rc;
+  const RobustOut ro{hs.at<double>(s_mean), hs.at<double>(s_worst), hs.at<int32_t>(s_nf), hs.at<int32_t>(s_wd),
+                     hs.at<int32_t>(s_st)};
+  const DrawStatsOut dv{hs.at<int32_t>(s_n),  hs.at<double>(s_mn), hs.at<double>(s_lo), hs.at<int32_t>(s_ld), hs.at<double>(s_hi),
+                        hs.at<int32_t>(s_hd), hs.at<double>(s_q),  hs.at<double>(s_cv), hs.at<int32_t>(s_qd)};
+  rc = launch(hs, ro, dv);
+  if (rc) return hs.abandon(rc);
+  return hs.finish();
+}
+
 extern "C" int32_t mpct_eval_robust_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
                                             const double* delta, const double* lambda, int32_t nref, const double* r,
                                             const double* v, double j_bound, const mpct_opts* opts,
@@ -1810,28 +1863,303 @@ extern "C" int32_t mpct_eval_robust_indices(mpct_scenario* s, int64_t C, const i
   DevCtx* cx = nullptr;
   rc = ctx_for(s, opts, &cx);
   if (rc) return rc;
-  // host buffers in, the records out on the context's own stream, staged as eval_host does: every field of
-  // base and out lives on the device only where it is asked for (the per-level ones only with nlev >= 1)
   size_t W = 0;
   for (int q = 0; q < nsel; ++q) W += field_width(s, fields[q]);
-  const size_t cm = (size_t)C * s->my * 8, cols = (size_t)C * W, lev = cols * (size_t)nlev;
-  const mpct_robust_result hb = base ? *base : mpct_robust_result{};
-  const mpct_draw_stats_result ho = out ? *out : mpct_draw_stats_result{};
+  return robust_stats_host(s, cx, b, W, nlev, base, out, [&](HostStage& hs, const RobustOut& ro, const DrawStatsOut& dv) {
+    return launch_robust_indices(s, cx, hs.dev, j_bound, opts, params, nsel, fields, nlev, levels, ro, dv, hs.st);
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// limit indices per simulation and their statistics over the draws (limit_indices.hip; include/mpct.h,
+// DESIGN.md §20)
+
+static LimitOut limit_out(const mpct_limit_result* o) {
+  return LimitOut{o->viol, o->viol2, o->vmax,   o->t_vmax,  o->n_out,    o->t_in,     o->y_margin,
+                  o->n_lo, o->n_hi,  o->n_rate, o->sat_run, o->u_margin, o->du_margin};
+}
+// width of limit field id in a scenario's records, and the bits of the int32 fields
+static int limit_width(const mpct_scenario* s, int id) { return id < MPCT_LX_N_LO ? s->my : s->nu; }
+constexpr unsigned kLimitInts = 1u << MPCT_LX_T_VMAX | 1u << MPCT_LX_N_OUT | 1u << MPCT_LX_T_IN | 1u << MPCT_LX_N_LO |
+                                1u << MPCT_LX_N_HI | 1u << MPCT_LX_N_RATE | 1u << MPCT_LX_SAT_RUN;
+
+// the checks on the parameters from t0 on, in the header's order, and the kernel's by-value parameters: the
+// caller's array where it gave one, else the scenario's own bound (s may be NULL), else no bound
+static int limit_resolve(const mpct_scenario* s, int32_t my, int32_t nu, int32_t nit, const mpct_limit_params* p,
+                         LimitParams* lp) {
+  if (p->t0 < 0 || p->t0 >= nit) return fail(MPCT_EINVAL, "t0 must be 0 .. nit-1");
+  if (my > MPCT_LIMIT_MAX_CH || nu > MPCT_LIMIT_MAX_CH)
+    return fail(MPCT_ERANGE, "my or nu exceeds MPCT_LIMIT_MAX_CH (32): the bounds travel in the kernel argument");
+  if (!(p->out_tol >= 0.0 && p->out_tol <= 1.7976931348623157e308 && p->sat_tol >= 0.0 &&
+        p->sat_tol <= 1.7976931348623157e308))
+    return fail(MPCT_EINVAL, "out_tol and sat_tol must be finite and >= 0, not NaN");
+  const double *sy_lo = nullptr, *sy_hi = nullptr, *su_lo = nullptr, *su_hi = nullptr, *sd_lo = nullptr, *sd_hi = nullptr;
+  if (s && s->nmpc) {  // nm: parameters | x0[3] | u0[nu] | u_min[nu] | u_max[nu] | ..
+    su_lo = s->nm.data() + NM_NPAR + 3 + nu;
+    su_hi = su_lo + nu;
+  } else if (s) {
+    sd_lo = s->bnd.data(), sd_hi = sd_lo + nu, su_lo = sd_lo + 2 * nu, su_hi = sd_lo + 3 * nu;
+    if (s->mdband) sy_lo = s->obnd.data(), sy_hi = sy_lo + my;
+  }
+  *lp = LimitParams{};
+  lp->t0 = p->t0, lp->out_tol = p->out_tol, lp->sat_tol = p->sat_tol;
+  auto fill = [](double* dst, const double* own, const double* scen, int n, double none) {
+    for (int c = 0; c < kLimitMaxCh; ++c) dst[c] = c >= n ? none : (own ? own[c] : (scen ? scen[c] : none));
+  };
+  fill(lp->y_lo, p->y_lo, sy_lo, my, -INFINITY), fill(lp->y_hi, p->y_hi, sy_hi, my, INFINITY);
+  fill(lp->u_lo, p->u_lo, su_lo, nu, -INFINITY), fill(lp->u_hi, p->u_hi, su_hi, nu, INFINITY);
+  fill(lp->du_lo, p->du_lo, sd_lo, nu, -INFINITY), fill(lp->du_hi, p->du_hi, sd_hi, nu, INFINITY);
+  auto ok = [](const double* lo, const double* hi, int n) {
+    for (int c = 0; c < n; ++c)
+      if (!(lo[c] <= hi[c]) || lo[c] == INFINITY || hi[c] == -INFINITY) return false;  // !(<=) catches NaN
+    return true;
+  };
+  if (!ok(lp->y_lo, lp->y_hi, my) || !ok(lp->u_lo, lp->u_hi, nu) || !ok(lp->du_lo, lp->du_hi, nu))
+    return fail(MPCT_EINVAL, "bad bound: NaN, a lower bound above its upper bound, lower = +inf or upper = -inf");
+  return MPCT_OK;
+}
+
+static int limit_check_out(int64_t S, int32_t my, int32_t nu, const mpct_limit_result* out, bool have_y, bool have_u) {
+  if (!out) return fail(MPCT_EINVAL, "no output pointer in mpct_limit_result");
+  const LimitOut lo = limit_out(out);
+  if (!lo.any_y() && !lo.any_u()) return fail(MPCT_EINVAL, "no output pointer in mpct_limit_result");
+  if (lo.any_y() && (my < 1 || (S > 0 && !have_y)))
+    return fail(MPCT_EINVAL, "an output-row field needs my >= 1 and the trajectory y");
+  if (lo.any_u() && (nu < 1 || (S > 0 && !have_u)))
+    return fail(MPCT_EINVAL, "an input-row field needs nu >= 1 and the trajectory u");
+  if (S * (int64_t)my > kIndexMaxRows || S * (int64_t)nu > kIndexMaxRows)
+    return fail(MPCT_ERANGE, "S*my or S*nu exceeds MPCT_INDEX_MAX_ROWS");
+  return MPCT_OK;
+}
+
+static int limit_check(const double* y, const double* u, int64_t S, int32_t my, int32_t nu, int32_t nit,
+                       const mpct_limit_params* p, const mpct_limit_result* out, LimitParams* lp) {
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (S < 0 || my < 0 || nu < 0 || nit < 1) return fail(MPCT_EINVAL, "bad shape: S < 0, my < 0, nu < 0 or nit < 1");
+  const int rc = limit_resolve(nullptr, my, nu, nit, p, lp);
+  if (rc) return rc;
+  return limit_check_out(S, my, nu, out, y != nullptr, u != nullptr);
+}
+
+static int32_t limit_launch(const double* y, const double* u, int64_t S, int32_t my, int32_t nu, int32_t nit,
+                            const LimitParams& lp, const LimitOut& lo, hipStream_t stream) {
+  if (S == 0) return MPCT_OK;
+  std::string err;
+  const int rc = launch_limit_indices(y, u, S, my, nu, nit, lp, lo, stream, &err);
+  return rc ? fail(MPCT_EDEVICE, err) : MPCT_OK;
+}
+
+extern "C" int32_t mpct_limit_indices_device(const double* y, const double* u, int64_t S, int32_t my, int32_t nu,
+                                             int32_t nit, const mpct_limit_params* params, const mpct_limit_result* out,
+                                             void* stream) {
+  LimitParams lp;
+  const int rc = limit_check(y, u, S, my, nu, nit, params, out, &lp);
+  if (rc) return rc;
+  return limit_launch(y, u, S, my, nu, nit, lp, limit_out(out), static_cast<hipStream_t>(stream));
+}
+
+// the thirteen fields of an mpct_limit_result in the struct's order, each with its host pointer, its width
+// per simulation and its element size
+template <class F>
+static void each_limit_field(const mpct_limit_result& o, int my, int nu, F f) {
+  void* const host[13] = {o.viol, o.viol2, o.vmax,   o.t_vmax,  o.n_out,    o.t_in,     o.y_margin,
+                          o.n_lo, o.n_hi,  o.n_rate, o.sat_run, o.u_margin, o.du_margin};
+  for (int id = 0; id < 13; ++id) f(id, host[id], id < MPCT_LX_N_LO ? my : nu, (kLimitInts >> id & 1u) ? 4 : 8);
+}
+// the device-side record from the slots slot0 .. slot0 + 12 of a stage
+template <class Stage>
+static mpct_limit_result limit_slots(const Stage& st, int slot0) {
+  auto dd = [&](int id) { return st.template at<double>(slot0 + id); };
+  auto di = [&](int id) { return st.template at<int32_t>(slot0 + id); };
+  return mpct_limit_result{dd(0), dd(1), dd(2), di(3), di(4), di(5), dd(6), di(7), di(8), di(9), di(10), dd(11), dd(12)};
+}
+
+extern "C" int32_t mpct_limit_indices(const double* y, const double* u, int64_t S, int32_t my, int32_t nu, int32_t nit,
+                                      const mpct_limit_params* params, int32_t device, const mpct_limit_result* out) {
+  LimitParams lp;
+  int rc = limit_check(y, u, S, my, nu, nit, params, out, &lp);
+  if (rc) return rc;
+  if (S == 0) return MPCT_OK;  // nothing to stage
+  const LimitOut ho = limit_out(out);
+  CallStage cs{"mpct_limit_indices", "limit staging", "trajectories", "limit records"};
+  // y travels only behind an output-row field, u only behind an input-row field
+  const int s_y = cs.in(ho.any_y() ? y : nullptr, (size_t)S * my * nit * 8),
+            s_u = cs.in(ho.any_u() ? u : nullptr, (size_t)S * nu * nit * 8);
+  int slot0 = -1;
+  each_limit_field(*out, my, nu, [&](int, void* host, int w, int esz) {
+    const int k = cs.out(host, (size_t)S * w * esz);
+    if (slot0 < 0) slot0 = k;
+  });
+  rc = cs.open(device);
+  if (rc == MPCT_OK) {
+    const mpct_limit_result dv = limit_slots(cs, slot0);
+    rc = limit_launch(cs.at<double>(s_y), cs.at<double>(s_u), S, my, nu, nit, lp, limit_out(&dv), cs.st);
+  }
+  return cs.close(rc);
+}
+
+// the argument checks of the two scoring entries, in the header's order; nothing here touches a device
+static int check_eval_limits(mpct_scenario* s, const Batch& b, const mpct_opts* opts, const mpct_limit_params* p,
+                             const mpct_result* res, const mpct_limit_result* out, LimitParams* lp) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the index entries are closed-loop only: open_loop must be 0");
+  if (res && (res->y || res->u || res->ys || res->uopt))
+    return fail(MPCT_EINVAL, "the trajectory pointers of res must be NULL: the trajectories stay on the device");
+  const mpct_result any{};
+  int rc = check_args(s, b, opts, &any);
+  if (rc) return rc;
+  rc = limit_resolve(s, s->my, s->nu, s->nit, p, lp);
+  if (rc) return rc;
+  return limit_check_out(b.C * b.nref, s->my, s->nu, out, true, true);
+}
+
+static int launch_limits(mpct_scenario* s, DevCtx* cx, const Batch& b, const mpct_opts* opts, const LimitParams& lp,
+                         const mpct_result* res, const mpct_limit_result* out, hipStream_t stream) {
+  const LimitOut lo = limit_out(out);
+  return walk_chunks(s, cx, b, opts, res, stream, [&](const double* y, const double* u, int64_t n, int64_t s0) {
+    return limit_launch(y, u, n * b.nref, s->my, s->nu, s->nit, lp, lo.from(s0, s->my, s->nu), stream);
+  });
+}
+
+extern "C" int32_t mpct_eval_limit_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                  const double* delta, const double* lambda, int32_t nref,
+                                                  const double* r, const double* v, const mpct_opts* opts,
+                                                  const mpct_limit_params* params, mpct_result* res,
+                                                  const mpct_limit_result* out, void* stream) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  LimitParams lp;
+  int rc = check_eval_limits(s, b, opts, params, res, out, &lp);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  return launch_limits(s, cx, b, opts, lp, res, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_eval_limit_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                           const double* delta, const double* lambda, int32_t nref, const double* r,
+                                           const double* v, const mpct_opts* opts, const mpct_limit_params* params,
+                                           mpct_result* res, const mpct_limit_result* out) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  LimitParams lp;
+  int rc = check_eval_limits(s, b, opts, params, res, out, &lp);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  // host buffers in, the records out on the context's own stream, staged as mpct_eval_indices does: slots
+  // 0..9 the fields of `res` (its six cost fields on the device with a `res`, its trajectories never),
+  // 10..22 the limit fields that are asked for
+  const size_t S = (size_t)(C * nref);
   HostStage hs(s, cx, C);
-  const int s_mean = hs.want(hb.mean, cm), s_worst = hs.want(hb.worst, cm), s_nf = hs.want(hb.n_failed, (size_t)C * 4),
-            s_wd = hs.want(hb.worst_draw, (size_t)C * 4), s_st = hs.want(hb.status, (size_t)C * 4);
-  const int s_n = hs.want(ho.n, cols * 4), s_mn = hs.want(ho.mean, cols * 8), s_lo = hs.want(ho.lo, cols * 8),
-            s_ld = hs.want(ho.lo_draw, cols * 4), s_hi = hs.want(ho.hi, cols * 8), s_hd = hs.want(ho.hi_draw, cols * 4),
-            s_q = hs.want(ho.quantile, lev * 8), s_cv = hs.want(ho.cvar, lev * 8), s_qd = hs.want(ho.q_draw, lev * 4);
+  mpct_result hres = res ? *res : mpct_result{};
+  int k = 0;
+  each_field(hres, s->my, s->nu, s->nit, [&](auto* host, int64_t w) {
+    hs.keep(host, S * w * sizeof(*host), res && k < 6);
+    ++k;
+  });
+  each_limit_field(*out, s->my, s->nu, [&](int, void* host, int w, int esz) { hs.want(host, S * w * esz); });
   rc = hs.upload(s, b);
   if (rc) return rc;
-  const RobustOut ro{hs.at<double>(s_mean), hs.at<double>(s_worst), hs.at<int32_t>(s_nf), hs.at<int32_t>(s_wd),
-                     hs.at<int32_t>(s_st)};
-  const DrawStatsOut dv{hs.at<int32_t>(s_n),  hs.at<double>(s_mn), hs.at<double>(s_lo), hs.at<int32_t>(s_ld), hs.at<double>(s_hi),
-                        hs.at<int32_t>(s_hd), hs.at<double>(s_q),  hs.at<double>(s_cv), hs.at<int32_t>(s_qd)};
-  rc = launch_robust_indices(s, cx, hs.dev, j_bound, opts, params, nsel, fields, nlev, levels, ro, dv, hs.st);
+  mpct_result dres{};
+  k = 0;
+  each_field(dres, s->my, s->nu, s->nit, [&](auto*& dev, int64_t) { hs.bind(k++, dev); });
+  const mpct_limit_result dout = limit_slots(hs, 10);
+  rc = launch_limits(s, cx, hs.dev, opts, lp, res ? &dres : nullptr, &dout, hs.st);
   if (rc) return hs.abandon(rc);
   return hs.finish();
+}
+
+// the argument checks of the two robust limit entries, in the header's order; nothing here touches a device
+static int check_robust_limits(mpct_scenario* s, const Batch& b, double j_bound, const mpct_opts* opts,
+                               const mpct_limit_params* p, int32_t nsel, const int32_t* fields, int32_t nlev,
+                               const double* levels, const mpct_robust_result* base, const mpct_draw_stats_result* out,
+                               LimitParams* lp) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the index entries are closed-loop only: open_loop must be 0");
+  if (nsel < 1 || nsel > 13 || !fields) return fail(MPCT_EINVAL, "nsel must be 1 .. 13 with a field list");
+  unsigned seen = 0;
+  for (int q = 0; q < nsel; ++q) {
+    if (fields[q] < MPCT_LX_VIOL || fields[q] > MPCT_LX_DU_MARGIN) return fail(MPCT_EINVAL, "field id out of range");
+    if (seen & (1u << fields[q])) return fail(MPCT_EINVAL, "field id repeated");
+    seen |= 1u << fields[q];
+  }
+  if (b.nref < 1) return fail(MPCT_EINVAL, "nref < 1: the statistics need at least one draw");
+  if (!(j_bound >= 0.0)) return fail(MPCT_EINVAL, "j_bound must be >= 0 (0 = 1e100, +inf allowed), not negative or NaN");
+  int rc = stats_check_levels(nlev, levels);
+  if (rc) return rc;
+  const bool any_base = base && (base->mean || base->worst || base->n_failed || base->worst_draw || base->status);
+  const bool any_out = out && stats_out(out).any();
+  if (!any_base && !any_out) return fail(MPCT_EINVAL, "every output pointer of base and out is NULL");
+  if (base && base->J1) return fail(MPCT_EINVAL, "base->J1 must be NULL: the sample lives per chunk");
+  if (nlev == 0 && out && stats_out(out).any_level()) return fail(MPCT_EINVAL, "quantile, cvar and q_draw need nlev >= 1");
+  const mpct_result any{};
+  rc = check_args(s, b, opts, &any);
+  if (rc) return rc;
+  rc = limit_resolve(s, s->my, s->nu, s->nit, p, lp);
+  if (rc) return rc;
+  if (b.nref > MPCT_TAIL_MAX_DRAWS) return fail(MPCT_ERANGE, "nref > MPCT_TAIL_MAX_DRAWS (4096): the kernel's LDS holds no more draws");
+  if (b.C * b.nref * (int64_t)s->my > kIndexMaxRows || b.C * b.nref * (int64_t)s->nu > kIndexMaxRows)
+    return fail(MPCT_ERANGE, "C*nref*my or C*nref*nu exceeds MPCT_INDEX_MAX_ROWS");
+  return MPCT_OK;
+}
+
+static int launch_robust_limits(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
+                                const LimitParams& lp, int32_t nsel, const int32_t* fields, int32_t nlev,
+                                const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream) {
+  return walk_robust_chunks(
+      s, cx, b, j_bound, opts, MPCT_LX_N_LO, kLimitInts, nsel, fields, nlev, levels, base, out, stream,
+      [&](void* const* rec, const double* y, const double* u, int64_t S) {
+        const LimitOut lo{(double*)rec[0], (double*)rec[1], (double*)rec[2],  (int*)rec[3],     (int*)rec[4],
+                          (int*)rec[5],    (double*)rec[6], (int*)rec[7],     (int*)rec[8],     (int*)rec[9],
+                          (int*)rec[10],   (double*)rec[11], (double*)rec[12]};
+        return limit_launch(y, u, S, s->my, s->nu, s->nit, lp, lo, stream);
+      });
+}
+
+extern "C" int32_t mpct_eval_robust_limit_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                         const double* delta, const double* lambda, int32_t nref,
+                                                         const double* r, const double* v, double j_bound,
+                                                         const mpct_opts* opts, const mpct_limit_params* params,
+                                                         int32_t nsel, const int32_t* fields, int32_t nlev,
+                                                         const double* levels, mpct_robust_result* base,
+                                                         const mpct_draw_stats_result* out, void* stream) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  LimitParams lp;
+  int rc = check_robust_limits(s, b, j_bound, opts, params, nsel, fields, nlev, levels, base, out, &lp);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  const RobustOut ro = base ? RobustOut{base->mean, base->worst, base->n_failed, base->worst_draw, base->status} : RobustOut{};
+  return launch_robust_limits(s, cx, b, j_bound, opts, lp, nsel, fields, nlev, levels, ro,
+                              out ? stats_out(out) : DrawStatsOut{}, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_eval_robust_limit_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                  const double* delta, const double* lambda, int32_t nref,
+                                                  const double* r, const double* v, double j_bound,
+                                                  const mpct_opts* opts, const mpct_limit_params* params, int32_t nsel,
+                                                  const int32_t* fields, int32_t nlev, const double* levels,
+                                                  mpct_robust_result* base, const mpct_draw_stats_result* out) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  LimitParams lp;
+  int rc = check_robust_limits(s, b, j_bound, opts, params, nsel, fields, nlev, levels, base, out, &lp);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  size_t W = 0;
+  for (int q = 0; q < nsel; ++q) W += limit_width(s, fields[q]);
+  return robust_stats_host(s, cx, b, W, nlev, base, out, [&](HostStage& hs, const RobustOut& ro, const DrawStatsOut& dv) {
+    return launch_robust_limits(s, cx, hs.dev, j_bound, opts, lp, nsel, fields, nlev, levels, ro, dv, hs.st);
+  });
 }
 
 static int32_t copy_name(const std::string& nm, char* buf, int32_t cap) {

@@ -118,6 +118,23 @@ class MpctIndexResult(C.Structure):
     _fields_ = [(n, c_int32_p if i else c_double_p) for n, _, i in INDEX_FIELDS]
 
 
+class MpctLimitParams(C.Structure):
+    _fields_ = [("t0", C.c_int32), ("out_tol", C.c_double), ("sat_tol", C.c_double),
+                ("y_lo", c_double_p), ("y_hi", c_double_p), ("u_lo", c_double_p), ("u_hi", c_double_p),
+                ("du_lo", c_double_p), ("du_hi", c_double_p)]
+
+
+# the fields of mpct_limit_result in the struct's order (their positions are MPCT_LX_*): (name, per output row?, integer?)
+LIMIT_FIELDS = [("viol", True, False), ("viol2", True, False), ("vmax", True, False), ("t_vmax", True, True),
+                ("n_out", True, True), ("t_in", True, True), ("y_margin", True, False),
+                ("n_lo", False, True), ("n_hi", False, True), ("n_rate", False, True), ("sat_run", False, True),
+                ("u_margin", False, False), ("du_margin", False, False)]
+
+
+class MpctLimitResult(C.Structure):
+    _fields_ = [(n, c_int32_p if i else c_double_p) for n, _, i in LIMIT_FIELDS]
+
+
 class MpctRobustTail(C.Structure):
     _fields_ = [("quantile", c_double_p), ("cvar", c_double_p), ("q_draw", c_int32_p)]
 
@@ -143,6 +160,8 @@ EXPORTS = [
     "mpct_draw_stats_device", "mpct_draw_stats", "mpct_eval_robust_indices", "mpct_eval_robust_indices_device",
     "mpct_hypervolume_device", "mpct_hypervolume", "mpct_hv_select_device", "mpct_hv_select",
     "mpct_hypervolume_exact_device", "mpct_hypervolume_exact",
+    "mpct_limit_indices_device", "mpct_limit_indices", "mpct_eval_limit_indices", "mpct_eval_limit_indices_device",
+    "mpct_eval_robust_limit_indices", "mpct_eval_robust_limit_indices_device",
 ]
 
 ABI_VERSION = 7
@@ -152,6 +171,7 @@ HV_MAX_SAMPLES, HV_BINS = 1073741824, 8
 HVSEL_MAX_PICKS = 1024
 HVX_MAX_OBJ, HVX_MAX_M = 3, 65536
 INDEX_MAX_ROWS, INDEX_SCRATCH_BYTES = 2147483647, 268435456
+LIMIT_MAX_CH = 32
 STAT_F64, STAT_I32 = 0, 1
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
 ST_SQP_MAXITER, ST_BOUNDS, ST_NOT_RUN = 32, 64, 128
@@ -297,6 +317,22 @@ def load():
     lib.mpct_eval_robust_indices.restype = C.c_int32
     lib.mpct_eval_robust_indices_device.argtypes = robust_index_args + [C.c_void_p]
     lib.mpct_eval_robust_indices_device.restype = C.c_int32
+    limit_args = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MpctLimitParams)]
+    lib.mpct_limit_indices_device.argtypes = limit_args + [C.POINTER(MpctLimitResult), C.c_void_p]
+    lib.mpct_limit_indices_device.restype = C.c_int32
+    lib.mpct_limit_indices.argtypes = limit_args + [C.c_int32, C.POINTER(MpctLimitResult)]
+    lib.mpct_limit_indices.restype = C.c_int32
+    eval_limit_args = batch_args[:10] + [C.POINTER(MpctLimitParams), C.POINTER(MpctResult), C.POINTER(MpctLimitResult)]
+    lib.mpct_eval_limit_indices.argtypes = eval_limit_args
+    lib.mpct_eval_limit_indices.restype = C.c_int32
+    lib.mpct_eval_limit_indices_device.argtypes = eval_limit_args + [C.c_void_p]
+    lib.mpct_eval_limit_indices_device.restype = C.c_int32
+    robust_limit_args = robust_args[:11] + [C.POINTER(MpctLimitParams), C.c_int32, c_int32_p, C.c_int32, c_double_p,
+                                            C.POINTER(MpctRobustResult), C.POINTER(MpctDrawStats)]
+    lib.mpct_eval_robust_limit_indices.argtypes = robust_limit_args
+    lib.mpct_eval_robust_limit_indices.restype = C.c_int32
+    lib.mpct_eval_robust_limit_indices_device.argtypes = robust_limit_args + [C.c_void_p]
+    lib.mpct_eval_robust_limit_indices_device.restype = C.c_int32
     # the largest grid of draw_stats_kernel in workgroups (0: the default): a test hook
     lib.mpct_internal_draw_stats_grid.argtypes = [C.c_int32]
     lib.mpct_internal_draw_stats_grid.restype = C.c_int32

@@ -18,6 +18,12 @@
   draw_stats_device   mpct_draw_stats_device (torch CUDA tensors, enqueued on the current stream)
   eval_robust_indices mpct_eval_robust_indices: per-candidate statistics of the indices over the plant draws
   eval_robust_indices_device  mpct_eval_robust_indices_device (torch CUDA tensors, enqueued on a stream)
+  limit_indices       mpct_limit_indices: band violation, saturation and rate-limit use of stored trajectories
+  limit_indices_device  mpct_limit_indices_device (torch CUDA tensors, enqueued on the current stream)
+  eval_limit_indices  mpct_eval_limit_indices: score a batch and return only its limit records
+  eval_limit_indices_device  mpct_eval_limit_indices_device (torch CUDA tensors, enqueued on a stream)
+  eval_robust_limit_indices  mpct_eval_robust_limit_indices: their statistics over the plant draws
+  eval_robust_limit_indices_device  mpct_eval_robust_limit_indices_device (torch CUDA tensors, enqueued on a stream)
 
 No CPU fallback: every numerical result comes from the HIP kernel.
 """
@@ -1306,3 +1312,289 @@ def eval_robust_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, base: di
         nlev, _dp(lv) if nlev else None, C.byref(br), C.byref(so), C.c_void_p(stream.cuda_stream))
     if rc != 0:
         raise MpctError("mpct_eval_robust_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+# --------------------------------------------------------------------------------------------
+# limit indices per simulation and their statistics over the draws (mpct_limit_indices, mpct_eval_limit_indices,
+# mpct_eval_robust_limit_indices; include/mpct.h)
+LIMIT_FIELDS = tuple(n for n, _, _ in _lib.LIMIT_FIELDS)
+_LIMIT_BOUNDS = ("y_lo", "y_hi", "u_lo", "u_hi", "du_lo", "du_hi")
+
+
+@dataclass
+class LimitResult:
+    """One array per field of mpct_limit_result: the output-row fields (C, nref, my), the input-row fields
+    (C, nref, nu); a field that was not asked for is None.  An invalid row (a non-finite sample in
+    [t0, nit)) holds NaN / -1."""
+    viol: np.ndarray | None = None
+    viol2: np.ndarray | None = None
+    vmax: np.ndarray | None = None
+    t_vmax: np.ndarray | None = None
+    n_out: np.ndarray | None = None
+    t_in: np.ndarray | None = None       # nit = still outside at the last sample
+    y_margin: np.ndarray | None = None   # +inf without a bound
+    n_lo: np.ndarray | None = None
+    n_hi: np.ndarray | None = None
+    n_rate: np.ndarray | None = None
+    sat_run: np.ndarray | None = None
+    u_margin: np.ndarray | None = None
+    du_margin: np.ndarray | None = None
+    nit: int = 0
+    t0: int = 0
+    batch: EvalResult | None = None      # eval_limit_indices(want_costs=True): J1, j22, status, qp_iters of the same launch
+
+    def costs(self, names, reduce: str = "max") -> np.ndarray:
+        """(C, len(names)) float matrix for ``pareto``: each named field folded over the references and
+        channels by ``reduce`` ('max' or 'sum').  The integer fields enter as floats, ``t_vmax`` and ``t_in``
+        as samples after t0.  The margins enter negated (less margin costs more), and a channel without a
+        bound (an infinite margin) takes no part in the fold.  A candidate with an invalid row (NaN / -1), or
+        with no bounded channel for a margin, gets NaN in that column: invalid for ``pareto``, last for
+        ``rank``."""
+        if reduce not in ("max", "sum"):
+            raise ValueError("reduce must be 'max' or 'sum'")
+        is_int = {n: i for n, _, i in _lib.LIMIT_FIELDS}
+        cols = []
+        for name in names:
+            if name not in LIMIT_FIELDS:
+                raise ValueError("unknown limit field %r" % (name,))
+            a = getattr(self, name)
+            if a is None:
+                raise ValueError("this result has no %s" % name)
+            a = np.asarray(a)
+            x = a.reshape(a.shape[0], -1).astype(float)
+            neutral = np.zeros(x.shape, dtype=bool)
+            if is_int[name]:
+                x = np.where(x < 0, np.nan, x - (self.t0 if name in ("t_vmax", "t_in") else 0))
+            elif name.endswith("margin"):
+                neutral = np.isposinf(x)
+                x = -x
+            # a NaN in the row makes the fold NaN (np.max and np.sum propagate it)
+            x = np.where(neutral, -np.inf if reduce == "max" else 0.0, x)
+            col = x.max(axis=1) if reduce == "max" else x.sum(axis=1)
+            col = np.where(neutral.all(axis=1) & (x.shape[1] > 0), np.nan, col)
+            cols.append(col)
+        return np.stack(cols, axis=1) if cols else np.zeros((0, 0))
+
+
+def _limit_fields(fields):
+    fields = LIMIT_FIELDS if fields is None else tuple(fields)
+    for f in fields:
+        if f not in LIMIT_FIELDS:
+            raise ValueError("unknown limit field %r" % (f,))
+    return fields
+
+
+def _limit_params(my, nu, t0, out_tol, sat_tol, bounds: dict):
+    """The MpctLimitParams of a call and the host arrays it points to (keep them alive for the call).  ``bounds``
+    maps y_lo, y_hi (my values) and u_lo, u_hi, du_lo, du_hi (nu values) to sequences; an absent or None entry
+    stays NULL (no bound in the scenario-free entries, the scenario's own bound in the others)."""
+    p = _lib.MpctLimitParams(int(t0), float(out_tol), float(sat_tol))
+    keep = []
+    for name in bounds:
+        if name not in _LIMIT_BOUNDS:
+            raise ValueError("unknown bound %r" % (name,))
+    for name in _LIMIT_BOUNDS:
+        a = bounds.get(name)
+        if a is None:
+            continue
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64), (my if name[0] == "y" else nu,)))
+        keep.append(a)
+        setattr(p, name, _dp(a))
+    return p, keep
+
+
+def _limit_result(Cn, nref, my, nu, nit, t0, fields):
+    """A LimitResult with the arrays of ``fields`` and the MpctLimitResult that points into them."""
+    res = LimitResult(nit=int(nit), t0=int(t0))
+    r = _lib.MpctLimitResult()
+    for name, is_y, is_int in _lib.LIMIT_FIELDS:
+        if name in fields:
+            a = np.zeros((Cn, nref, my if is_y else nu), dtype=np.int32 if is_int else np.float64)
+            setattr(res, name, a)
+            setattr(r, name, _ip(a) if is_int else _dp(a))
+    return res, r
+
+
+def _limit_struct(out: dict):
+    r = _lib.MpctLimitResult()
+    for name, _, is_int in _lib.LIMIT_FIELDS:
+        setattr(r, name, _tptr(out.get(name), _lib.c_int32_p if is_int else _lib.c_double_p))
+    return r
+
+
+def limit_indices(y, u, t0=0, out_tol=0.0, sat_tol=0.0, fields=None, nref=1, device=-1, **bounds) -> LimitResult:
+    """mpct_limit_indices: the limit indices of stored trajectories, reduced on the GPU (host arrays in and
+    out).  ``y`` (S, my, nit), ``u`` (S, nu, nit); ``y`` may be None when ``fields`` names no output-row field,
+    ``u`` when it names no input-row field.  ``bounds``: y_lo, y_hi, u_lo, u_hi, du_lo, du_hi per channel (a
+    scalar is broadcast; absent: no bound).  The arrays of the result are (S / nref, nref, my) and
+    (S / nref, nref, nu)."""
+    y = None if y is None else np.ascontiguousarray(y, dtype=np.float64)
+    u = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
+    if (y is not None and y.ndim != 3) or (u is not None and u.ndim != 3):
+        raise ValueError("y and u must be 3-d: (S, my, nit), (S, nu, nit)")
+    if y is None and u is None:
+        raise ValueError("y or u is needed")
+    some = y if y is not None else u
+    S, nit = some.shape[0], some.shape[2]
+    my = y.shape[1] if y is not None else 0
+    nu = u.shape[1] if u is not None else 0
+    if u is not None and u.shape[::2] != (S, nit):
+        raise ValueError("y and u disagree on S or nit")
+    if fields is None:
+        fields = tuple(n for n, is_y, _ in _lib.LIMIT_FIELDS if (y if is_y else u) is not None)
+    fields = _limit_fields(fields)
+    if nref < 1 or S % nref:
+        raise ValueError("S must be a multiple of nref")
+    res, out = _limit_result(S // nref, nref, my, nu, nit, t0, fields)
+    p, keep = _limit_params(my, nu, t0, out_tol, sat_tol, bounds)
+    rc = _lib.load().mpct_limit_indices(y.ctypes.data if y is not None else None, u.ctypes.data if u is not None else None,
+                                        S, my, nu, nit, C.byref(p), int(device), C.byref(out))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_limit_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return res
+
+
+def limit_indices_device(y, u, out: dict, t0=0, out_tol=0.0, sat_tol=0.0, **bounds):
+    """mpct_limit_indices_device: ``y`` [S, my, nit] and ``u`` [S, nu, nit] are contiguous float64 CUDA (HIP)
+    tensors (None where no field needs them); the records are written into the tensors of ``out`` (keys as the
+    fields of LimitResult: float64 / int32, [S, my] or [S, nu]; any may be absent).  ``bounds`` are HOST
+    sequences, as in limit_indices.  Enqueued on the current torch stream of the tensors' device and not
+    synchronised."""
+    import torch
+
+    some = y if y is not None else u
+    for t in (y, u):
+        if t is not None and (t.dtype != torch.float64 or t.dim() != 3 or not t.is_contiguous()):
+            raise ValueError("y and u must be contiguous float64 tensors with three dimensions")
+    S, nit = some.shape[0], some.shape[2]
+    my = y.shape[1] if y is not None else 0
+    nu = u.shape[1] if u is not None else 0
+    p, keep = _limit_params(my, nu, t0, out_tol, sat_tol, bounds)
+    o = _limit_struct(out)
+    stream = torch.cuda.current_stream(some.device).cuda_stream
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(some.device):
+        rc = _lib.load().mpct_limit_indices_device(ptr(y), ptr(u), S, my, nu, nit, C.byref(p), C.byref(o),
+                                                   C.c_void_p(stream))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_limit_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+def eval_limit_indices(sc, N2, Nu, delta, lam, refs, v=None, t0=0, out_tol=0.0, sat_tol=0.0, fields=None,
+                       want_costs=False, device=-1, max_qp_iter=0, feas_tol=0.0, **bounds) -> LimitResult:
+    """mpct_eval_limit_indices: score C candidates against nref reference sets and return only the limit
+    records of the closed loops (host arrays in and out); the trajectories stay on the device.  A bound that
+    is not given is the scenario's own (du_min / du_max / u_min / u_max, y_min / y_max of a band scenario), or
+    none where the scenario holds none.  ``want_costs`` adds ``batch``: J1, j22, status and qp_iters of the
+    same launch, as eval_batch returns them."""
+    fields = _limit_fields(fields)
+    N2, Nu, delta, lam, refs, Cn, nref, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    res, out = _limit_result(Cn, nref, sc.my, sc.nu, sc.nit, t0, fields)
+    br = None
+    if want_costs:
+        res.batch, br = _eval_result(sc, Cn * nref, nref, False, False)
+    p, keep = _limit_params(sc.my, sc.nu, t0, out_tol, sat_tol, bounds)
+    o = _opts(False, False, device, max_qp_iter, feas_tol)
+    rc = sc.lib.mpct_eval_limit_indices(sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data,
+                                        lam.ctypes.data, nref, refs.ctypes.data, vv.ctypes.data if vv is not None else None,
+                                        C.byref(o), C.byref(p), C.byref(br) if br is not None else None, C.byref(out))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_eval_limit_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return res
+
+
+def eval_limit_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, v=None, t0=0, out_tol=0.0, sat_tol=0.0,
+                              device=-1, stream=None, **bounds):
+    """Device-pointer entry of eval_limit_indices: every argument is a CUDA (HIP) torch tensor (``bounds`` are
+    HOST sequences); the records are written into the tensors of ``out`` (the keys of limit_indices_device,
+    [C * nref, my] / [C * nref, nu], plus the optional J1, j21, j22, Jnu, status, qp_iters of
+    eval_batch_device).  Enqueued on ``stream`` (torch stream; default: current) and not synchronised."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    br = _lib.MpctResult()
+    br.J1, br.j21 = _tptr(out.get("J1"), _lib.c_double_p), _tptr(out.get("j21"), _lib.c_double_p)
+    br.j22, br.Jnu = _tptr(out.get("j22"), _lib.c_double_p), _tptr(out.get("Jnu"), _lib.c_double_p)
+    br.status, br.qp_iters = _tptr(out.get("status"), _lib.c_int32_p), _tptr(out.get("qp_iters"), _lib.c_int64_p)
+    p, keep = _limit_params(sc.my, sc.nu, t0, out_tol, sat_tol, bounds)
+    o = _opts(False, False, device)
+    lo = _limit_struct(out)
+    rc = sc.lib.mpct_eval_limit_indices_device(
+        sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+        C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+        C.c_void_p(v.data_ptr()) if v is not None else None, C.byref(o), C.byref(p), C.byref(br), C.byref(lo),
+        C.c_void_p(stream.cuda_stream))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_eval_limit_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+def _limit_field_ids(sc, fields):
+    """The MPCT_LX_* ids of the selected fields as the int32 vector the library reads, and the (field, channel)
+    columns."""
+    fields = _limit_fields(fields)
+    ids = np.ascontiguousarray([LIMIT_FIELDS.index(f) for f in fields], dtype=np.int32)
+    is_y = {n: y for n, y, _ in _lib.LIMIT_FIELDS}
+    cols = [(f, ch) for f in fields for ch in range(sc.my if is_y[f] else sc.nu)]
+    return ids, cols
+
+
+def eval_robust_limit_indices(sc, N2, Nu, delta, lam, refs, v=None, fields=None, levels=None, j_bound=0.0, t0=0,
+                              out_tol=0.0, sat_tol=0.0, device=-1, max_qp_iter=0, feas_tol=0.0,
+                              **bounds) -> RobustIndexResult:
+    """mpct_eval_robust_limit_indices: score C candidates over the D = len(refs) draws and reduce, on the
+    device, the limit indices ``fields`` (default: all thirteen) of the C x D closed loops to per-candidate
+    statistics over the surviving draws (host arrays in and out): eval_robust_indices for the limit indices,
+    with the bounds of eval_limit_indices.  A draw without a value in a column (an invalid row, or an infinite
+    margin: no bound) does not enter that column."""
+    N2, Nu, delta, lam, refs, Cn, D, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    ids, cols = _limit_field_ids(sc, fields)
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    arr, out = _stats_arrays(Cn, len(cols), nlev)
+    base = RobustResult(mean=np.zeros((Cn, sc.my)), worst=np.zeros((Cn, sc.my)), n_failed=np.zeros(Cn, dtype=np.int32),
+                        worst_draw=np.zeros(Cn, dtype=np.int32), status=np.zeros(Cn, dtype=np.int32), draws=D)
+    br = _lib.MpctRobustResult()
+    br.mean, br.worst = _dp(base.mean), _dp(base.worst)
+    br.n_failed, br.worst_draw, br.status = _ip(base.n_failed), _ip(base.worst_draw), _ip(base.status)
+    p, keep = _limit_params(sc.my, sc.nu, t0, out_tol, sat_tol, bounds)
+    o = _opts(False, False, device, max_qp_iter, feas_tol)
+    rc = sc.lib.mpct_eval_robust_limit_indices(
+        sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data, lam.ctypes.data, D, refs.ctypes.data,
+        vv.ctypes.data if vv is not None else None, float(j_bound), C.byref(o), C.byref(p), ids.size, _ip(ids), nlev,
+        _dp(lv) if nlev else None, C.byref(br), C.byref(out))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_limit_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return RobustIndexResult(columns=cols, levels=lv, base=base, **arr)
+
+
+def eval_robust_limit_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, base: dict | None = None, v=None,
+                                     fields=None, levels=None, j_bound=0.0, t0=0, out_tol=0.0, sat_tol=0.0, device=-1,
+                                     stream=None, **bounds):
+    """Device-pointer entry of eval_robust_limit_indices: every argument is a CUDA (HIP) torch tensor
+    (``fields``, ``levels`` and ``bounds`` are HOST sequences); ``out`` and ``base`` as in
+    eval_robust_indices_device.  Enqueued on ``stream`` (torch stream; default: current) and not synchronised."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    ids, _ = _limit_field_ids(sc, fields)
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    br = _robust_struct(base or {})
+    p, keep = _limit_params(sc.my, sc.nu, t0, out_tol, sat_tol, bounds)
+    o = _opts(False, False, device)
+    so = _stats_struct(out)
+    rc = sc.lib.mpct_eval_robust_limit_indices_device(
+        sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+        C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+        C.c_void_p(v.data_ptr()) if v is not None else None, float(j_bound), C.byref(o), C.byref(p), ids.size, _ip(ids),
+        nlev, _dp(lv) if nlev else None, C.byref(br), C.byref(so), C.c_void_p(stream.cuda_stream))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_limit_indices_device failed (%d): %s" % (rc, _lib.last_error()))
