@@ -36,7 +36,10 @@
  *     objectives (mpct_hvx_result, mpct_hypervolume_exact_device, mpct_hypervolume_exact), and the limit
  *     indices (mpct_limit_params, mpct_limit_result, mpct_limit_indices_device, mpct_limit_indices,
  *     mpct_eval_limit_indices, mpct_eval_limit_indices_device, mpct_eval_robust_limit_indices,
- *     mpct_eval_robust_limit_indices_device).
+ *     mpct_eval_robust_limit_indices_device), and the step-response indices per setpoint segment
+ *     (mpct_segment_params, mpct_segment_result, mpct_reference_segments, mpct_segment_indices_device,
+ *     mpct_segment_indices, mpct_eval_segment_indices, mpct_eval_segment_indices_device,
+ *     mpct_eval_robust_segment_indices, mpct_eval_robust_segment_indices_device).
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -1214,6 +1217,198 @@ int32_t mpct_eval_robust_limit_indices_device(mpct_scenario* s, int64_t C, const
                                               const int32_t* fields, int32_t nlev, const double* levels,
                                               mpct_robust_result* base, const mpct_draw_stats_result* out,
                                               void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Step-response indices per setpoint segment, reduced on the device from the trajectories
+ * (segment_indices.hip).  The performance indices above measure overshoot and settling time
+ * against ONE step per run, r_f = r(nit-1) and d = r_f - y(t0); a scenario whose reference changes several
+ * times (Shell 3x3: samples 9, 79, 199, 399, and back to 0) has d = 0 there.  These entries cut the run into
+ * segments at the setpoint changes and give one record per (row, segment): the indices above per segment,
+ * plus the rise time and the undershoot of an inverse response.
+ *
+ * Segments.  nseg in [1, MPCT_SEG_MAX]; tseg[nseg+1] is a HOST pointer to strictly ascending int32 with
+ * 0 <= tseg[0] and tseg[nseg] <= nit.  Segment g covers the samples a <= t < b with a = tseg[g], b = tseg[g+1].
+ * One boundary list serves every row and every reference set; the boundaries travel to the kernel by value in
+ * its argument.  Nothing before tseg[0] or from tseg[nseg] on is ever read.
+ *
+ * Trajectories in mpct_result's layout: y[S][my][nit], u[S][nu][nit], r[nref][my][nit]; simulation s reads
+ * reference set s % nref (S is a multiple of nref).
+ *
+ * Output row (s, i), segment g, with e(t) = y(t) - r(t) and r_g = r(b-1).  The base level c: in segment 0
+ * c = y(a), whatever `base`; in a later segment c = y(a) with base = 0 (the rule of the performance indices)
+ * and c = r(a-1), the level the reference left, with base = 1.  d = r_g - c, sigma = sign(d) (0 for d = 0),
+ * p(t) = sigma*(y(t) - c):
+ *   iae      sum_t |e(t)|
+ *   ise      sum_t e(t)*e(t)
+ *   itae     sum_t (double)(t - a) * |e(t)|
+ *   emax     max_t |e(t)|;  t_emax  the first t that attains it (an absolute sample)
+ *   over     sigma != 0: max_t sigma*e(t) where that is > 0, else +0.0.  sigma = 0: emax
+ *   under    the excursion on the wrong side of the base level (inverse response).  sigma != 0: max_t -p(t)
+ *            where that is > 0, else +0.0.  sigma = 0: +0.0
+ *   e_final  e(b-1), signed
+ *   settle   the smallest T in [a, b] with |y(t) - r_g| <= band_rel*|d| + band_abs for every t in [T, b): the
+ *            last violating sample + 1, a when there is none; b = "not settled inside the segment"
+ *   rise     t_hi - t_lo, where t_lo / t_hi are the first t in [a, b) with p(t) >= rise_lo*|d| /
+ *            p(t) >= rise_hi*|d|; b - a when sigma != 0 and t_hi does not exist; -1 when sigma = 0
+ * Input row (s, n), segment g, with du(t) = u(t) - u(t-1) for t in [max(a, tseg[0]+1), b): the move across a
+ * boundary belongs to the segment it starts, so over real numbers the segments' tv add up to the whole run's:
+ *   tv       sum |du|         du2    sum du*du        dumax  max |du|; the three are 0.0 over an empty range
+ *   u_lo, u_hi  min and max of u(t) over [a, b); a zero extreme is +0.0
+ *
+ * Layout.  Element (row*nseg + g) of each array: output fields [S][my][nseg], input fields [S][nu][nseg].
+ *
+ * Validity.  The unit is one (row, segment).  It is INVALID when any sample it reads is non-finite: y and r in
+ * [a, b), and r(a-1) where base = 1 uses it (g >= 1), for an output unit; u in [a, b), and u(a-1) for g >= 1,
+ * for an input unit.  An invalid unit gives NaN in its doubles and -1 in its integers; no other unit is
+ * affected, the other segments of the same row included.
+ *
+ * No contraction; fixed order.  Every product above is rounded to double before it is added (e*e,
+ * (t-a)*|e|, du*du, band_rel*|d|, rise_lo*|d|, rise_hi*|d|): no fused multiply-add anywhere.  Lane
+ * l = (t - a) mod 64 accumulates its samples in ascending t, starting from 0.0; the 64 partials are combined
+ * as the pairwise tree in lane order of the performance indices.  Extremes, t_emax, settle and rise are
+ * exact.  A repeated call is bitwise identical and a record does not depend on the simulation's place in the
+ * batch.
+ *
+ * Consequence.  With nseg = 1, base = 0 and tseg = {t0, nit}, every field shared with mpct_index_result (all
+ * but under and rise) equals that of mpct_indices_device with the same t0, band_rel and band_abs bit for bit.
+ *
+ * Any result pointer may be NULL, but not all of them.  y and r may be NULL when no output-row field is
+ * requested, u when no input-row field is.  Only the requested arrays are written.
+ *
+ * Argument errors, in this order and before any device is touched:
+ *   MPCT_EINVAL  params NULL; S < 0, my < 0, nu < 0 or nit < 1
+ *   MPCT_EINVAL  nref < 1
+ *   MPCT_EINVAL  S not a multiple of nref
+ *   MPCT_EINVAL  nseg < 1 or tseg NULL
+ *   MPCT_ERANGE  nseg > MPCT_SEG_MAX (the boundaries travel in the kernel argument)
+ *   MPCT_EINVAL  tseg[0] < 0, tseg[nseg] > nit, or tseg not strictly ascending
+ *   MPCT_EINVAL  base neither 0 nor 1
+ *   MPCT_EINVAL  band_rel or band_abs negative, infinite or NaN
+ *   MPCT_EINVAL  rise_lo or rise_hi NaN, or not 0 <= rise_lo <= rise_hi <= 1
+ *   MPCT_EINVAL  out NULL, or all fifteen of its pointers NULL
+ *   MPCT_EINVAL  an output-row field with my < 1, or (S > 0) with y or r NULL; an input-row field with
+ *                nu < 1, or (S > 0) with u NULL
+ *   MPCT_ERANGE  S*my*nseg or S*nu*nseg > MPCT_INDEX_MAX_ROWS (one wave per row and segment)
+ * S = 0 is MPCT_OK and writes nothing. */
+#define MPCT_SEG_MAX 16
+typedef struct mpct_segment_params {
+  int32_t nseg;        /* 1 .. MPCT_SEG_MAX */
+  const int32_t* tseg; /* [nseg+1] HOST, strictly ascending, 0 <= tseg[0], tseg[nseg] <= nit */
+  int32_t base;        /* base level of segments g >= 1: 0 = y(a), 1 = r(a-1) */
+  double band_rel;     /* settling band relative to the step size |d| */
+  double band_abs;     /* plus an absolute band; both finite and >= 0 */
+  double rise_lo;      /* rise levels as fractions of |d| (0.1 and 0.9: the 10-90 % rise time); */
+  double rise_hi;      /* 0 <= rise_lo <= rise_hi <= 1 */
+} mpct_segment_params;
+
+typedef struct mpct_segment_result {
+  double* iae;      /* [S*my*nseg] */
+  double* ise;      /* [S*my*nseg] */
+  double* itae;     /* [S*my*nseg] */
+  double* emax;     /* [S*my*nseg] */
+  int32_t* t_emax;  /* [S*my*nseg] */
+  double* over;     /* [S*my*nseg] */
+  double* under;    /* [S*my*nseg] */
+  double* e_final;  /* [S*my*nseg] */
+  int32_t* settle;  /* [S*my*nseg] */
+  int32_t* rise;    /* [S*my*nseg] */
+  double* tv;       /* [S*nu*nseg] */
+  double* du2;      /* [S*nu*nseg] */
+  double* dumax;    /* [S*nu*nseg] */
+  double* u_lo;     /* [S*nu*nseg] */
+  double* u_hi;     /* [S*nu*nseg] */
+} mpct_segment_result;
+
+/* the field ids of mpct_eval_robust_segment_indices, in the member order of mpct_segment_result */
+#define MPCT_SX_IAE 0
+#define MPCT_SX_ISE 1
+#define MPCT_SX_ITAE 2
+#define MPCT_SX_EMAX 3
+#define MPCT_SX_T_EMAX 4
+#define MPCT_SX_OVER 5
+#define MPCT_SX_UNDER 6
+#define MPCT_SX_E_FINAL 7
+#define MPCT_SX_SETTLE 8
+#define MPCT_SX_RISE 9
+#define MPCT_SX_TV 10
+#define MPCT_SX_DU2 11
+#define MPCT_SX_DUMAX 12
+#define MPCT_SX_U_LO 13
+#define MPCT_SX_U_HI 14
+
+/* The segment boundaries of a reference, on the host (no device): {0} u {t >= 1 where any row of any
+ * reference set has r(t) != r(t-1)} u the caller's `extra` event samples u {nit}, sorted and deduplicated,
+ * into tseg_out[0 .. *nseg].  r is [nref][my][nit]; `extra` (nextra values, or NULL with nextra = 0) carries
+ * instants the reference does not show, such as the sample of a measured disturbance; tseg_out holds
+ * max_seg + 1 values.  MPCT_EINVAL, in this order: r, tseg_out or nseg NULL; nref < 1, my < 1 or nit < 1;
+ * max_seg < 1; nextra < 0, or nextra > 0 with extra NULL; an extra sample outside [0, nit]; a non-finite r.
+ * More than max_seg segments: MPCT_ERANGE (nothing is written). */
+int32_t mpct_reference_segments(const double* r, int32_t nref, int32_t my, int32_t nit, const int32_t* extra,
+                                int32_t nextra, int32_t max_seg, int32_t* tseg_out, int32_t* nseg);
+
+/* y, u, r and the pointers of `out` DEVICE pointers (params and its tseg HOST, read before the call returns);
+ * enqueued on `stream` (NULL = default stream) and NOT synchronised.  Needs no scenario and no scratch: one
+ * kernel launch. */
+int32_t mpct_segment_indices_device(const double* y, const double* u, const double* r, int64_t S, int32_t nref,
+                                    int32_t my, int32_t nu, int32_t nit, const mpct_segment_params* params,
+                                    const mpct_segment_result* out, void* stream);
+
+/* Host pointers (MATLAB and C callers), for trajectories from any source.  device: HIP ordinal, -1 = the
+ * current device (an ordinal out of range is MPCT_EINVAL).  Stages on a stream of its own and waits for that
+ * stream only; y and r travel only behind an output-row field and u only behind an input-row field; the
+ * calling thread's current device is unchanged on return.  Without a device: MPCT_EDEVICE with a message. */
+int32_t mpct_segment_indices(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my,
+                             int32_t nu, int32_t nit, const mpct_segment_params* params, int32_t device,
+                             const mpct_segment_result* out);
+
+/* Score a batch and return only the segment records (host pointers; arguments as mpct_eval_indices, whose
+ * chunking, scratch, `res` and `opts` rules hold unchanged): S = C*nref simulations, output fields
+ * [S*my*nseg], input fields [S*nu*nseg]; the reference sets of the indices are the call's r.  Every record is
+ * bitwise independent of the chunk size.
+ * MPCT_EINVAL, in this order and before any device is touched: s NULL; params NULL; open_loop set; a
+ * trajectory pointer in res; then everything mpct_eval_batch rejects; then the checks of
+ * mpct_segment_indices_device from nseg on, nit the scenario's.  C = 0 is MPCT_OK and writes nothing.  Without a
+ * device: MPCT_EDEVICE with a message. */
+int32_t mpct_eval_segment_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                  const double* delta, const double* lambda, int32_t nref, const double* r,
+                                  const double* v, const mpct_opts* opts, const mpct_segment_params* params,
+                                  mpct_result* res, const mpct_segment_result* out);
+
+/* Same, all pointers DEVICE pointers (res's and out's included; params and its tseg HOST), enqueued on
+ * `stream` (NULL = default stream) and NOT synchronised: the contract of mpct_eval_indices_device, whose
+ * scratch and stream-ordering rule it shares. */
+int32_t mpct_eval_segment_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                         const double* delta, const double* lambda, int32_t nref, const double* r,
+                                         const double* v, const mpct_opts* opts, const mpct_segment_params* params,
+                                         mpct_result* res, const mpct_segment_result* out, void* stream);
+
+/* Score C candidates x D = nref draws and return, per candidate, the statistics over the draws of the
+ * selected segment indices: the arguments and semantics of mpct_eval_robust_indices with mpct_segment_params
+ * in place of mpct_index_params and `fields` drawn from MPCT_SX_IAE .. MPCT_SX_U_HI (1 <= nsel <= 15).  A
+ * selected output-row field contributes my*nseg columns (channel i, segment g at i*nseg + g), an input-row
+ * field nu*nseg: the tables of `out` are [C][W] and [C][W][nlev] with W the sum over the selection.  t_emax,
+ * settle and rise enter the statistics as MPCT_STAT_I32, so a rise of -1 (sigma = 0) is a draw without a
+ * value; the others as MPCT_STAT_F64.  `base` is the robust J1 record of the same launch.
+ * Errors, in this order and before any device is touched: those of mpct_eval_robust_indices up to and
+ * including everything mpct_eval_batch rejects; then the checks of mpct_segment_indices_device from nseg up
+ * to rise_hi; then MPCT_ERANGE for nref > MPCT_TAIL_MAX_DRAWS, and for C*nref*my*nseg or C*nref*nu*nseg >
+ * MPCT_INDEX_MAX_ROWS.  C = 0 is MPCT_OK and writes nothing. */
+int32_t mpct_eval_robust_segment_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                         const double* delta, const double* lambda, int32_t nref, const double* r,
+                                         const double* v, double j_bound, const mpct_opts* opts,
+                                         const mpct_segment_params* params, int32_t nsel, const int32_t* fields,
+                                         int32_t nlev, const double* levels, mpct_robust_result* base,
+                                         const mpct_draw_stats_result* out);
+
+/* Same, all pointers DEVICE pointers except params with its tseg, fields and levels; enqueued on `stream`
+ * and NOT synchronised: the contract of mpct_eval_robust_indices_device. */
+int32_t mpct_eval_robust_segment_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                const double* delta, const double* lambda, int32_t nref,
+                                                const double* r, const double* v, double j_bound,
+                                                const mpct_opts* opts, const mpct_segment_params* params,
+                                                int32_t nsel, const int32_t* fields, int32_t nlev,
+                                                const double* levels, mpct_robust_result* base,
+                                                const mpct_draw_stats_result* out, void* stream);
 
 #ifdef __cplusplus
 }

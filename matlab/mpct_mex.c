@@ -84,6 +84,12 @@
  *                                                    the same for a scored batch, bounds of the scenario by default
  *   T = mpct_mex('eval_robust_limit_indices', h, N2, Nu, delta, lambda, r, v, params)
  *                                                    their statistics over the D pages of r
+ *   tseg = mpct_mex('reference_segments', r, extra)  the segment boundaries of a reference (mpct_reference_segments)
+ *   G = mpct_mex('segment_indices', y, u, r, params) step-response indices per setpoint segment of stored trajectories
+ *   G = mpct_mex('eval_segment_indices', h, N2, Nu, delta, lambda, r, v, params)
+ *                                                    the same for a scored batch, boundaries of r by default
+ *   T = mpct_mex('eval_robust_segment_indices', h, N2, Nu, delta, lambda, r, v, params)
+ *                                                    their statistics over the D pages of r
  *   T = mpct_mex('eval_robust_indices', h, N2, Nu, delta, lambda, r, v, params)
  *                                                    statistics of the performance indices over the D pages of r
  *                                                    (mpct_eval_robust_indices).  params (optional struct): fields
@@ -1286,6 +1292,259 @@ static void cmd_eval_robust_indices(mxArray* plhs[], int nrhs, const mxArray* pr
   plhs[0] = T;
 }
 
+/* ---- step-response indices per setpoint segment (mpct_reference_segments, mpct_segment_indices,
+ * mpct_eval_segment_indices, mpct_eval_robust_segment_indices; include/mpct.h) */
+static const char* const kSegNames[15] = {"iae", "ise", "itae", "emax", "t_emax", "over", "under", "e_final",
+                                          "settle", "rise", "tv", "du2", "dumax", "u_lo", "u_hi"};
+static const int kSegIsInt[15] = {0, 0, 0, 0, 1, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0};
+
+/* the boundaries of a reference r (my x nit x nref in the library's layout rr) with the 'extra' samples of params */
+static int32_t* segments_of(const double* rr, int nref, int my, int nit, const mxArray* po, int32_t* nseg) {
+  const mxArray* e = po ? mxGetField(po, 0, "extra") : NULL;
+  const long nextra = e && !mxIsEmpty(e) ? (long)mxGetNumberOfElements(e) : 0;
+  int32_t* extra = nextra ? ints(e, -1, "extra") : NULL;
+  int32_t* tseg = (int32_t*)mxCalloc(MPCT_SEG_MAX + 1, sizeof(int32_t));
+  if (mpct_reference_segments(rr, nref, my, nit, extra, (int32_t)nextra, MPCT_SEG_MAX, tseg, nseg) != MPCT_OK)
+    lib_error("mpct:reference_segments");
+  return tseg;
+}
+
+/* params struct (all fields optional): tseg (0-based boundaries; default: those of the reference r with the event
+ * samples 'extra'), base (1), band_rel (0.02), band_abs (0), rise_lo (0.1), rise_hi (0.9), device */
+static mpct_segment_params read_segment_params(const mxArray* o, double* device, const double* rr, int nref, int my, int nit) {
+  mpct_segment_params p;
+  memset(&p, 0, sizeof p);
+  *device = -1.0;
+  p.base = 1, p.band_rel = 0.02, p.rise_lo = 0.1, p.rise_hi = 0.9;
+  if (o && !mxIsStruct(o))
+    mexErrMsgIdAndTxt("mpct:arg", "params must be a struct (tseg, extra, base, band_rel, band_abs, rise_lo, rise_hi, device)");
+  const mxArray* t = o ? mxGetField(o, 0, "tseg") : NULL;
+  if (t && !mxIsEmpty(t)) {
+    const long n = (long)mxGetNumberOfElements(t);
+    if (n < 2) mexErrMsgIdAndTxt("mpct:arg", "'tseg' must hold at least two boundaries");
+    p.tseg = ints(t, -1, "tseg");
+    p.nseg = (int32_t)(n - 1);
+  } else {
+    if (!rr) mexErrMsgIdAndTxt("mpct:arg", "'tseg' is needed where there is no reference to take the boundaries from");
+    p.tseg = segments_of(rr, nref, my, nit, o, &p.nseg);
+  }
+  if (!o) return p;
+  const double base = fscalar(o, "base", 1.0);
+  *device = fscalar(o, "device", -1.0);
+  if (base != floor(base) || fabs(base) > 1e6) mexErrMsgIdAndTxt("mpct:arg", "'base' must be an integer");
+  if (*device != floor(*device) || fabs(*device) > 1e6) mexErrMsgIdAndTxt("mpct:arg", "'device' must be an integer");
+  p.base = (int32_t)base;
+  p.band_rel = fscalar(o, "band_rel", 0.02);
+  p.band_abs = fscalar(o, "band_abs", 0.0);
+  p.rise_lo = fscalar(o, "rise_lo", 0.1);
+  p.rise_hi = fscalar(o, "rise_hi", 0.9);
+  return p;
+}
+
+static mpct_segment_result segment_buffers(long S, int my, int nu, int nseg, int with_y, int with_u, void* slot[15]) {
+  mpct_segment_result r;
+  memset(&r, 0, sizeof r);
+  void** f[15] = {(void**)&r.iae,  (void**)&r.ise,     (void**)&r.itae,   (void**)&r.emax, (void**)&r.t_emax,
+                  (void**)&r.over, (void**)&r.under,   (void**)&r.e_final, (void**)&r.settle, (void**)&r.rise,
+                  (void**)&r.tv,   (void**)&r.du2,     (void**)&r.dumax,  (void**)&r.u_lo, (void**)&r.u_hi};
+  for (int k = 0; k < 15; ++k) {
+    slot[k] = NULL;
+    if (k < 10 ? with_y : with_u)
+      slot[k] = *f[k] = mxCalloc((size_t)(S * (k < 10 ? my : nu) * nseg + 1), kSegIsInt[k] ? sizeof(int32_t) : sizeof(double));
+  }
+  return r;
+}
+
+/* the fifteen fields into struct R: S x (my * nseg) / S x (nu * nseg), channel i and segment g (both from 1) in
+ * column (i - 1) * nseg + g; [] for a group that was not computed; then tseg (1 x (nseg + 1), 0-based) */
+static void set_segment_fields(mxArray* R, void* const slot[15], const mpct_segment_params* p, long S, int my, int nu) {
+  for (int k = 0; k < 15; ++k) {
+    const int w = (k < 10 ? my : nu) * p->nseg;
+    mxArray* a;
+    if (!slot[k]) a = mxCreateDoubleMatrix(0, 0, mxREAL);
+    else if (kSegIsInt[k]) a = out_int_rows((const int32_t*)slot[k], S, w);
+    else a = out_rows((const double*)slot[k], S, w);
+    mxSetField(R, 0, kSegNames[k], a);
+  }
+  mxSetField(R, 0, "tseg", out_int_rows(p->tseg, 1, p->nseg + 1));
+}
+
+/* tseg = mpct_mex('reference_segments', r [, extra]): r my x nit x nref; the 0-based boundaries as a row */
+static void cmd_reference_segments(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 2 || nrhs > 3) mexErrMsgIdAndTxt("mpct:arg", "usage: tseg = mpct_mex('reference_segments', r [, extra])");
+  int my, nit;
+  long nref;
+  signal_dims(prhs[1], "r", &my, &nit, &nref);
+  if (nref < 1 || nref > 2147483647L) mexErrMsgIdAndTxt("mpct:arg", "'r' must be my x nit x nref");
+  int pg = 0;
+  double* r = signals(prhs[1], my, nit, &pg, "r");
+  const long nextra = nrhs > 2 && !mxIsEmpty(prhs[2]) ? (long)mxGetNumberOfElements(prhs[2]) : 0;
+  int32_t* extra = nextra ? ints(prhs[2], -1, "extra") : NULL;
+  int32_t tseg[MPCT_SEG_MAX + 1], nseg = 0;
+  if (mpct_reference_segments(r, (int32_t)nref, my, nit, extra, (int32_t)nextra, MPCT_SEG_MAX, tseg, &nseg) != MPCT_OK)
+    lib_error("mpct:reference_segments");
+  plhs[0] = out_int_rows(tseg, 1, nseg + 1);
+}
+
+/* G = mpct_mex('segment_indices', y, u, r [, params]): the layouts of 'indices'; t_emax, settle and tseg are the
+ * library's 0-based samples */
+static void cmd_segment_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 4 || nrhs > 5) mexErrMsgIdAndTxt("mpct:arg", "usage: G = mpct_mex('segment_indices', y, u, r [, params])");
+  int my, nity, nu, nitu, myr, nitr;
+  long Sy, Su, nref;
+  signal_dims(prhs[1], "y", &my, &nity, &Sy);
+  signal_dims(prhs[2], "u", &nu, &nitu, &Su);
+  signal_dims(prhs[3], "r", &myr, &nitr, &nref);
+  const int with_y = Sy > 0, with_u = Su > 0;
+  if (!with_y && !with_u) mexErrMsgIdAndTxt("mpct:arg", "'y' and 'u' are both empty");
+  if (with_y && (nref < 1 || myr != my || nitr != nity)) mexErrMsgIdAndTxt("mpct:arg", "'r' must be my x nit x nref like 'y'");
+  if (with_y && with_u && (Sy != Su || nity != nitu)) mexErrMsgIdAndTxt("mpct:arg", "'y' and 'u' must agree on nit and S");
+  const long S = with_y ? Sy : Su;
+  const int nit = with_y ? nity : nitu;
+  if (!with_y) nref = 1;
+  if (S > 2147483647L || nref > 2147483647L) mexErrMsgIdAndTxt("mpct:arg", "too many pages");
+  int pg = 0;
+  double* y = with_y ? signals(prhs[1], my, nit, &pg, "y") : NULL;
+  pg = 0;
+  double* u = with_u ? signals(prhs[2], nu, nit, &pg, "u") : NULL;
+  pg = 0;
+  double* r = with_y ? signals(prhs[3], my, nit, &pg, "r") : NULL;
+  double device;
+  const mpct_segment_params p =
+      read_segment_params(nrhs > 4 && !mxIsEmpty(prhs[4]) ? prhs[4] : NULL, &device, r, (int)nref, my, nit);
+  void* slot[15];
+  const int nb = p.nseg > 0 && p.nseg <= MPCT_SEG_MAX ? p.nseg : 1; /* a bad count sizes nothing: the library rejects it */
+  const mpct_segment_result res = segment_buffers(S, my, nu, nb, with_y, with_u, slot);
+  if (mpct_segment_indices(y, u, r, S, (int32_t)nref, my, nu, nit, &p, (int32_t)device, &res) != MPCT_OK)
+    lib_error("mpct:segment_indices");
+  const char* names[16];
+  for (int k = 0; k < 15; ++k) names[k] = kSegNames[k];
+  names[15] = "tseg";
+  mxArray* R = mxCreateStructMatrix(1, 1, 16, names);
+  set_segment_fields(R, slot, &p, S, my, nu);
+  plhs[0] = R;
+}
+
+/* G = mpct_mex('eval_segment_indices', h, N2, Nu, delta, lambda, r [, v, params]): the fifteen fields and tseg plus
+ * J1, j22 (S x my), status and iters (S x 1) of the same launch */
+static void cmd_eval_segment_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 7 || nrhs > 9)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: G = mpct_mex('eval_segment_indices', h, N2, Nu, delta, lambda, r [, v, params])");
+  const batch_args b = read_batch(nrhs, prhs, 2);
+  const int my = b.my, nu = b.nu, nit = b.nit;
+  double device;
+  const mpct_segment_params p = read_segment_params(nrhs > 8 && !mxIsEmpty(prhs[8]) ? prhs[8] : NULL, &device, b.r, b.nref, my, nit);
+  mpct_opts o = read_opts(NULL);
+  o.device = (int32_t)device;
+  const long C = b.C, S = C * b.nref;
+  void* slot[15];
+  const int nb = p.nseg > 0 && p.nseg <= MPCT_SEG_MAX ? p.nseg : 1;
+  const mpct_segment_result res = segment_buffers(S, my, nu, nb, 1, 1, slot);
+  mpct_result br;
+  memset(&br, 0, sizeof br);
+  br.J1 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
+  br.j22 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
+  br.status = (int32_t*)mxCalloc((size_t)(S + 1), sizeof(int32_t));
+  br.qp_iters = (int64_t*)mxCalloc((size_t)(S + 1), sizeof(int64_t));
+  if (mpct_eval_segment_indices(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, &o, &p, &br, &res) != MPCT_OK)
+    lib_error("mpct:eval_segment_indices");
+  const char* names[20];
+  for (int k = 0; k < 15; ++k) names[k] = kSegNames[k];
+  names[15] = "tseg";
+  names[16] = "J1";
+  names[17] = "j22";
+  names[18] = "status";
+  names[19] = "iters";
+  mxArray* R = mxCreateStructMatrix(1, 1, 20, names);
+  set_segment_fields(R, slot, &p, S, my, nu);
+  mxSetField(R, 0, "J1", out_rows(br.J1, S, my));
+  mxSetField(R, 0, "j22", out_rows(br.j22, S, my));
+  mxSetField(R, 0, "status", out_int_rows(br.status, S, 1));
+  mxArray* it = mxCreateDoubleMatrix((mwSize)S, 1, mxREAL);
+  for (long k = 0; k < S; ++k) mxGetPr(it)[k] = (double)br.qp_iters[k];
+  mxSetField(R, 0, "iters", it);
+  plhs[0] = R;
+}
+
+/* T = mpct_mex('eval_robust_segment_indices', h, N2, Nu, delta, lambda, r [, v, params]): the table of
+ * 'eval_robust_indices' with the columns (field, channel, segment); params adds fields (MPCT_SX_* ids), levels,
+ * j_bound to those of 'segment_indices' */
+static void cmd_eval_robust_segment_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 7 || nrhs > 9)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: T = mpct_mex('eval_robust_segment_indices', h, N2, Nu, delta, lambda, r [, v, params])");
+  const mxArray* po = nrhs > 8 && !mxIsEmpty(prhs[8]) ? prhs[8] : NULL;
+  const batch_args b = read_batch(nrhs, prhs, 2);
+  const int my = b.my, nu = b.nu, nit = b.nit;
+  double device;
+  const mpct_segment_params p = read_segment_params(po, &device, b.r, b.nref, my, nit);
+  int32_t all[15], *fields = all;
+  long nsel = 15, nlev = 0;
+  double* levels = NULL;
+  double j_bound = 0.0;
+  for (int k = 0; k < 15; ++k) all[k] = k;
+  if (po) {
+    const mxArray* f = mxGetField(po, 0, "fields");
+    if (f && !mxIsEmpty(f)) {
+      nsel = (long)mxGetNumberOfElements(f);
+      if (nsel > 15) mexErrMsgIdAndTxt("mpct:arg", "'fields' must hold 1 .. 15 ids (has %ld)", nsel);
+      fields = ints(f, -1, "fields");
+    }
+    levels = read_levels(mxGetField(po, 0, "levels"), &nlev);
+    j_bound = fscalar(po, "j_bound", 0.0);
+  }
+  mpct_opts o = read_opts(NULL);
+  o.device = (int32_t)device;
+  const long C = b.C;
+  const int nb = p.nseg > 0 && p.nseg <= MPCT_SEG_MAX ? p.nseg : 1;
+  int W = 0; /* an id out of range must not size anything: it counts as one column */
+  for (long q = 0; q < nsel; ++q) W += (fields[q] >= 0 && fields[q] <= 14) ? (fields[q] < 10 ? my : nu) * nb : 1;
+  const mpct_draw_stats_result res = stats_buffers(C * W, nlev);
+  mpct_robust_result base;
+  memset(&base, 0, sizeof base);
+  base.mean = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
+  base.worst = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
+  base.n_failed = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  base.worst_draw = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  base.status = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  if (mpct_eval_robust_segment_indices(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, &p, (int32_t)nsel,
+                                       fields, (int32_t)nlev, levels, &base, &res) != MPCT_OK)
+    lib_error("mpct:eval_robust_segment_indices");
+  const char* names[19];
+  names[0] = "field";
+  names[1] = "channel";
+  names[2] = "segment";
+  for (int k = 0; k < 10; ++k) names[3 + k] = kStatNames[k];
+  names[13] = "J1_mean";
+  names[14] = "J1_worst";
+  names[15] = "n_failed";
+  names[16] = "worst_draw";
+  names[17] = "status";
+  names[18] = "tseg";
+  mxArray* T = mxCreateStructMatrix(1, 1, 19, names);
+  mxArray* fa = mxCreateDoubleMatrix(1, (mwSize)W, mxREAL);
+  mxArray* ca = mxCreateDoubleMatrix(1, (mwSize)W, mxREAL);
+  mxArray* ga = mxCreateDoubleMatrix(1, (mwSize)W, mxREAL);
+  int col = 0;
+  for (long q = 0; q < nsel; ++q)
+    for (int i = 0; i < (fields[q] < 10 ? my : nu); ++i)
+      for (int g = 0; g < nb; ++g, ++col) {
+        mxGetPr(fa)[col] = fields[q];
+        mxGetPr(ca)[col] = i + 1;
+        mxGetPr(ga)[col] = g + 1;
+      }
+  mxSetField(T, 0, "field", fa);
+  mxSetField(T, 0, "channel", ca);
+  mxSetField(T, 0, "segment", ga);
+  set_stats_fields(T, &res, levels, nlev, C, W);
+  mxSetField(T, 0, "J1_mean", out_rows(base.mean, C, my));
+  mxSetField(T, 0, "J1_worst", out_rows(base.worst, C, my));
+  mxSetField(T, 0, "n_failed", out_int_rows(base.n_failed, C, 1));
+  mxSetField(T, 0, "worst_draw", out_int_rows(base.worst_draw, C, 1));
+  mxSetField(T, 0, "status", out_int_rows(base.status, C, 1));
+  mxSetField(T, 0, "tseg", out_int_rows(p.tseg, 1, p.nseg + 1));
+  plhs[0] = T;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (!g_atexit) {
     mexAtExit(destroy_all);
@@ -1332,6 +1591,14 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_eval_limit_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "eval_robust_limit_indices")) {
     cmd_eval_robust_indices(plhs, nrhs, prhs, 1);
+  } else if (!strcmp(cmd, "reference_segments")) {
+    cmd_reference_segments(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "segment_indices")) {
+    cmd_segment_indices(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "eval_segment_indices")) {
+    cmd_eval_segment_indices(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "eval_robust_segment_indices")) {
+    cmd_eval_robust_segment_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "instance")) {
     if (nrhs < 2) mexErrMsgIdAndTxt("mpct:arg", "usage: name = mpct_mex('instance', h [, opts])");
     mpct_scenario* s = handle(prhs[1]);

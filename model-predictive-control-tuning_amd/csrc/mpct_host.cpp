@@ -22,6 +22,7 @@
 #include "hypervolume_exact.h"
 #include "traj_indices.h"
 #include "limit_indices.h"
+#include "segment_indices.h"
 #include "draw_stats.h"
 
 namespace mpct {
@@ -474,7 +475,7 @@ struct CallStage {
   // the entry's words in the messages: "<entry> failed on the device", "hipMalloc failed (<staging>)",
   // "hipMemcpyAsync failed (<inputs>)", "hipMemcpyAsync failed (<results>)"
   const char *entry, *staging, *inputs, *results;
-  static constexpr int kMaxSlots = 16;  // mpct_indices, the widest entry: 3 trajectories and 13 fields
+  static constexpr int kMaxSlots = 18;  // mpct_segment_indices, the widest entry: 3 trajectories and 15 fields
   struct Slot {
     void* host;  // NULL: nothing reserved
     size_t bytes, off;
@@ -905,7 +906,7 @@ struct HostStage {
   size_t off = 0;
   size_t o_N2, o_Nu, o_d, o_l;  // the candidates' slots
   Batch dev{};                  // the candidates and signals on the device, after upload()
-  static constexpr int kMaxSlots = 23;  // mpct_eval_indices, the widest entry: an mpct_result and 13 index fields
+  static constexpr int kMaxSlots = 25;  // mpct_eval_segment_indices, the widest entry: an mpct_result and 15 fields
   struct Slot {
     void* host;  // NULL: nothing to copy back
     size_t bytes, off;
@@ -1720,15 +1721,17 @@ static int check_robust_indices(mpct_scenario* s, const Batch& b, double j_bound
 // enqueue one batch with device pointers on `stream` (ctx's device is current).  Per chunk of whole
 // candidates: the closed loops with trajectories, J1 and status into the context's index scratch, the
 // selected index records, alive[c][k], then the statistics of each selected field and the base record
-// (shared by the performance and the limit indices: ny_fields of the thirteen field ids are output-row
-// fields, int_mask has the bits of the int32 ones, records(rec, y, u, S) enqueues the chunk's reduction kernel
-// with rec[id] the selected fields' device records)
+// (shared by the performance, the limit and the segment indices: ny_fields of the up to kMaxRobustFields field
+// ids are output-row fields, a row holds per_row values of a field (the segments; else 1), int_mask has the
+// bits of the int32 ones, records(rec, y, u, S) enqueues the chunk's reduction kernel with rec[id] the
+// selected fields' device records)
+constexpr int kMaxRobustFields = 15;
 template <class Records>
 static int walk_robust_chunks(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
-                              int ny_fields, unsigned int_mask, int32_t nsel, const int32_t* fields, int32_t nlev,
+                              int ny_fields, int per_row, unsigned int_mask, int32_t nsel, const int32_t* fields, int32_t nlev,
                               const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream,
                               Records records) {
-  auto field_width = [&](const mpct_scenario* sc, int id) { return id < ny_fields ? sc->my : sc->nu; };
+  auto field_width = [&](const mpct_scenario* sc, int id) { return (id < ny_fields ? sc->my : sc->nu) * per_row; };
   auto field_is_int = [&](int id) { return (int_mask >> id & 1u) != 0; };
   if (b.C == 0) return MPCT_OK;
   const int my = s->my, nu = s->nu, nit = s->nit;
@@ -1740,7 +1743,7 @@ static int walk_robust_chunks(mpct_scenario* s, DevCtx* cx, const Batch& b, doub
   auto al = [](size_t n) { return (n + 255) & ~(size_t)255; };
   const size_t Sc = (size_t)cc * nref;
   const size_t o_j1 = al((size_t)cc * traj_bytes(nref, my, nu, nit)), o_st = o_j1 + al(Sc * my * 8), o_al = o_st + al(Sc * 4);
-  size_t o_f[13], off = o_al + al(Sc * 4);
+  size_t o_f[kMaxRobustFields], off = o_al + al(Sc * 4);
   int W = 0;
   for (int q = 0; q < nsel; ++q) {
     o_f[q] = off;
@@ -1751,7 +1754,7 @@ static int walk_robust_chunks(mpct_scenario* s, DevCtx* cx, const Batch& b, doub
   int rc = cx->index.acquire(off, stream, "trajectory scratch", &scr);
   if (rc) return rc;
   const mpct_opts o = traj_opts(opts);
-  void* rec[13] = {nullptr};
+  void* rec[kMaxRobustFields] = {nullptr};
   for (int q = 0; q < nsel; ++q) rec[fields[q]] = scr + o_f[q];
   const bool any_base = base.mean || base.worst || base.n_failed || base.worst_draw || base.status;
   std::string err;
@@ -1796,7 +1799,7 @@ static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, d
                                  const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream) {
   const unsigned ints = 1u << MPCT_IX_T_EMAX | 1u << MPCT_IX_SETTLE;
   return walk_robust_chunks(
-      s, cx, b, j_bound, opts, 8, ints, nsel, fields, nlev, levels, base, out, stream,
+      s, cx, b, j_bound, opts, 8, 1, ints, nsel, fields, nlev, levels, base, out, stream,
       [&](void* const* rec, const double* y, const double* u, int64_t S) {
         const IndexOut io{(double*)rec[0], (double*)rec[1], (double*)rec[2], (double*)rec[3],  (int*)rec[4],
                           (double*)rec[5], (double*)rec[6], (int*)rec[7],    (double*)rec[8],  (double*)rec[9],
@@ -2112,7 +2115,7 @@ static int launch_robust_limits(mpct_scenario* s, DevCtx* cx, const Batch& b, do
                                 const LimitParams& lp, int32_t nsel, const int32_t* fields, int32_t nlev,
                                 const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream) {
   return walk_robust_chunks(
-      s, cx, b, j_bound, opts, MPCT_LX_N_LO, kLimitInts, nsel, fields, nlev, levels, base, out, stream,
+      s, cx, b, j_bound, opts, MPCT_LX_N_LO, 1, kLimitInts, nsel, fields, nlev, levels, base, out, stream,
       [&](void* const* rec, const double* y, const double* u, int64_t S) {
         const LimitOut lo{(double*)rec[0], (double*)rec[1], (double*)rec[2],  (int*)rec[3],     (int*)rec[4],
                           (int*)rec[5],    (double*)rec[6], (int*)rec[7],     (int*)rec[8],     (int*)rec[9],
@@ -2159,6 +2162,318 @@ extern "C" int32_t mpct_eval_robust_limit_indices(mpct_scenario* s, int64_t C, c
   for (int q = 0; q < nsel; ++q) W += limit_width(s, fields[q]);
   return robust_stats_host(s, cx, b, W, nlev, base, out, [&](HostStage& hs, const RobustOut& ro, const DrawStatsOut& dv) {
     return launch_robust_limits(s, cx, hs.dev, j_bound, opts, lp, nsel, fields, nlev, levels, ro, dv, hs.st);
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// step-response indices per setpoint segment and their statistics over the draws (segment_indices.hip;
+// include/mpct.h)
+
+static SegOut seg_out(const mpct_segment_result* o) {
+  return SegOut{o->iae,    o->ise,  o->itae, o->emax, o->t_emax, o->over, o->under, o->e_final,
+                o->settle, o->rise, o->tv,   o->du2,  o->dumax,  o->u_lo, o->u_hi};
+}
+// the bits of the int32 fields, and the fields of an mpct_segment_result in the struct's order, each with its
+// host pointer, its width per simulation and segment and its element size
+constexpr unsigned kSegInts = 1u << MPCT_SX_T_EMAX | 1u << MPCT_SX_SETTLE | 1u << MPCT_SX_RISE;
+template <class F>
+static void each_seg_field(const mpct_segment_result& o, int my, int nu, F f) {
+  void* const host[15] = {o.iae,    o.ise,  o.itae, o.emax, o.t_emax, o.over, o.under, o.e_final,
+                          o.settle, o.rise, o.tv,   o.du2,  o.dumax,  o.u_lo, o.u_hi};
+  for (int id = 0; id < 15; ++id) f(id, host[id], id < MPCT_SX_TV ? my : nu, (kSegInts >> id & 1u) ? 4 : 8);
+}
+// the device-side record from the slots slot0 .. slot0 + 14 of a stage
+template <class Stage>
+static mpct_segment_result seg_slots(const Stage& st, int slot0) {
+  auto dd = [&](int id) { return st.template at<double>(slot0 + id); };
+  auto di = [&](int id) { return st.template at<int32_t>(slot0 + id); };
+  return mpct_segment_result{dd(0), dd(1), dd(2), dd(3), di(4), dd(5), dd(6), dd(7), di(8), di(9), dd(10), dd(11), dd(12),
+                             dd(13), dd(14)};
+}
+
+// the checks on the parameters from nseg to rise_hi, in the header's order, and the kernel's by-value parameters
+static int seg_resolve(int32_t nit, const mpct_segment_params* p, SegParams* sp) {
+  if (p->nseg < 1 || !p->tseg) return fail(MPCT_EINVAL, "nseg must be >= 1 with a boundary list tseg");
+  if (p->nseg > MPCT_SEG_MAX)
+    return fail(MPCT_ERANGE, "nseg exceeds MPCT_SEG_MAX (16): the boundaries travel in the kernel argument");
+  bool ok = p->tseg[0] >= 0 && p->tseg[p->nseg] <= nit;
+  for (int g = 0; g < p->nseg; ++g) ok = ok && p->tseg[g] < p->tseg[g + 1];
+  if (!ok) return fail(MPCT_EINVAL, "tseg must be strictly ascending with 0 <= tseg[0] and tseg[nseg] <= nit");
+  if (p->base != 0 && p->base != 1) return fail(MPCT_EINVAL, "base must be 0 or 1");
+  if (!(p->band_rel >= 0.0 && p->band_rel <= 1.7976931348623157e308 && p->band_abs >= 0.0 &&
+        p->band_abs <= 1.7976931348623157e308))
+    return fail(MPCT_EINVAL, "band_rel and band_abs must be finite and >= 0, not NaN");
+  if (!(p->rise_lo >= 0.0 && p->rise_lo <= p->rise_hi && p->rise_hi <= 1.0))  // a NaN fails a comparison
+    return fail(MPCT_EINVAL, "rise_lo and rise_hi must satisfy 0 <= rise_lo <= rise_hi <= 1");
+  *sp = SegParams{};
+  sp->nseg = p->nseg, sp->base = p->base;
+  // the unused boundaries repeat the last one: no segment of theirs exists
+  for (int g = 0; g <= kSegMax; ++g) sp->tseg[g] = p->tseg[std::min<int>(g, p->nseg)];
+  sp->band_rel = p->band_rel, sp->band_abs = p->band_abs, sp->rise_lo = p->rise_lo, sp->rise_hi = p->rise_hi;
+  return MPCT_OK;
+}
+
+static int seg_check_out(int64_t S, int32_t my, int32_t nu, int32_t nseg, const mpct_segment_result* out, bool have_y,
+                         bool have_u) {
+  if (!out) return fail(MPCT_EINVAL, "no output pointer in mpct_segment_result");
+  const SegOut so = seg_out(out);
+  if (!so.any_y() && !so.any_u()) return fail(MPCT_EINVAL, "no output pointer in mpct_segment_result");
+  if (so.any_y() && (my < 1 || (S > 0 && !have_y)))
+    return fail(MPCT_EINVAL, "an output-row field needs my >= 1 and the trajectories y and r");
+  if (so.any_u() && (nu < 1 || (S > 0 && !have_u)))
+    return fail(MPCT_EINVAL, "an input-row field needs nu >= 1 and the trajectory u");
+  // S * my <= 2^31 * 2^31 holds in int64 only below these guards: compare by division
+  if ((my > 0 && S > kIndexMaxRows / ((int64_t)my * nseg)) || (nu > 0 && S > kIndexMaxRows / ((int64_t)nu * nseg)))
+    return fail(MPCT_ERANGE, "S*my*nseg or S*nu*nseg exceeds MPCT_INDEX_MAX_ROWS");
+  return MPCT_OK;
+}
+
+static int seg_check(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my, int32_t nu,
+                     int32_t nit, const mpct_segment_params* p, const mpct_segment_result* out, SegParams* sp) {
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (S < 0 || my < 0 || nu < 0 || nit < 1) return fail(MPCT_EINVAL, "bad shape: S < 0, my < 0, nu < 0 or nit < 1");
+  if (nref < 1) return fail(MPCT_EINVAL, "nref < 1");
+  if (S % nref != 0) return fail(MPCT_EINVAL, "S must be a multiple of nref");
+  const int rc = seg_resolve(nit, p, sp);
+  if (rc) return rc;
+  return seg_check_out(S, my, nu, p->nseg, out, y && r, u != nullptr);
+}
+
+static int32_t seg_launch(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my,
+                          int32_t nu, int32_t nit, const SegParams& sp, const SegOut& so, hipStream_t stream) {
+  if (S == 0) return MPCT_OK;
+  std::string err;
+  const int rc = launch_segment_indices(y, u, r, S, nref, my, nu, nit, sp, so, stream, &err);
+  return rc ? fail(MPCT_EDEVICE, err) : MPCT_OK;
+}
+
+extern "C" int32_t mpct_reference_segments(const double* r, int32_t nref, int32_t my, int32_t nit, const int32_t* extra,
+                                           int32_t nextra, int32_t max_seg, int32_t* tseg_out, int32_t* nseg) {
+  if (!r || !tseg_out || !nseg) return fail(MPCT_EINVAL, "null pointer: r, tseg_out and nseg are needed");
+  if (nref < 1 || my < 1 || nit < 1) return fail(MPCT_EINVAL, "bad shape: nref < 1, my < 1 or nit < 1");
+  if (max_seg < 1) return fail(MPCT_EINVAL, "max_seg < 1");
+  if (nextra < 0 || (nextra > 0 && !extra)) return fail(MPCT_EINVAL, "nextra < 0, or extra samples without a list");
+  for (int k = 0; k < nextra; ++k)
+    if (extra[k] < 0 || extra[k] > nit) return fail(MPCT_EINVAL, "an extra sample lies outside [0, nit]");
+  std::vector<char> cut((size_t)nit + 1, 0);
+  cut[0] = cut[nit] = 1;
+  for (int k = 0; k < nextra; ++k) cut[extra[k]] = 1;
+  for (int64_t row = 0; row < (int64_t)nref * my; ++row) {
+    const double* rr = r + row * nit;
+    if (!std::isfinite(rr[0])) return fail(MPCT_EINVAL, "the reference holds a non-finite sample");
+    for (int t = 1; t < nit; ++t) {
+      if (!std::isfinite(rr[t])) return fail(MPCT_EINVAL, "the reference holds a non-finite sample");
+      if (rr[t] != rr[t - 1]) cut[t] = 1;
+    }
+  }
+  int64_t n = 0;
+  for (int t = 0; t <= nit; ++t) n += cut[t];
+  if (n - 1 > max_seg) return fail(MPCT_ERANGE, "the reference has more than max_seg segments");
+  int k = 0;
+  for (int t = 0; t <= nit; ++t)
+    if (cut[t]) tseg_out[k++] = t;
+  *nseg = k - 1;
+  return MPCT_OK;
+}
+
+extern "C" int32_t mpct_segment_indices_device(const double* y, const double* u, const double* r, int64_t S, int32_t nref,
+                                               int32_t my, int32_t nu, int32_t nit, const mpct_segment_params* params,
+                                               const mpct_segment_result* out, void* stream) {
+  SegParams sp;
+  const int rc = seg_check(y, u, r, S, nref, my, nu, nit, params, out, &sp);
+  if (rc) return rc;
+  return seg_launch(y, u, r, S, nref, my, nu, nit, sp, seg_out(out), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_segment_indices(const double* y, const double* u, const double* r, int64_t S, int32_t nref,
+                                        int32_t my, int32_t nu, int32_t nit, const mpct_segment_params* params,
+                                        int32_t device, const mpct_segment_result* out) {
+  SegParams sp;
+  int rc = seg_check(y, u, r, S, nref, my, nu, nit, params, out, &sp);
+  if (rc) return rc;
+  if (S == 0) return MPCT_OK;  // nothing to stage
+  const SegOut ho = seg_out(out);
+  CallStage cs{"mpct_segment_indices", "segment staging", "trajectories", "segment records"};
+  // y and r travel only behind an output-row field, u only behind an input-row field
+  const int s_y = cs.in(ho.any_y() ? y : nullptr, (size_t)S * my * nit * 8),
+            s_u = cs.in(ho.any_u() ? u : nullptr, (size_t)S * nu * nit * 8),
+            s_r = cs.in(ho.any_y() ? r : nullptr, (size_t)nref * my * nit * 8);
+  int slot0 = -1;
+  each_seg_field(*out, my, nu, [&](int, void* host, int w, int esz) {
+    const int k = cs.out(host, (size_t)S * w * sp.nseg * esz);
+    if (slot0 < 0) slot0 = k;
+  });
+  rc = cs.open(device);
+  if (rc == MPCT_OK) {
+    const mpct_segment_result dv = seg_slots(cs, slot0);
+    rc = seg_launch(cs.at<double>(s_y), cs.at<double>(s_u), cs.at<double>(s_r), S, nref, my, nu, nit, sp, seg_out(&dv), cs.st);
+  }
+  return cs.close(rc);
+}
+
+// the argument checks of the two scoring entries, in the header's order; nothing here touches a device
+static int check_eval_segments(mpct_scenario* s, const Batch& b, const mpct_opts* opts, const mpct_segment_params* p,
+                               const mpct_result* res, const mpct_segment_result* out, SegParams* sp) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the index entries are closed-loop only: open_loop must be 0");
+  if (res && (res->y || res->u || res->ys || res->uopt))
+    return fail(MPCT_EINVAL, "the trajectory pointers of res must be NULL: the trajectories stay on the device");
+  const mpct_result any{};
+  int rc = check_args(s, b, opts, &any);
+  if (rc) return rc;
+  rc = seg_resolve(s->nit, p, sp);
+  if (rc) return rc;
+  return seg_check_out(b.C * b.nref, s->my, s->nu, p->nseg, out, true, true);
+}
+
+static int launch_segments(mpct_scenario* s, DevCtx* cx, const Batch& b, const mpct_opts* opts, const SegParams& sp,
+                           const mpct_result* res, const mpct_segment_result* out, hipStream_t stream) {
+  const SegOut so = seg_out(out);
+  return walk_chunks(s, cx, b, opts, res, stream, [&](const double* y, const double* u, int64_t n, int64_t s0) {
+    return seg_launch(y, u, b.r, n * b.nref, b.nref, s->my, s->nu, s->nit, sp, so.from(s0, s->my, s->nu, sp.nseg), stream);
+  });
+}
+
+extern "C" int32_t mpct_eval_segment_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                    const double* delta, const double* lambda, int32_t nref,
+                                                    const double* r, const double* v, const mpct_opts* opts,
+                                                    const mpct_segment_params* params, mpct_result* res,
+                                                    const mpct_segment_result* out, void* stream) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  SegParams sp;
+  int rc = check_eval_segments(s, b, opts, params, res, out, &sp);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  return launch_segments(s, cx, b, opts, sp, res, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_eval_segment_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                             const double* delta, const double* lambda, int32_t nref, const double* r,
+                                             const double* v, const mpct_opts* opts, const mpct_segment_params* params,
+                                             mpct_result* res, const mpct_segment_result* out) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  SegParams sp;
+  int rc = check_eval_segments(s, b, opts, params, res, out, &sp);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  // host buffers in, the records out on the context's own stream, staged as mpct_eval_indices does: slots
+  // 0..9 the fields of `res` (its six cost fields on the device with a `res`, its trajectories never),
+  // 10..24 the segment fields that are asked for
+  const size_t S = (size_t)(C * nref);
+  HostStage hs(s, cx, C);
+  mpct_result hres = res ? *res : mpct_result{};
+  int k = 0;
+  each_field(hres, s->my, s->nu, s->nit, [&](auto* host, int64_t w) {
+    hs.keep(host, S * w * sizeof(*host), res && k < 6);
+    ++k;
+  });
+  each_seg_field(*out, s->my, s->nu, [&](int, void* host, int w, int esz) { hs.want(host, S * w * sp.nseg * esz); });
+  rc = hs.upload(s, b);
+  if (rc) return rc;
+  mpct_result dres{};
+  k = 0;
+  each_field(dres, s->my, s->nu, s->nit, [&](auto*& dev, int64_t) { hs.bind(k++, dev); });
+  const mpct_segment_result dout = seg_slots(hs, 10);
+  rc = launch_segments(s, cx, hs.dev, opts, sp, res ? &dres : nullptr, &dout, hs.st);
+  if (rc) return hs.abandon(rc);
+  return hs.finish();
+}
+
+// the argument checks of the two robust segment entries, in the header's order; nothing here touches a device
+static int check_robust_segments(mpct_scenario* s, const Batch& b, double j_bound, const mpct_opts* opts,
+                                 const mpct_segment_params* p, int32_t nsel, const int32_t* fields, int32_t nlev,
+                                 const double* levels, const mpct_robust_result* base, const mpct_draw_stats_result* out,
+                                 SegParams* sp) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the index entries are closed-loop only: open_loop must be 0");
+  if (nsel < 1 || nsel > 15 || !fields) return fail(MPCT_EINVAL, "nsel must be 1 .. 15 with a field list");
+  unsigned seen = 0;
+  for (int q = 0; q < nsel; ++q) {
+    if (fields[q] < MPCT_SX_IAE || fields[q] > MPCT_SX_U_HI) return fail(MPCT_EINVAL, "field id out of range");
+    if (seen & (1u << fields[q])) return fail(MPCT_EINVAL, "field id repeated");
+    seen |= 1u << fields[q];
+  }
+  if (b.nref < 1) return fail(MPCT_EINVAL, "nref < 1: the statistics need at least one draw");
+  if (!(j_bound >= 0.0)) return fail(MPCT_EINVAL, "j_bound must be >= 0 (0 = 1e100, +inf allowed), not negative or NaN");
+  int rc = stats_check_levels(nlev, levels);
+  if (rc) return rc;
+  const bool any_base = base && (base->mean || base->worst || base->n_failed || base->worst_draw || base->status);
+  const bool any_out = out && stats_out(out).any();
+  if (!any_base && !any_out) return fail(MPCT_EINVAL, "every output pointer of base and out is NULL");
+  if (base && base->J1) return fail(MPCT_EINVAL, "base->J1 must be NULL: the sample lives per chunk");
+  if (nlev == 0 && out && stats_out(out).any_level()) return fail(MPCT_EINVAL, "quantile, cvar and q_draw need nlev >= 1");
+  const mpct_result any{};
+  rc = check_args(s, b, opts, &any);
+  if (rc) return rc;
+  rc = seg_resolve(s->nit, p, sp);
+  if (rc) return rc;
+  if (b.nref > MPCT_TAIL_MAX_DRAWS) return fail(MPCT_ERANGE, "nref > MPCT_TAIL_MAX_DRAWS (4096): the kernel's LDS holds no more draws");
+  const int64_t S = b.C * b.nref;
+  if (S > kIndexMaxRows / ((int64_t)s->my * p->nseg) || S > kIndexMaxRows / ((int64_t)s->nu * p->nseg))
+    return fail(MPCT_ERANGE, "C*nref*my*nseg or C*nref*nu*nseg exceeds MPCT_INDEX_MAX_ROWS");
+  return MPCT_OK;
+}
+
+static int launch_robust_segments(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
+                                  const SegParams& sp, int32_t nsel, const int32_t* fields, int32_t nlev,
+                                  const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream) {
+  return walk_robust_chunks(
+      s, cx, b, j_bound, opts, MPCT_SX_TV, sp.nseg, kSegInts, nsel, fields, nlev, levels, base, out, stream,
+      [&](void* const* rec, const double* y, const double* u, int64_t S) {
+        const SegOut so{(double*)rec[0], (double*)rec[1], (double*)rec[2],  (double*)rec[3],  (int*)rec[4],
+                        (double*)rec[5], (double*)rec[6], (double*)rec[7],  (int*)rec[8],     (int*)rec[9],
+                        (double*)rec[10], (double*)rec[11], (double*)rec[12], (double*)rec[13], (double*)rec[14]};
+        return seg_launch(y, u, b.r, S, b.nref, s->my, s->nu, s->nit, sp, so, stream);
+      });
+}
+
+extern "C" int32_t mpct_eval_robust_segment_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2,
+                                                           const int32_t* Nu, const double* delta, const double* lambda,
+                                                           int32_t nref, const double* r, const double* v, double j_bound,
+                                                           const mpct_opts* opts, const mpct_segment_params* params,
+                                                           int32_t nsel, const int32_t* fields, int32_t nlev,
+                                                           const double* levels, mpct_robust_result* base,
+                                                           const mpct_draw_stats_result* out, void* stream) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  SegParams sp;
+  int rc = check_robust_segments(s, b, j_bound, opts, params, nsel, fields, nlev, levels, base, out, &sp);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  const RobustOut ro = base ? RobustOut{base->mean, base->worst, base->n_failed, base->worst_draw, base->status} : RobustOut{};
+  return launch_robust_segments(s, cx, b, j_bound, opts, sp, nsel, fields, nlev, levels, ro,
+                                out ? stats_out(out) : DrawStatsOut{}, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_eval_robust_segment_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                    const double* delta, const double* lambda, int32_t nref,
+                                                    const double* r, const double* v, double j_bound,
+                                                    const mpct_opts* opts, const mpct_segment_params* params,
+                                                    int32_t nsel, const int32_t* fields, int32_t nlev,
+                                                    const double* levels, mpct_robust_result* base,
+                                                    const mpct_draw_stats_result* out) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  SegParams sp;
+  int rc = check_robust_segments(s, b, j_bound, opts, params, nsel, fields, nlev, levels, base, out, &sp);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  size_t W = 0;
+  for (int q = 0; q < nsel; ++q) W += (size_t)(fields[q] < MPCT_SX_TV ? s->my : s->nu) * sp.nseg;
+  return robust_stats_host(s, cx, b, W, nlev, base, out, [&](HostStage& hs, const RobustOut& ro, const DrawStatsOut& dv) {
+    return launch_robust_segments(s, cx, hs.dev, j_bound, opts, sp, nsel, fields, nlev, levels, ro, dv, hs.st);
   });
 }
 

@@ -135,6 +135,23 @@ class MpctLimitResult(C.Structure):
     _fields_ = [(n, c_int32_p if i else c_double_p) for n, _, i in LIMIT_FIELDS]
 
 
+class MpctSegmentParams(C.Structure):
+    _fields_ = [("nseg", C.c_int32), ("tseg", c_int32_p), ("base", C.c_int32), ("band_rel", C.c_double),
+                ("band_abs", C.c_double), ("rise_lo", C.c_double), ("rise_hi", C.c_double)]
+
+
+# the fields of mpct_segment_result in the struct's order (their positions are MPCT_SX_*): (name, per output row?, integer?)
+SEGMENT_FIELDS = [("iae", True, False), ("ise", True, False), ("itae", True, False), ("emax", True, False),
+                  ("t_emax", True, True), ("over", True, False), ("under", True, False), ("e_final", True, False),
+                  ("settle", True, True), ("rise", True, True),
+                  ("tv", False, False), ("du2", False, False), ("dumax", False, False), ("u_lo", False, False),
+                  ("u_hi", False, False)]
+
+
+class MpctSegmentResult(C.Structure):
+    _fields_ = [(n, c_int32_p if i else c_double_p) for n, _, i in SEGMENT_FIELDS]
+
+
 class MpctRobustTail(C.Structure):
     _fields_ = [("quantile", c_double_p), ("cvar", c_double_p), ("q_draw", c_int32_p)]
 
@@ -162,6 +179,8 @@ EXPORTS = [
     "mpct_hypervolume_exact_device", "mpct_hypervolume_exact",
     "mpct_limit_indices_device", "mpct_limit_indices", "mpct_eval_limit_indices", "mpct_eval_limit_indices_device",
     "mpct_eval_robust_limit_indices", "mpct_eval_robust_limit_indices_device",
+    "mpct_reference_segments", "mpct_segment_indices_device", "mpct_segment_indices", "mpct_eval_segment_indices",
+    "mpct_eval_segment_indices_device", "mpct_eval_robust_segment_indices", "mpct_eval_robust_segment_indices_device",
 ]
 
 ABI_VERSION = 7
@@ -172,6 +191,7 @@ HVSEL_MAX_PICKS = 1024
 HVX_MAX_OBJ, HVX_MAX_M = 3, 65536
 INDEX_MAX_ROWS, INDEX_SCRATCH_BYTES = 2147483647, 268435456
 LIMIT_MAX_CH = 32
+SEG_MAX = 16
 STAT_F64, STAT_I32 = 0, 1
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
 ST_SQP_MAXITER, ST_BOUNDS, ST_NOT_RUN = 32, 64, 128
@@ -333,6 +353,26 @@ def load():
     lib.mpct_eval_robust_limit_indices.restype = C.c_int32
     lib.mpct_eval_robust_limit_indices_device.argtypes = robust_limit_args + [C.c_void_p]
     lib.mpct_eval_robust_limit_indices_device.restype = C.c_int32
+    lib.mpct_reference_segments.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_int32_p, C.c_int32, C.c_int32,
+                                            c_int32_p, c_int32_p]
+    lib.mpct_reference_segments.restype = C.c_int32
+    seg_args = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                C.POINTER(MpctSegmentParams)]
+    lib.mpct_segment_indices_device.argtypes = seg_args + [C.POINTER(MpctSegmentResult), C.c_void_p]
+    lib.mpct_segment_indices_device.restype = C.c_int32
+    lib.mpct_segment_indices.argtypes = seg_args + [C.c_int32, C.POINTER(MpctSegmentResult)]
+    lib.mpct_segment_indices.restype = C.c_int32
+    eval_seg_args = batch_args[:10] + [C.POINTER(MpctSegmentParams), C.POINTER(MpctResult), C.POINTER(MpctSegmentResult)]
+    lib.mpct_eval_segment_indices.argtypes = eval_seg_args
+    lib.mpct_eval_segment_indices.restype = C.c_int32
+    lib.mpct_eval_segment_indices_device.argtypes = eval_seg_args + [C.c_void_p]
+    lib.mpct_eval_segment_indices_device.restype = C.c_int32
+    robust_seg_args = robust_args[:11] + [C.POINTER(MpctSegmentParams), C.c_int32, c_int32_p, C.c_int32, c_double_p,
+                                          C.POINTER(MpctRobustResult), C.POINTER(MpctDrawStats)]
+    lib.mpct_eval_robust_segment_indices.argtypes = robust_seg_args
+    lib.mpct_eval_robust_segment_indices.restype = C.c_int32
+    lib.mpct_eval_robust_segment_indices_device.argtypes = robust_seg_args + [C.c_void_p]
+    lib.mpct_eval_robust_segment_indices_device.restype = C.c_int32
     # the largest grid of draw_stats_kernel in workgroups (0: the default): a test hook
     lib.mpct_internal_draw_stats_grid.argtypes = [C.c_int32]
     lib.mpct_internal_draw_stats_grid.restype = C.c_int32

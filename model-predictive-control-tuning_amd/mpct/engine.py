@@ -24,6 +24,13 @@
   eval_limit_indices_device  mpct_eval_limit_indices_device (torch CUDA tensors, enqueued on a stream)
   eval_robust_limit_indices  mpct_eval_robust_limit_indices: their statistics over the plant draws
   eval_robust_limit_indices_device  mpct_eval_robust_limit_indices_device (torch CUDA tensors, enqueued on a stream)
+  reference_segments  mpct_reference_segments: the segment boundaries of a reference (host only)
+  segment_indices     mpct_segment_indices: step-response indices per setpoint segment of stored trajectories
+  segment_indices_device  mpct_segment_indices_device (torch CUDA tensors, enqueued on the current stream)
+  eval_segment_indices  mpct_eval_segment_indices: score a batch and return only its segment records
+  eval_segment_indices_device  mpct_eval_segment_indices_device (torch CUDA tensors, enqueued on a stream)
+  eval_robust_segment_indices  mpct_eval_robust_segment_indices: their statistics over the plant draws
+  eval_robust_segment_indices_device  mpct_eval_robust_segment_indices_device (torch CUDA tensors, enqueued on a stream)
 
 No CPU fallback: every numerical result comes from the HIP kernel.
 """
@@ -1598,3 +1605,359 @@ def eval_robust_limit_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, ba
     del keep
     if rc != 0:
         raise MpctError("mpct_eval_robust_limit_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+# --------------------------------------------------------------------------------------------
+# step-response indices per setpoint segment and their statistics over the draws (mpct_reference_segments,
+# mpct_segment_indices, mpct_eval_segment_indices, mpct_eval_robust_segment_indices; include/mpct.h)
+SEGMENT_FIELDS = tuple(n for n, _, _ in _lib.SEGMENT_FIELDS)
+
+
+def reference_segments(r, extra=(), max_seg: int = _lib.SEG_MAX) -> np.ndarray:
+    """mpct_reference_segments (host only): the segment boundaries of the reference ``r`` (my, nit) or
+    (nref, my, nit) -- 0, every sample at which some row of some reference set changes, the ``extra`` event
+    samples (a measured disturbance's instant) and nit -- as the int32 vector ``tseg`` the segment entries take."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    if r.ndim == 2:
+        r = r[None]
+    if r.ndim != 3:
+        raise ValueError("r must be (my, nit) or (nref, my, nit)")
+    ex = np.ascontiguousarray(np.asarray(list(extra), dtype=np.int32))
+    tseg = np.zeros(int(max_seg) + 1, dtype=np.int32)
+    nseg = C.c_int32(0)
+    rc = _lib.load().mpct_reference_segments(r.ctypes.data, r.shape[0], r.shape[1], r.shape[2],
+                                             _ip(ex) if ex.size else None, ex.size, int(max_seg), _ip(tseg), C.byref(nseg))
+    if rc != 0:
+        raise MpctError("mpct_reference_segments failed (%d): %s" % (rc, _lib.last_error()))
+    return tseg[:nseg.value + 1].copy()
+
+
+def _segment_cost_table(get, names, tseg, segments, reduce):
+    """the fold of SegmentResult.costs: get(name) -> float array (C, rows, nseg) with NaN for no value"""
+    if reduce not in ("max", "sum"):
+        raise ValueError("reduce must be 'max' or 'sum'")
+    nseg = len(tseg) - 1
+    seg = list(range(nseg)) if segments is None else [int(g) for g in segments]
+    if any(g < 0 or g >= nseg for g in seg):
+        raise ValueError("segment out of range")
+    cols = []
+    for name in names:
+        x = get(name)[:, :, seg]
+        x = x.reshape(x.shape[0], -1)
+        # a NaN in the row makes the fold NaN (np.max and np.sum propagate it)
+        cols.append(x.max(axis=1) if reduce == "max" else x.sum(axis=1))
+    return np.stack(cols, axis=1) if cols else np.zeros((0, 0))
+
+
+@dataclass
+class SegmentResult:
+    """One array per field of mpct_segment_result: the output-row fields (C, nref, my, nseg), the input-row
+    fields (C, nref, nu, nseg); a field that was not asked for is None.  An invalid unit (a non-finite sample
+    the segment reads) holds NaN / -1."""
+    iae: np.ndarray | None = None
+    ise: np.ndarray | None = None
+    itae: np.ndarray | None = None
+    emax: np.ndarray | None = None
+    t_emax: np.ndarray | None = None     # an absolute sample
+    over: np.ndarray | None = None
+    under: np.ndarray | None = None
+    e_final: np.ndarray | None = None
+    settle: np.ndarray | None = None     # an absolute sample; tseg[g + 1] = not settled inside segment g
+    rise: np.ndarray | None = None       # tseg[g + 1] - tseg[g] = rise_hi never reached; -1 = no step (sigma = 0)
+    tv: np.ndarray | None = None
+    du2: np.ndarray | None = None
+    dumax: np.ndarray | None = None
+    u_lo: np.ndarray | None = None
+    u_hi: np.ndarray | None = None
+    tseg: np.ndarray | None = None
+    batch: EvalResult | None = None      # eval_segment_indices(want_costs=True): J1, j22, status, qp_iters of the same launch
+
+    def costs(self, names, segments=None, reduce: str = "max") -> np.ndarray:
+        """(C, len(names)) float matrix for ``pareto``: each named field folded over the references, the
+        channels and the ``segments`` (None: all) by ``reduce`` ('max' or 'sum').  ``e_final`` enters by its
+        magnitude, ``settle`` and ``t_emax`` as samples after the segment's start.  A candidate with an invalid
+        unit (NaN / -1), an unsettled segment (settle = its end) or a step that never reaches ``rise_hi``
+        (rise = the segment's length) gets NaN in that column: invalid for ``pareto``, last for ``rank``.  A
+        ``rise`` of -1 where the unit is valid (no step on that channel in that segment) takes no part in the
+        fold; a candidate without any step gets NaN."""
+        tseg = np.asarray(self.tseg)
+        a, b = tseg[:-1].astype(float), tseg[1:].astype(float)
+
+        def get(name):
+            if name not in SEGMENT_FIELDS:
+                raise ValueError("unknown segment field %r" % (name,))
+            arr = getattr(self, name)
+            if arr is None:
+                raise ValueError("this result has no %s" % name)
+            arr = np.asarray(arr)
+            x = arr.reshape(arr.shape[0], -1, arr.shape[-1]).astype(float)
+            if name in ("settle", "t_emax"):
+                bad = x < 0
+                if name == "settle":
+                    bad |= x >= b
+                x = np.where(bad, np.nan, x - a)
+            elif name == "rise":
+                if self.settle is None and self.t_emax is None:
+                    valid = np.ones(x.shape, dtype=bool)     # nothing tells an invalid unit from "no step"
+                else:
+                    other = np.asarray(self.settle if self.settle is not None else self.t_emax)
+                    valid = other.reshape(x.shape) >= 0
+                none = (x < 0) & valid
+                x = np.where((x < 0) & ~valid, np.nan, np.where(x >= b - a, np.nan, x))
+                # no step here: neutral in the fold, NaN where the candidate has no step at all
+                x = np.where(none, -np.inf if reduce == "max" else 0.0, x)
+                x = np.where(none.all(axis=(1, 2), keepdims=True), np.nan, x)
+            elif name == "e_final":
+                x = np.abs(x)
+            return x
+
+        return _segment_cost_table(get, names, tseg, segments, reduce)
+
+
+def _segment_fields(fields):
+    fields = SEGMENT_FIELDS if fields is None else tuple(fields)
+    for f in fields:
+        if f not in SEGMENT_FIELDS:
+            raise ValueError("unknown segment field %r" % (f,))
+    return fields
+
+
+def _segment_params(tseg, base, band_rel, band_abs, rise_lo, rise_hi):
+    """The MpctSegmentParams of a call and the host boundary vector it points to (keep it alive for the call)."""
+    t = np.ascontiguousarray(np.asarray(tseg, dtype=np.int32).reshape(-1))
+    if t.size < 2:
+        raise ValueError("tseg needs at least two boundaries")
+    p = _lib.MpctSegmentParams(t.size - 1, _ip(t), int(base), float(band_rel), float(band_abs), float(rise_lo),
+                               float(rise_hi))
+    return p, t
+
+
+def _segment_result(Cn, nref, my, nu, tseg, fields):
+    """A SegmentResult with the arrays of ``fields`` and the MpctSegmentResult that points into them."""
+    nseg = len(tseg) - 1
+    res = SegmentResult(tseg=np.array(tseg, dtype=np.int32))
+    r = _lib.MpctSegmentResult()
+    for name, is_y, is_int in _lib.SEGMENT_FIELDS:
+        if name in fields:
+            a = np.zeros((Cn, nref, my if is_y else nu, nseg), dtype=np.int32 if is_int else np.float64)
+            setattr(res, name, a)
+            setattr(r, name, _ip(a) if is_int else _dp(a))
+    return res, r
+
+
+def _segment_struct(out: dict):
+    r = _lib.MpctSegmentResult()
+    for name, _, is_int in _lib.SEGMENT_FIELDS:
+        setattr(r, name, _tptr(out.get(name), _lib.c_int32_p if is_int else _lib.c_double_p))
+    return r
+
+
+def segment_indices(y, u, r, tseg, base=1, band_rel=0.02, band_abs=0.0, rise_lo=0.1, rise_hi=0.9, fields=None,
+                    device=-1) -> SegmentResult:
+    """mpct_segment_indices: the step-response indices per setpoint segment of stored trajectories, reduced on
+    the GPU (host arrays in and out).  ``y`` (S, my, nit), ``u`` (S, nu, nit), ``r`` (nref, my, nit); simulation
+    s reads reference set s % nref; ``tseg`` the nseg + 1 boundaries (``reference_segments``).  ``y`` and ``r``
+    may be None when ``fields`` names no output-row field, ``u`` when it names no input-row field.  The arrays
+    of the result are (S / nref, nref, my, nseg) and (S / nref, nref, nu, nseg)."""
+    y = None if y is None else np.ascontiguousarray(y, dtype=np.float64)
+    u = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
+    r = None if r is None else np.ascontiguousarray(r, dtype=np.float64)
+    if (y is not None and y.ndim != 3) or (u is not None and u.ndim != 3) or (r is not None and r.ndim != 3):
+        raise ValueError("y, u and r must be 3-d: (S, my, nit), (S, nu, nit), (nref, my, nit)")
+    if y is None and u is None:
+        raise ValueError("y or u is needed")
+    some = y if y is not None else u
+    S, nit = some.shape[0], some.shape[2]
+    my = y.shape[1] if y is not None else 0
+    nu = u.shape[1] if u is not None else 0
+    nref = r.shape[0] if r is not None else 1
+    if (u is not None and u.shape[::2] != (S, nit)) or (r is not None and y is not None and r.shape[1:] != (my, nit)):
+        raise ValueError("y, u and r disagree on S, my or nit")
+    if fields is None:
+        fields = tuple(n for n, is_y, _ in _lib.SEGMENT_FIELDS if (y if is_y else u) is not None)
+    fields = _segment_fields(fields)
+    if S % nref:
+        raise ValueError("S must be a multiple of nref")
+    p, t = _segment_params(tseg, base, band_rel, band_abs, rise_lo, rise_hi)
+    res, out = _segment_result(S // nref, nref, my, nu, t, fields)
+    ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+    rc = _lib.load().mpct_segment_indices(ptr(y), ptr(u), ptr(r), S, nref, my, nu, nit, C.byref(p), int(device),
+                                          C.byref(out))
+    if rc != 0:
+        raise MpctError("mpct_segment_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return res
+
+
+def segment_indices_device(y, u, r, out: dict, tseg, base=1, band_rel=0.02, band_abs=0.0, rise_lo=0.1, rise_hi=0.9):
+    """mpct_segment_indices_device: ``y`` [S, my, nit], ``u`` [S, nu, nit], ``r`` [nref, my, nit] are contiguous
+    float64 CUDA (HIP) tensors (None where no field needs them), ``tseg`` a HOST sequence; the records are
+    written into the tensors of ``out`` (keys as the fields of SegmentResult: float64 / int32, [S, my, nseg] or
+    [S, nu, nseg]; any may be absent).  Enqueued on the current torch stream of the tensors' device and not
+    synchronised."""
+    import torch
+
+    some = y if y is not None else u
+    for t in (y, u, r):
+        if t is not None and (t.dtype != torch.float64 or t.dim() != 3 or not t.is_contiguous()):
+            raise ValueError("y, u and r must be contiguous float64 tensors with three dimensions")
+    S, nit = some.shape[0], some.shape[2]
+    my = y.shape[1] if y is not None else 0
+    nu = u.shape[1] if u is not None else 0
+    nref = r.shape[0] if r is not None else 1
+    p, keep = _segment_params(tseg, base, band_rel, band_abs, rise_lo, rise_hi)
+    o = _segment_struct(out)
+    stream = torch.cuda.current_stream(some.device).cuda_stream
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(some.device):
+        rc = _lib.load().mpct_segment_indices_device(ptr(y), ptr(u), ptr(r), S, nref, my, nu, nit, C.byref(p), C.byref(o),
+                                                     C.c_void_p(stream))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_segment_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+def eval_segment_indices(sc, N2, Nu, delta, lam, refs, v=None, tseg=None, extra=(), base=1, band_rel=0.02, band_abs=0.0,
+                         rise_lo=0.1, rise_hi=0.9, fields=None, want_costs=False, device=-1, max_qp_iter=0,
+                         feas_tol=0.0) -> SegmentResult:
+    """mpct_eval_segment_indices: score C candidates against nref reference sets and return only the segment
+    records of the closed loops (host arrays in and out); the trajectories stay on the device.  ``tseg``
+    defaults to ``reference_segments(refs, extra)``.  ``want_costs`` adds ``batch``: J1, j22, status and
+    qp_iters of the same launch, as eval_batch returns them."""
+    fields = _segment_fields(fields)
+    N2, Nu, delta, lam, refs, Cn, nref, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    if tseg is None:
+        tseg = reference_segments(refs, extra)
+    p, t = _segment_params(tseg, base, band_rel, band_abs, rise_lo, rise_hi)
+    res, out = _segment_result(Cn, nref, sc.my, sc.nu, t, fields)
+    br = None
+    if want_costs:
+        res.batch, br = _eval_result(sc, Cn * nref, nref, False, False)
+    o = _opts(False, False, device, max_qp_iter, feas_tol)
+    rc = sc.lib.mpct_eval_segment_indices(sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data,
+                                          lam.ctypes.data, nref, refs.ctypes.data, vv.ctypes.data if vv is not None else None,
+                                          C.byref(o), C.byref(p), C.byref(br) if br is not None else None, C.byref(out))
+    if rc != 0:
+        raise MpctError("mpct_eval_segment_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return res
+
+
+def eval_segment_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, tseg, v=None, base=1, band_rel=0.02,
+                                band_abs=0.0, rise_lo=0.1, rise_hi=0.9, device=-1, stream=None):
+    """Device-pointer entry of eval_segment_indices: every argument is a CUDA (HIP) torch tensor (``tseg`` is a
+    HOST sequence); the records are written into the tensors of ``out`` (the keys of segment_indices_device,
+    [C * nref, my, nseg] / [C * nref, nu, nseg], plus the optional J1, j21, j22, Jnu, status, qp_iters of
+    eval_batch_device).  Enqueued on ``stream`` (torch stream; default: current) and not synchronised."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    br = _lib.MpctResult()
+    br.J1, br.j21 = _tptr(out.get("J1"), _lib.c_double_p), _tptr(out.get("j21"), _lib.c_double_p)
+    br.j22, br.Jnu = _tptr(out.get("j22"), _lib.c_double_p), _tptr(out.get("Jnu"), _lib.c_double_p)
+    br.status, br.qp_iters = _tptr(out.get("status"), _lib.c_int32_p), _tptr(out.get("qp_iters"), _lib.c_int64_p)
+    p, keep = _segment_params(tseg, base, band_rel, band_abs, rise_lo, rise_hi)
+    o = _opts(False, False, device)
+    so = _segment_struct(out)
+    rc = sc.lib.mpct_eval_segment_indices_device(
+        sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+        C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+        C.c_void_p(v.data_ptr()) if v is not None else None, C.byref(o), C.byref(p), C.byref(br), C.byref(so),
+        C.c_void_p(stream.cuda_stream))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_eval_segment_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+@dataclass
+class RobustSegmentResult(RobustIndexResult):
+    """RobustIndexResult for the segment indices: ``columns`` names the W columns as (field name, channel,
+    segment) in selection order, an output-row field contributing my * nseg columns and an input-row field
+    nu * nseg; ``tseg`` the boundaries."""
+    tseg: np.ndarray | None = None
+
+    def costs(self, stat="hi", names=None, segments=None, max_failed: int = 0) -> np.ndarray:
+        """(C, k) cost table for ``pareto``: the statistic ``stat`` (as RobustIndexResult.costs) of the columns
+        whose field is in ``names`` (None: every field) and whose segment is in ``segments`` (None: every
+        segment), in selection order.  NaN for every candidate with more than ``max_failed`` failed draws."""
+        cols, self.columns = self.columns, [(f, (ch, g)) for f, ch, g in self.columns]
+        try:
+            tab = RobustIndexResult.costs(self, stat, None, max_failed)
+        finally:
+            self.columns = cols
+        if names is not None:
+            for nm in names:
+                if not any(f == nm for f, _, _ in cols):
+                    raise ValueError("this result has no field %r" % (nm,))
+        seg = None if segments is None else set(int(g) for g in segments)
+        order = [k for nm in (names if names is not None else dict.fromkeys(f for f, _, _ in cols))
+                 for k, (f, _, g) in enumerate(cols) if f == nm and (seg is None or g in seg)]
+        return tab[:, order]
+
+
+def _segment_field_ids(sc, fields, nseg):
+    """The MPCT_SX_* ids of the selected fields as the int32 vector the library reads, and the (field, channel,
+    segment) columns."""
+    fields = _segment_fields(fields)
+    ids = np.ascontiguousarray([SEGMENT_FIELDS.index(f) for f in fields], dtype=np.int32)
+    is_y = {n: y for n, y, _ in _lib.SEGMENT_FIELDS}
+    cols = [(f, ch, g) for f in fields for ch in range(sc.my if is_y[f] else sc.nu) for g in range(nseg)]
+    return ids, cols
+
+
+def eval_robust_segment_indices(sc, N2, Nu, delta, lam, refs, v=None, tseg=None, extra=(), fields=None, levels=None,
+                                j_bound=0.0, base=1, band_rel=0.02, band_abs=0.0, rise_lo=0.1, rise_hi=0.9, device=-1,
+                                max_qp_iter=0, feas_tol=0.0) -> RobustSegmentResult:
+    """mpct_eval_robust_segment_indices: score C candidates over the D = len(refs) draws and reduce, on the
+    device, the segment indices ``fields`` (default: all fifteen) of the C x D closed loops to per-candidate
+    statistics over the surviving draws (host arrays in and out): eval_robust_indices per segment.  A draw
+    without a value in a column (an invalid unit, or a rise of -1: no step) does not enter that column.
+    ``base`` here is the base-level rule of the segments; the robust J1 record is the result's ``.base``."""
+    N2, Nu, delta, lam, refs, Cn, D, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    if tseg is None:
+        tseg = reference_segments(refs, extra)
+    p, t = _segment_params(tseg, base, band_rel, band_abs, rise_lo, rise_hi)
+    ids, cols = _segment_field_ids(sc, fields, t.size - 1)
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    arr, out = _stats_arrays(Cn, len(cols), nlev)
+    rb = RobustResult(mean=np.zeros((Cn, sc.my)), worst=np.zeros((Cn, sc.my)), n_failed=np.zeros(Cn, dtype=np.int32),
+                      worst_draw=np.zeros(Cn, dtype=np.int32), status=np.zeros(Cn, dtype=np.int32), draws=D)
+    br = _lib.MpctRobustResult()
+    br.mean, br.worst = _dp(rb.mean), _dp(rb.worst)
+    br.n_failed, br.worst_draw, br.status = _ip(rb.n_failed), _ip(rb.worst_draw), _ip(rb.status)
+    o = _opts(False, False, device, max_qp_iter, feas_tol)
+    rc = sc.lib.mpct_eval_robust_segment_indices(
+        sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data, lam.ctypes.data, D, refs.ctypes.data,
+        vv.ctypes.data if vv is not None else None, float(j_bound), C.byref(o), C.byref(p), ids.size, _ip(ids), nlev,
+        _dp(lv) if nlev else None, C.byref(br), C.byref(out))
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_segment_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return RobustSegmentResult(columns=cols, levels=lv, base=rb, tseg=t.copy(), **arr)
+
+
+def eval_robust_segment_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, tseg, base_out: dict | None = None, v=None,
+                                       fields=None, levels=None, j_bound=0.0, base=1, band_rel=0.02, band_abs=0.0,
+                                       rise_lo=0.1, rise_hi=0.9, device=-1, stream=None):
+    """Device-pointer entry of eval_robust_segment_indices: every argument is a CUDA (HIP) torch tensor
+    (``tseg``, ``fields`` and ``levels`` are HOST sequences); ``out`` as in eval_robust_indices_device, and
+    ``base_out`` its ``base`` (the tensors of the robust J1 record).  Enqueued on ``stream`` (torch stream;
+    default: current) and not synchronised."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    p, keep = _segment_params(tseg, base, band_rel, band_abs, rise_lo, rise_hi)
+    ids, _ = _segment_field_ids(sc, fields, keep.size - 1)
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    br = _robust_struct(base_out or {})
+    o = _opts(False, False, device)
+    so = _stats_struct(out)
+    rc = sc.lib.mpct_eval_robust_segment_indices_device(
+        sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+        C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+        C.c_void_p(v.data_ptr()) if v is not None else None, float(j_bound), C.byref(o), C.byref(p), ids.size, _ip(ids),
+        nlev, _dp(lv) if nlev else None, C.byref(br), C.byref(so), C.c_void_p(stream.cuda_stream))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_segment_indices_device failed (%d): %s" % (rc, _lib.last_error()))
