@@ -39,7 +39,10 @@
  *     mpct_eval_robust_limit_indices_device), and the step-response indices per setpoint segment
  *     (mpct_segment_params, mpct_segment_result, mpct_reference_segments, mpct_segment_indices_device,
  *     mpct_segment_indices, mpct_eval_segment_indices, mpct_eval_segment_indices_device,
- *     mpct_eval_robust_segment_indices, mpct_eval_robust_segment_indices_device).
+ *     mpct_eval_robust_segment_indices, mpct_eval_robust_segment_indices_device), and the oscillation
+ *     indices per setpoint segment (mpct_osc_params, mpct_osc_result, mpct_osc_indices_device,
+ *     mpct_osc_indices, mpct_eval_osc_indices, mpct_eval_osc_indices_device, mpct_eval_robust_osc_indices,
+ *     mpct_eval_robust_osc_indices_device).
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -1409,6 +1412,167 @@ int32_t mpct_eval_robust_segment_indices_device(mpct_scenario* s, int64_t C, con
                                                 int32_t nsel, const int32_t* fields, int32_t nlev,
                                                 const double* levels, mpct_robust_result* base,
                                                 const mpct_draw_stats_result* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Oscillation indices per setpoint segment, reduced on the device from the trajectories
+ * (osc_indices.hip).  The segment indices above say how far, how long and how late a closed
+ * loop misses its target; none of them says whether it RINGS.  One clean overshoot that dies and a lightly
+ * damped loop that crosses its setpoint six times can share `over`, `settle` and much of `iae`.  These entries
+ * count the band crossings of each output in each segment, give the decay ratio and the period of its first two
+ * peaks on one side and the peak of its last lobe, and count the direction reversals of each input (the valve
+ * wear figure beside tv).
+ *
+ * Segments.  Exactly those of mpct_segment_params: nseg in [1, MPCT_SEG_MAX]; tseg[nseg+1] is a HOST pointer to
+ * strictly ascending int32 with 0 <= tseg[0] and tseg[nseg] <= nit.  Segment g covers the samples a <= t < b
+ * with a = tseg[g], b = tseg[g+1].  mpct_reference_segments gives the boundaries of a reference; they travel to
+ * the kernel by value in its argument.  Nothing before tseg[0] or from tseg[nseg] on is ever read.
+ *
+ * Trajectories in mpct_result's layout: y[S][my][nit], u[S][nu][nit], r[nref][my][nit]; simulation s reads
+ * reference set s % nref (S is a multiple of nref).
+ *
+ * Output row (s, i), segment g.  r_g = r(b-1), the base level c (segment 0: y(a); later: y(a) with base = 0,
+ * r(a-1) with base = 1), d = r_g - c and sigma = sign(d) exactly as in the segment indices.  x(t) = y(t) - r_g
+ * is measured against the segment's final level, not against r(t).  h = band_rel*|d| + band_abs, the product
+ * rounded before the sum.  The STATE of a sample is +1 if x(t) > h, -1 if x(t) < -h, else INSIDE (|x| == h is
+ * inside).  Walk the OUTSIDE samples in ascending t:
+ *   - a CROSSING is an outside sample whose state differs from that of the previous outside sample, however
+ *     many inside samples lie between them; the first outside sample is no crossing;
+ *   - LOBE k (k = 0, 1, ..) is the set of outside samples after the k-th crossing and before the (k+1)-th (lobe
+ *     0: before the first), A_k the largest |x| in lobe k, T_k the first t that attains A_k.
+ * k0 = 1 when sigma != 0 (lobe 0 is then the approach to the new level), k0 = 0 otherwise (a disturbance or a
+ * hold: lobe 0 is the first excursion).
+ *   ncross   the number of crossings
+ *   decay    A_{k0+2} / A_{k0}, one IEEE division, when ncross >= k0 + 2; else +0.0 (no second peak on the same
+ *            side left the band)
+ *   period   T_{k0+2} - T_{k0} when ncross >= k0 + 2; else -1
+ *   a_last   A_ncross, the peak of the last lobe, when ncross >= k0; else +0.0; +0.0 as well when no sample
+ *            is outside (an empty lobe has no peak).  A loop whose a_last is near A_{k0} oscillates undamped;
+ *            above it, it grows
+ * Input row (s, n), segment g, with the moves du(t) = u(t) - u(t-1) for t in [max(a, tseg[0]+1), b), the range
+ * of the segment indices (the move across a boundary belongs to the segment it starts).  The state of a move
+ * is +1 if du > rev_tol, -1 if du < -rev_tol, else inside:
+ *   nmove    the number of outside moves
+ *   nrev     the number of crossings among the outside moves, as above: the direction reversals
+ *   t_rev    the sample t of the last reversing move; -1 when nrev = 0
+ *
+ * Layout.  Element (row*nseg + g) of each array: output fields [S][my][nseg], input fields [S][nu][nseg].
+ *
+ * Validity.  The unit is one (row, segment).  It is INVALID when any sample it reads is non-finite.  An output
+ * unit reads y in [a, b), r(b-1), and r(a-1) where base = 1 uses it (g >= 1); no other sample of r: x does
+ * not involve r(t).  An input unit reads u in [a, b), and u(a-1) for g >= 1.  An invalid unit gives NaN in its
+ * doubles and -1 in its integers; no other unit is affected, the other segments of the same row included.
+ *
+ * Exact; no contraction.  Every field is an exact integer or a bit-exact double: the doubles are maxima of |x|
+ * and one division; there is no sum, so no summation order.  band_rel*|d| is rounded to double before band_abs
+ * is added: no fused multiply-add.  -0.0 counts as +0.0 in every comparison (rev_tol = 0: a move of +-0.0 is
+ * inside).  A repeated call is bitwise identical and a record does not depend on the simulation's place in the
+ * batch.
+ *
+ * Any result pointer may be NULL, but not all of them.  y and r may be NULL when no output-row field is
+ * requested, u when no input-row field is.  Only the requested arrays are written.
+ *
+ * Argument errors, in this order and before any device is touched:
+ *   MPCT_EINVAL  params NULL; S < 0, my < 0, nu < 0 or nit < 1
+ *   MPCT_EINVAL  nref < 1
+ *   MPCT_EINVAL  S not a multiple of nref
+ *   MPCT_EINVAL  nseg < 1 or tseg NULL
+ *   MPCT_ERANGE  nseg > MPCT_SEG_MAX (the boundaries travel in the kernel argument)
+ *   MPCT_EINVAL  tseg[0] < 0, tseg[nseg] > nit, or tseg not strictly ascending
+ *   MPCT_EINVAL  base neither 0 nor 1
+ *   MPCT_EINVAL  band_rel or band_abs negative, infinite or NaN
+ *   MPCT_EINVAL  rev_tol negative, infinite or NaN
+ *   MPCT_EINVAL  out NULL, or all seven of its pointers NULL
+ *   MPCT_EINVAL  an output-row field with my < 1, or (S > 0) with y or r NULL; an input-row field with
+ *                nu < 1, or (S > 0) with u NULL
+ *   MPCT_ERANGE  S*my*nseg or S*nu*nseg > MPCT_INDEX_MAX_ROWS (one wave per row and segment)
+ * S = 0 is MPCT_OK and writes nothing. */
+typedef struct mpct_osc_params {
+  int32_t nseg;        /* 1 .. MPCT_SEG_MAX */
+  const int32_t* tseg; /* [nseg+1] HOST, strictly ascending, 0 <= tseg[0], tseg[nseg] <= nit */
+  int32_t base;        /* base level of segments g >= 1: 0 = y(a), 1 = r(a-1) */
+  double band_rel;     /* band around r_g relative to the step size |d| */
+  double band_abs;     /* plus an absolute band; both finite and >= 0 */
+  double rev_tol;      /* dead zone of a move: |du| <= rev_tol is no move; finite and >= 0 */
+} mpct_osc_params;
+
+typedef struct mpct_osc_result {
+  int32_t* ncross;  /* [S*my*nseg] */
+  double* decay;    /* [S*my*nseg] */
+  int32_t* period;  /* [S*my*nseg] */
+  double* a_last;   /* [S*my*nseg] */
+  int32_t* nmove;   /* [S*nu*nseg] */
+  int32_t* nrev;    /* [S*nu*nseg] */
+  int32_t* t_rev;   /* [S*nu*nseg] */
+} mpct_osc_result;
+
+/* the field ids of mpct_eval_robust_osc_indices, in the member order of mpct_osc_result */
+#define MPCT_OX_NCROSS 0
+#define MPCT_OX_DECAY 1
+#define MPCT_OX_PERIOD 2
+#define MPCT_OX_A_LAST 3
+#define MPCT_OX_NMOVE 4
+#define MPCT_OX_NREV 5
+#define MPCT_OX_T_REV 6
+
+/* y, u, r and the pointers of `out` DEVICE pointers (params and its tseg HOST, read before the call returns);
+ * enqueued on `stream` (NULL = default stream) and NOT synchronised.  Needs no scenario and no scratch: one
+ * kernel launch. */
+int32_t mpct_osc_indices_device(const double* y, const double* u, const double* r, int64_t S, int32_t nref,
+                                int32_t my, int32_t nu, int32_t nit, const mpct_osc_params* params,
+                                const mpct_osc_result* out, void* stream);
+
+/* Host pointers (MATLAB and C callers), for trajectories from any source: the staging, device and stream
+ * rules of mpct_segment_indices.  Without a device: MPCT_EDEVICE with a message. */
+int32_t mpct_osc_indices(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my,
+                         int32_t nu, int32_t nit, const mpct_osc_params* params, int32_t device,
+                         const mpct_osc_result* out);
+
+/* Score a batch and return only the oscillation records (host pointers; arguments as
+ * mpct_eval_segment_indices, whose chunking, scratch, `res` and `opts` rules hold unchanged): S = C*nref
+ * simulations, output fields [S*my*nseg], input fields [S*nu*nseg]; the reference sets of the indices are the
+ * call's r.  Every record is bitwise independent of the chunk size.
+ * MPCT_EINVAL, in this order and before any device is touched: s NULL; params NULL; open_loop set; a
+ * trajectory pointer in res; then everything mpct_eval_batch rejects; then the checks of
+ * mpct_osc_indices_device from nseg on, nit the scenario's.  C = 0 is MPCT_OK and writes nothing.  Without a
+ * device: MPCT_EDEVICE with a message. */
+int32_t mpct_eval_osc_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
+                              const double* lambda, int32_t nref, const double* r, const double* v,
+                              const mpct_opts* opts, const mpct_osc_params* params, mpct_result* res,
+                              const mpct_osc_result* out);
+
+/* Same, all pointers DEVICE pointers (res's and out's included; params and its tseg HOST), enqueued on
+ * `stream` (NULL = default stream) and NOT synchronised: the contract of mpct_eval_segment_indices_device. */
+int32_t mpct_eval_osc_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                     const double* delta, const double* lambda, int32_t nref, const double* r,
+                                     const double* v, const mpct_opts* opts, const mpct_osc_params* params,
+                                     mpct_result* res, const mpct_osc_result* out, void* stream);
+
+/* Score C candidates x D = nref draws and return, per candidate, the statistics over the draws of the
+ * selected oscillation indices: the arguments and semantics of mpct_eval_robust_segment_indices with
+ * mpct_osc_params in place of mpct_segment_params and `fields` drawn from MPCT_OX_NCROSS .. MPCT_OX_T_REV
+ * (1 <= nsel <= 7).  A selected output-row field contributes my*nseg columns (channel i, segment g at
+ * i*nseg + g), an input-row field nu*nseg.  ncross, period, nmove, nrev and t_rev enter the statistics as
+ * MPCT_STAT_I32, so a period or a t_rev of -1 is a draw without a value; decay and a_last as MPCT_STAT_F64.
+ * The worst decay and the upper quantiles of ncross over the draws stand beside the worst overshoot.
+ * Errors, in this order and before any device is touched: those of mpct_eval_robust_indices up to and
+ * including everything mpct_eval_batch rejects; then the checks of mpct_osc_indices_device from nseg up to
+ * rev_tol; then MPCT_ERANGE for nref > MPCT_TAIL_MAX_DRAWS, and for C*nref*my*nseg or C*nref*nu*nseg >
+ * MPCT_INDEX_MAX_ROWS.  C = 0 is MPCT_OK and writes nothing. */
+int32_t mpct_eval_robust_osc_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                     const double* delta, const double* lambda, int32_t nref, const double* r,
+                                     const double* v, double j_bound, const mpct_opts* opts,
+                                     const mpct_osc_params* params, int32_t nsel, const int32_t* fields,
+                                     int32_t nlev, const double* levels, mpct_robust_result* base,
+                                     const mpct_draw_stats_result* out);
+
+/* Same, all pointers DEVICE pointers except params with its tseg, fields and levels; enqueued on `stream`
+ * and NOT synchronised: the contract of mpct_eval_robust_indices_device. */
+int32_t mpct_eval_robust_osc_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                            const double* delta, const double* lambda, int32_t nref, const double* r,
+                                            const double* v, double j_bound, const mpct_opts* opts,
+                                            const mpct_osc_params* params, int32_t nsel, const int32_t* fields,
+                                            int32_t nlev, const double* levels, mpct_robust_result* base,
+                                            const mpct_draw_stats_result* out, void* stream);
 
 #ifdef __cplusplus
 }

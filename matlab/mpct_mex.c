@@ -90,6 +90,11 @@
  *                                                    the same for a scored batch, boundaries of r by default
  *   T = mpct_mex('eval_robust_segment_indices', h, N2, Nu, delta, lambda, r, v, params)
  *                                                    their statistics over the D pages of r
+ *   O = mpct_mex('osc_indices', y, u, r, params)     oscillation indices per setpoint segment of stored trajectories
+ *   O = mpct_mex('eval_osc_indices', h, N2, Nu, delta, lambda, r, v, params)
+ *                                                    the same for a scored batch, boundaries of r by default
+ *   T = mpct_mex('eval_robust_osc_indices', h, N2, Nu, delta, lambda, r, v, params)
+ *                                                    their statistics over the D pages of r
  *   T = mpct_mex('eval_robust_indices', h, N2, Nu, delta, lambda, r, v, params)
  *                                                    statistics of the performance indices over the D pages of r
  *                                                    (mpct_eval_robust_indices).  params (optional struct): fields
@@ -1545,6 +1550,208 @@ static void cmd_eval_robust_segment_indices(mxArray* plhs[], int nrhs, const mxA
   plhs[0] = T;
 }
 
+/* ---- oscillation indices per setpoint segment (mpct_osc_indices, mpct_eval_osc_indices,
+ * mpct_eval_robust_osc_indices; include/mpct.h) */
+#define OSC_NF 7 /* fields; the first OSC_NY per output row */
+#define OSC_NY 4
+static const char* const kOscNames[OSC_NF] = {"ncross", "decay", "period", "a_last", "nmove", "nrev", "t_rev"};
+static const int kOscIsInt[OSC_NF] = {1, 0, 1, 0, 1, 1, 1};
+
+/* params struct (all fields optional): tseg, extra, base, band_rel, band_abs and device as for 'segment_indices',
+ * and rev_tol (0), the dead zone of a move */
+static mpct_osc_params read_osc_params(const mxArray* o, double* device, const double* rr, int nref, int my, int nit) {
+  const mpct_segment_params s = read_segment_params(o, device, rr, nref, my, nit);
+  mpct_osc_params p;
+  memset(&p, 0, sizeof p);
+  p.nseg = s.nseg, p.tseg = s.tseg, p.base = s.base, p.band_rel = s.band_rel, p.band_abs = s.band_abs;
+  p.rev_tol = o ? fscalar(o, "rev_tol", 0.0) : 0.0;
+  return p;
+}
+
+static mpct_osc_result osc_buffers(long S, int my, int nu, int nseg, int with_y, int with_u, void* slot[OSC_NF]) {
+  mpct_osc_result r;
+  memset(&r, 0, sizeof r);
+  void** f[OSC_NF] = {(void**)&r.ncross, (void**)&r.decay, (void**)&r.period, (void**)&r.a_last,
+                      (void**)&r.nmove,  (void**)&r.nrev,  (void**)&r.t_rev};
+  for (int k = 0; k < OSC_NF; ++k) {
+    slot[k] = NULL;
+    if (k < OSC_NY ? with_y : with_u)
+      slot[k] = *f[k] = mxCalloc((size_t)(S * (k < OSC_NY ? my : nu) * nseg + 1), kOscIsInt[k] ? sizeof(int32_t) : sizeof(double));
+  }
+  return r;
+}
+
+/* the seven fields into struct R in the layout of set_segment_fields; then tseg (1 x (nseg + 1), 0-based) */
+static void set_osc_fields(mxArray* R, void* const slot[OSC_NF], const mpct_osc_params* p, long S, int my, int nu) {
+  for (int k = 0; k < OSC_NF; ++k) {
+    const int w = (k < OSC_NY ? my : nu) * p->nseg;
+    mxArray* a;
+    if (!slot[k]) a = mxCreateDoubleMatrix(0, 0, mxREAL);
+    else if (kOscIsInt[k]) a = out_int_rows((const int32_t*)slot[k], S, w);
+    else a = out_rows((const double*)slot[k], S, w);
+    mxSetField(R, 0, kOscNames[k], a);
+  }
+  mxSetField(R, 0, "tseg", out_int_rows(p->tseg, 1, p->nseg + 1));
+}
+
+/* O = mpct_mex('osc_indices', y, u, r [, params]): the layouts of 'segment_indices'; t_rev and tseg are the library's
+ * 0-based samples */
+static void cmd_osc_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 4 || nrhs > 5) mexErrMsgIdAndTxt("mpct:arg", "usage: O = mpct_mex('osc_indices', y, u, r [, params])");
+  int my, nity, nu, nitu, myr, nitr;
+  long Sy, Su, nref;
+  signal_dims(prhs[1], "y", &my, &nity, &Sy);
+  signal_dims(prhs[2], "u", &nu, &nitu, &Su);
+  signal_dims(prhs[3], "r", &myr, &nitr, &nref);
+  const int with_y = Sy > 0, with_u = Su > 0;
+  if (!with_y && !with_u) mexErrMsgIdAndTxt("mpct:arg", "'y' and 'u' are both empty");
+  if (with_y && (nref < 1 || myr != my || nitr != nity)) mexErrMsgIdAndTxt("mpct:arg", "'r' must be my x nit x nref like 'y'");
+  if (with_y && with_u && (Sy != Su || nity != nitu)) mexErrMsgIdAndTxt("mpct:arg", "'y' and 'u' must agree on nit and S");
+  const long S = with_y ? Sy : Su;
+  const int nit = with_y ? nity : nitu;
+  if (!with_y) nref = 1;
+  if (S > 2147483647L || nref > 2147483647L) mexErrMsgIdAndTxt("mpct:arg", "too many pages");
+  int pg = 0;
+  double* y = with_y ? signals(prhs[1], my, nit, &pg, "y") : NULL;
+  pg = 0;
+  double* u = with_u ? signals(prhs[2], nu, nit, &pg, "u") : NULL;
+  pg = 0;
+  double* r = with_y ? signals(prhs[3], my, nit, &pg, "r") : NULL;
+  double device;
+  const mpct_osc_params p = read_osc_params(nrhs > 4 && !mxIsEmpty(prhs[4]) ? prhs[4] : NULL, &device, r, (int)nref, my, nit);
+  void* slot[OSC_NF];
+  const int nb = p.nseg > 0 && p.nseg <= MPCT_SEG_MAX ? p.nseg : 1; /* a bad count sizes nothing: the library rejects it */
+  const mpct_osc_result res = osc_buffers(S, my, nu, nb, with_y, with_u, slot);
+  if (mpct_osc_indices(y, u, r, S, (int32_t)nref, my, nu, nit, &p, (int32_t)device, &res) != MPCT_OK)
+    lib_error("mpct:osc_indices");
+  const char* names[OSC_NF + 1];
+  for (int k = 0; k < OSC_NF; ++k) names[k] = kOscNames[k];
+  names[OSC_NF] = "tseg";
+  mxArray* R = mxCreateStructMatrix(1, 1, OSC_NF + 1, names);
+  set_osc_fields(R, slot, &p, S, my, nu);
+  plhs[0] = R;
+}
+
+/* O = mpct_mex('eval_osc_indices', h, N2, Nu, delta, lambda, r [, v, params]): the seven fields and tseg plus J1, j22
+ * (S x my), status and iters (S x 1) of the same launch */
+static void cmd_eval_osc_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 7 || nrhs > 9)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: O = mpct_mex('eval_osc_indices', h, N2, Nu, delta, lambda, r [, v, params])");
+  const batch_args b = read_batch(nrhs, prhs, 2);
+  const int my = b.my, nu = b.nu, nit = b.nit;
+  double device;
+  const mpct_osc_params p = read_osc_params(nrhs > 8 && !mxIsEmpty(prhs[8]) ? prhs[8] : NULL, &device, b.r, b.nref, my, nit);
+  mpct_opts o = read_opts(NULL);
+  o.device = (int32_t)device;
+  const long C = b.C, S = C * b.nref;
+  void* slot[OSC_NF];
+  const int nb = p.nseg > 0 && p.nseg <= MPCT_SEG_MAX ? p.nseg : 1;
+  const mpct_osc_result res = osc_buffers(S, my, nu, nb, 1, 1, slot);
+  mpct_result br;
+  memset(&br, 0, sizeof br);
+  br.J1 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
+  br.j22 = (double*)mxCalloc((size_t)(S * my + 1), sizeof(double));
+  br.status = (int32_t*)mxCalloc((size_t)(S + 1), sizeof(int32_t));
+  br.qp_iters = (int64_t*)mxCalloc((size_t)(S + 1), sizeof(int64_t));
+  if (mpct_eval_osc_indices(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, &o, &p, &br, &res) != MPCT_OK)
+    lib_error("mpct:eval_osc_indices");
+  const char* names[OSC_NF + 5];
+  for (int k = 0; k < OSC_NF; ++k) names[k] = kOscNames[k];
+  names[OSC_NF] = "tseg";
+  names[OSC_NF + 1] = "J1";
+  names[OSC_NF + 2] = "j22";
+  names[OSC_NF + 3] = "status";
+  names[OSC_NF + 4] = "iters";
+  mxArray* R = mxCreateStructMatrix(1, 1, OSC_NF + 5, names);
+  set_osc_fields(R, slot, &p, S, my, nu);
+  mxSetField(R, 0, "J1", out_rows(br.J1, S, my));
+  mxSetField(R, 0, "j22", out_rows(br.j22, S, my));
+  mxSetField(R, 0, "status", out_int_rows(br.status, S, 1));
+  mxArray* it = mxCreateDoubleMatrix((mwSize)S, 1, mxREAL);
+  for (long k = 0; k < S; ++k) mxGetPr(it)[k] = (double)br.qp_iters[k];
+  mxSetField(R, 0, "iters", it);
+  plhs[0] = R;
+}
+
+/* T = mpct_mex('eval_robust_osc_indices', h, N2, Nu, delta, lambda, r [, v, params]): the table of
+ * 'eval_robust_segment_indices' with the columns (field, channel, segment); params adds fields (MPCT_OX_* ids),
+ * levels, j_bound to those of 'osc_indices' */
+static void cmd_eval_robust_osc_indices(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 7 || nrhs > 9)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: T = mpct_mex('eval_robust_osc_indices', h, N2, Nu, delta, lambda, r [, v, params])");
+  const mxArray* po = nrhs > 8 && !mxIsEmpty(prhs[8]) ? prhs[8] : NULL;
+  const batch_args b = read_batch(nrhs, prhs, 2);
+  const int my = b.my, nu = b.nu, nit = b.nit;
+  double device;
+  const mpct_osc_params p = read_osc_params(po, &device, b.r, b.nref, my, nit);
+  int32_t all[OSC_NF], *fields = all;
+  long nsel = OSC_NF, nlev = 0;
+  double* levels = NULL;
+  double j_bound = 0.0;
+  for (int k = 0; k < OSC_NF; ++k) all[k] = k;
+  if (po) {
+    const mxArray* f = mxGetField(po, 0, "fields");
+    if (f && !mxIsEmpty(f)) {
+      nsel = (long)mxGetNumberOfElements(f);
+      if (nsel > OSC_NF) mexErrMsgIdAndTxt("mpct:arg", "'fields' must hold 1 .. 7 ids (has %ld)", nsel);
+      fields = ints(f, -1, "fields");
+    }
+    levels = read_levels(mxGetField(po, 0, "levels"), &nlev);
+    j_bound = fscalar(po, "j_bound", 0.0);
+  }
+  mpct_opts o = read_opts(NULL);
+  o.device = (int32_t)device;
+  const long C = b.C;
+  const int nb = p.nseg > 0 && p.nseg <= MPCT_SEG_MAX ? p.nseg : 1;
+  int W = 0; /* an id out of range must not size anything: it counts as one column */
+  for (long q = 0; q < nsel; ++q) W += (fields[q] >= 0 && fields[q] < OSC_NF) ? (fields[q] < OSC_NY ? my : nu) * nb : 1;
+  const mpct_draw_stats_result res = stats_buffers(C * W, nlev);
+  mpct_robust_result base;
+  memset(&base, 0, sizeof base);
+  base.mean = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
+  base.worst = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
+  base.n_failed = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  base.worst_draw = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  base.status = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  if (mpct_eval_robust_osc_indices(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, &p, (int32_t)nsel,
+                                   fields, (int32_t)nlev, levels, &base, &res) != MPCT_OK)
+    lib_error("mpct:eval_robust_osc_indices");
+  const char* names[19];
+  names[0] = "field";
+  names[1] = "channel";
+  names[2] = "segment";
+  for (int k = 0; k < 10; ++k) names[3 + k] = kStatNames[k];
+  names[13] = "J1_mean";
+  names[14] = "J1_worst";
+  names[15] = "n_failed";
+  names[16] = "worst_draw";
+  names[17] = "status";
+  names[18] = "tseg";
+  mxArray* T = mxCreateStructMatrix(1, 1, 19, names);
+  mxArray* fa = mxCreateDoubleMatrix(1, (mwSize)W, mxREAL);
+  mxArray* ca = mxCreateDoubleMatrix(1, (mwSize)W, mxREAL);
+  mxArray* ga = mxCreateDoubleMatrix(1, (mwSize)W, mxREAL);
+  int col = 0;
+  for (long q = 0; q < nsel; ++q)
+    for (int i = 0; i < (fields[q] < OSC_NY ? my : nu); ++i)
+      for (int g = 0; g < nb; ++g, ++col) {
+        mxGetPr(fa)[col] = fields[q];
+        mxGetPr(ca)[col] = i + 1;
+        mxGetPr(ga)[col] = g + 1;
+      }
+  mxSetField(T, 0, "field", fa);
+  mxSetField(T, 0, "channel", ca);
+  mxSetField(T, 0, "segment", ga);
+  set_stats_fields(T, &res, levels, nlev, C, W);
+  mxSetField(T, 0, "J1_mean", out_rows(base.mean, C, my));
+  mxSetField(T, 0, "J1_worst", out_rows(base.worst, C, my));
+  mxSetField(T, 0, "n_failed", out_int_rows(base.n_failed, C, 1));
+  mxSetField(T, 0, "worst_draw", out_int_rows(base.worst_draw, C, 1));
+  mxSetField(T, 0, "status", out_int_rows(base.status, C, 1));
+  mxSetField(T, 0, "tseg", out_int_rows(p.tseg, 1, p.nseg + 1));
+  plhs[0] = T;
+}
+
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (!g_atexit) {
     mexAtExit(destroy_all);
@@ -1599,6 +1806,12 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_eval_segment_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "eval_robust_segment_indices")) {
     cmd_eval_robust_segment_indices(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "osc_indices")) {
+    cmd_osc_indices(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "eval_osc_indices")) {
+    cmd_eval_osc_indices(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "eval_robust_osc_indices")) {
+    cmd_eval_robust_osc_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "instance")) {
     if (nrhs < 2) mexErrMsgIdAndTxt("mpct:arg", "usage: name = mpct_mex('instance', h [, opts])");
     mpct_scenario* s = handle(prhs[1]);

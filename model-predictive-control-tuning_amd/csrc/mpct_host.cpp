@@ -22,6 +22,7 @@
 #include "hypervolume_exact.h"
 #include "traj_indices.h"
 #include "limit_indices.h"
+#include "osc_indices.h"
 #include "segment_indices.h"
 #include "draw_stats.h"
 
@@ -2474,6 +2475,278 @@ extern "C" int32_t mpct_eval_robust_segment_indices(mpct_scenario* s, int64_t C,
   for (int q = 0; q < nsel; ++q) W += (size_t)(fields[q] < MPCT_SX_TV ? s->my : s->nu) * sp.nseg;
   return robust_stats_host(s, cx, b, W, nlev, base, out, [&](HostStage& hs, const RobustOut& ro, const DrawStatsOut& dv) {
     return launch_robust_segments(s, cx, hs.dev, j_bound, opts, sp, nsel, fields, nlev, levels, ro, dv, hs.st);
+  });
+}
+
+// ------------------------------------------------------------------------------------------
+// oscillation indices per setpoint segment and their statistics over the draws (osc_indices.hip;
+// include/mpct.h): the segment family's entries with mpct_osc_params and seven fields
+
+static OscOut osc_out(const mpct_osc_result* o) {
+  return OscOut{o->ncross, o->decay, o->period, o->a_last, o->nmove, o->nrev, o->t_rev};
+}
+// the bits of the int32 fields, and the fields of an mpct_osc_result in the struct's order, each with its host
+// pointer, its width per simulation and segment and its element size
+constexpr int kOscFields = 7;
+constexpr unsigned kOscInts =
+    1u << MPCT_OX_NCROSS | 1u << MPCT_OX_PERIOD | 1u << MPCT_OX_NMOVE | 1u << MPCT_OX_NREV | 1u << MPCT_OX_T_REV;
+template <class F>
+static void each_osc_field(const mpct_osc_result& o, int my, int nu, F f) {
+  void* const host[kOscFields] = {o.ncross, o.decay, o.period, o.a_last, o.nmove, o.nrev, o.t_rev};
+  for (int id = 0; id < kOscFields; ++id) f(id, host[id], id < MPCT_OX_NMOVE ? my : nu, (kOscInts >> id & 1u) ? 4 : 8);
+}
+// the device-side record from the slots slot0 .. slot0 + 6 of a stage
+template <class Stage>
+static mpct_osc_result osc_slots(const Stage& st, int slot0) {
+  auto dd = [&](int id) { return st.template at<double>(slot0 + id); };
+  auto di = [&](int id) { return st.template at<int32_t>(slot0 + id); };
+  return mpct_osc_result{di(0), dd(1), di(2), dd(3), di(4), di(5), di(6)};
+}
+
+// the checks on the parameters from nseg to rev_tol, in the header's order, and the kernel's by-value
+// parameters.  The boundaries, the base rule and the band are the segment family's: seg_resolve checks them, with
+// rise levels that always pass
+static int osc_resolve(int32_t nit, const mpct_osc_params* p, OscParams* op) {
+  const mpct_segment_params as_seg{p->nseg, p->tseg, p->base, p->band_rel, p->band_abs, 0.0, 1.0};
+  SegParams sp;
+  const int rc = seg_resolve(nit, &as_seg, &sp);
+  if (rc) return rc;
+  if (!(p->rev_tol >= 0.0 && p->rev_tol <= 1.7976931348623157e308))
+    return fail(MPCT_EINVAL, "rev_tol must be finite and >= 0, not NaN");
+  *op = OscParams{};
+  op->nseg = sp.nseg, op->base = sp.base;
+  for (int g = 0; g <= kSegMax; ++g) op->tseg[g] = sp.tseg[g];
+  op->band_rel = sp.band_rel, op->band_abs = sp.band_abs, op->rev_tol = p->rev_tol;
+  return MPCT_OK;
+}
+
+static int osc_check_out(int64_t S, int32_t my, int32_t nu, int32_t nseg, const mpct_osc_result* out, bool have_y,
+                         bool have_u) {
+  if (!out) return fail(MPCT_EINVAL, "no output pointer in mpct_osc_result");
+  const OscOut oo = osc_out(out);
+  if (!oo.any_y() && !oo.any_u()) return fail(MPCT_EINVAL, "no output pointer in mpct_osc_result");
+  if (oo.any_y() && (my < 1 || (S > 0 && !have_y)))
+    return fail(MPCT_EINVAL, "an output-row field needs my >= 1 and the trajectories y and r");
+  if (oo.any_u() && (nu < 1 || (S > 0 && !have_u)))
+    return fail(MPCT_EINVAL, "an input-row field needs nu >= 1 and the trajectory u");
+  // S * my <= 2^31 * 2^31 holds in int64 only below these guards: compare by division
+  if ((my > 0 && S > kIndexMaxRows / ((int64_t)my * nseg)) || (nu > 0 && S > kIndexMaxRows / ((int64_t)nu * nseg)))
+    return fail(MPCT_ERANGE, "S*my*nseg or S*nu*nseg exceeds MPCT_INDEX_MAX_ROWS");
+  return MPCT_OK;
+}
+
+static int osc_check(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my, int32_t nu,
+                     int32_t nit, const mpct_osc_params* p, const mpct_osc_result* out, OscParams* op) {
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (S < 0 || my < 0 || nu < 0 || nit < 1) return fail(MPCT_EINVAL, "bad shape: S < 0, my < 0, nu < 0 or nit < 1");
+  if (nref < 1) return fail(MPCT_EINVAL, "nref < 1");
+  if (S % nref != 0) return fail(MPCT_EINVAL, "S must be a multiple of nref");
+  const int rc = osc_resolve(nit, p, op);
+  if (rc) return rc;
+  return osc_check_out(S, my, nu, p->nseg, out, y && r, u != nullptr);
+}
+
+static int32_t osc_launch(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my,
+                          int32_t nu, int32_t nit, const OscParams& op, const OscOut& oo, hipStream_t stream) {
+  if (S == 0) return MPCT_OK;
+  std::string err;
+  const int rc = launch_osc_indices(y, u, r, S, nref, my, nu, nit, op, oo, stream, &err);
+  return rc ? fail(MPCT_EDEVICE, err) : MPCT_OK;
+}
+
+extern "C" int32_t mpct_osc_indices_device(const double* y, const double* u, const double* r, int64_t S, int32_t nref,
+                                           int32_t my, int32_t nu, int32_t nit, const mpct_osc_params* params,
+                                           const mpct_osc_result* out, void* stream) {
+  OscParams op;
+  const int rc = osc_check(y, u, r, S, nref, my, nu, nit, params, out, &op);
+  if (rc) return rc;
+  return osc_launch(y, u, r, S, nref, my, nu, nit, op, osc_out(out), static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_osc_indices(const double* y, const double* u, const double* r, int64_t S, int32_t nref, int32_t my,
+                                    int32_t nu, int32_t nit, const mpct_osc_params* params, int32_t device,
+                                    const mpct_osc_result* out) {
+  OscParams op;
+  int rc = osc_check(y, u, r, S, nref, my, nu, nit, params, out, &op);
+  if (rc) return rc;
+  if (S == 0) return MPCT_OK;  // nothing to stage
+  const OscOut ho = osc_out(out);
+  CallStage cs{"mpct_osc_indices", "oscillation staging", "trajectories", "oscillation records"};
+  // y and r travel only behind an output-row field, u only behind an input-row field
+  const int s_y = cs.in(ho.any_y() ? y : nullptr, (size_t)S * my * nit * 8),
+            s_u = cs.in(ho.any_u() ? u : nullptr, (size_t)S * nu * nit * 8),
+            s_r = cs.in(ho.any_y() ? r : nullptr, (size_t)nref * my * nit * 8);
+  int slot0 = -1;
+  each_osc_field(*out, my, nu, [&](int, void* host, int w, int esz) {
+    const int k = cs.out(host, (size_t)S * w * op.nseg * esz);
+    if (slot0 < 0) slot0 = k;
+  });
+  rc = cs.open(device);
+  if (rc == MPCT_OK) {
+    const mpct_osc_result dv = osc_slots(cs, slot0);
+    rc = osc_launch(cs.at<double>(s_y), cs.at<double>(s_u), cs.at<double>(s_r), S, nref, my, nu, nit, op, osc_out(&dv), cs.st);
+  }
+  return cs.close(rc);
+}
+
+// the argument checks of the two scoring entries, in the header's order; nothing here touches a device
+static int check_eval_osc(mpct_scenario* s, const Batch& b, const mpct_opts* opts, const mpct_osc_params* p,
+                          const mpct_result* res, const mpct_osc_result* out, OscParams* op) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the index entries are closed-loop only: open_loop must be 0");
+  if (res && (res->y || res->u || res->ys || res->uopt))
+    return fail(MPCT_EINVAL, "the trajectory pointers of res must be NULL: the trajectories stay on the device");
+  const mpct_result any{};
+  int rc = check_args(s, b, opts, &any);
+  if (rc) return rc;
+  rc = osc_resolve(s->nit, p, op);
+  if (rc) return rc;
+  return osc_check_out(b.C * b.nref, s->my, s->nu, p->nseg, out, true, true);
+}
+
+static int launch_osc(mpct_scenario* s, DevCtx* cx, const Batch& b, const mpct_opts* opts, const OscParams& op,
+                      const mpct_result* res, const mpct_osc_result* out, hipStream_t stream) {
+  const OscOut oo = osc_out(out);
+  return walk_chunks(s, cx, b, opts, res, stream, [&](const double* y, const double* u, int64_t n, int64_t s0) {
+    return osc_launch(y, u, b.r, n * b.nref, b.nref, s->my, s->nu, s->nit, op, oo.from(s0, s->my, s->nu, op.nseg), stream);
+  });
+}
+
+extern "C" int32_t mpct_eval_osc_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                const double* delta, const double* lambda, int32_t nref, const double* r,
+                                                const double* v, const mpct_opts* opts, const mpct_osc_params* params,
+                                                mpct_result* res, const mpct_osc_result* out, void* stream) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  OscParams op;
+  int rc = check_eval_osc(s, b, opts, params, res, out, &op);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  return launch_osc(s, cx, b, opts, op, res, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_eval_osc_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                         const double* delta, const double* lambda, int32_t nref, const double* r,
+                                         const double* v, const mpct_opts* opts, const mpct_osc_params* params,
+                                         mpct_result* res, const mpct_osc_result* out) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  OscParams op;
+  int rc = check_eval_osc(s, b, opts, params, res, out, &op);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  // staged as mpct_eval_segment_indices does: slots 0..9 the fields of `res`, 10..16 the oscillation fields
+  // that are asked for
+  const size_t S = (size_t)(C * nref);
+  HostStage hs(s, cx, C);
+  mpct_result hres = res ? *res : mpct_result{};
+  int k = 0;
+  each_field(hres, s->my, s->nu, s->nit, [&](auto* host, int64_t w) {
+    hs.keep(host, S * w * sizeof(*host), res && k < 6);
+    ++k;
+  });
+  each_osc_field(*out, s->my, s->nu, [&](int, void* host, int w, int esz) { hs.want(host, S * w * op.nseg * esz); });
+  rc = hs.upload(s, b);
+  if (rc) return rc;
+  mpct_result dres{};
+  k = 0;
+  each_field(dres, s->my, s->nu, s->nit, [&](auto*& dev, int64_t) { hs.bind(k++, dev); });
+  const mpct_osc_result dout = osc_slots(hs, 10);
+  rc = launch_osc(s, cx, hs.dev, opts, op, res ? &dres : nullptr, &dout, hs.st);
+  if (rc) return hs.abandon(rc);
+  return hs.finish();
+}
+
+// the argument checks of the two robust oscillation entries, in the header's order; nothing here touches a device
+static int check_robust_osc(mpct_scenario* s, const Batch& b, double j_bound, const mpct_opts* opts,
+                            const mpct_osc_params* p, int32_t nsel, const int32_t* fields, int32_t nlev,
+                            const double* levels, const mpct_robust_result* base, const mpct_draw_stats_result* out,
+                            OscParams* op) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (!p) return fail(MPCT_EINVAL, "null params");
+  if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the index entries are closed-loop only: open_loop must be 0");
+  if (nsel < 1 || nsel > kOscFields || !fields) return fail(MPCT_EINVAL, "nsel must be 1 .. 7 with a field list");
+  unsigned seen = 0;
+  for (int q = 0; q < nsel; ++q) {
+    if (fields[q] < MPCT_OX_NCROSS || fields[q] > MPCT_OX_T_REV) return fail(MPCT_EINVAL, "field id out of range");
+    if (seen & (1u << fields[q])) return fail(MPCT_EINVAL, "field id repeated");
+    seen |= 1u << fields[q];
+  }
+  if (b.nref < 1) return fail(MPCT_EINVAL, "nref < 1: the statistics need at least one draw");
+  if (!(j_bound >= 0.0)) return fail(MPCT_EINVAL, "j_bound must be >= 0 (0 = 1e100, +inf allowed), not negative or NaN");
+  int rc = stats_check_levels(nlev, levels);
+  if (rc) return rc;
+  const bool any_base = base && (base->mean || base->worst || base->n_failed || base->worst_draw || base->status);
+  const bool any_out = out && stats_out(out).any();
+  if (!any_base && !any_out) return fail(MPCT_EINVAL, "every output pointer of base and out is NULL");
+  if (base && base->J1) return fail(MPCT_EINVAL, "base->J1 must be NULL: the sample lives per chunk");
+  if (nlev == 0 && out && stats_out(out).any_level()) return fail(MPCT_EINVAL, "quantile, cvar and q_draw need nlev >= 1");
+  const mpct_result any{};
+  rc = check_args(s, b, opts, &any);
+  if (rc) return rc;
+  rc = osc_resolve(s->nit, p, op);
+  if (rc) return rc;
+  if (b.nref > MPCT_TAIL_MAX_DRAWS) return fail(MPCT_ERANGE, "nref > MPCT_TAIL_MAX_DRAWS (4096): the kernel's LDS holds no more draws");
+  const int64_t S = b.C * b.nref;
+  if (S > kIndexMaxRows / ((int64_t)s->my * p->nseg) || S > kIndexMaxRows / ((int64_t)s->nu * p->nseg))
+    return fail(MPCT_ERANGE, "C*nref*my*nseg or C*nref*nu*nseg exceeds MPCT_INDEX_MAX_ROWS");
+  return MPCT_OK;
+}
+
+static int launch_robust_osc(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
+                             const OscParams& op, int32_t nsel, const int32_t* fields, int32_t nlev, const double* levels,
+                             const RobustOut& base, const DrawStatsOut& out, hipStream_t stream) {
+  return walk_robust_chunks(s, cx, b, j_bound, opts, MPCT_OX_NMOVE, op.nseg, kOscInts, nsel, fields, nlev, levels, base, out,
+                            stream, [&](void* const* rec, const double* y, const double* u, int64_t S) {
+                              const OscOut oo{(int*)rec[0], (double*)rec[1], (int*)rec[2], (double*)rec[3],
+                                              (int*)rec[4], (int*)rec[5],    (int*)rec[6]};
+                              return osc_launch(y, u, b.r, S, b.nref, s->my, s->nu, s->nit, op, oo, stream);
+                            });
+}
+
+extern "C" int32_t mpct_eval_robust_osc_indices_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                       const double* delta, const double* lambda, int32_t nref,
+                                                       const double* r, const double* v, double j_bound,
+                                                       const mpct_opts* opts, const mpct_osc_params* params, int32_t nsel,
+                                                       const int32_t* fields, int32_t nlev, const double* levels,
+                                                       mpct_robust_result* base, const mpct_draw_stats_result* out,
+                                                       void* stream) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  OscParams op;
+  int rc = check_robust_osc(s, b, j_bound, opts, params, nsel, fields, nlev, levels, base, out, &op);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  const RobustOut ro = base ? RobustOut{base->mean, base->worst, base->n_failed, base->worst_draw, base->status} : RobustOut{};
+  return launch_robust_osc(s, cx, b, j_bound, opts, op, nsel, fields, nlev, levels, ro, out ? stats_out(out) : DrawStatsOut{},
+                           static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_eval_robust_osc_indices(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                const double* delta, const double* lambda, int32_t nref, const double* r,
+                                                const double* v, double j_bound, const mpct_opts* opts,
+                                                const mpct_osc_params* params, int32_t nsel, const int32_t* fields,
+                                                int32_t nlev, const double* levels, mpct_robust_result* base,
+                                                const mpct_draw_stats_result* out) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  OscParams op;
+  int rc = check_robust_osc(s, b, j_bound, opts, params, nsel, fields, nlev, levels, base, out, &op);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  size_t W = 0;
+  for (int q = 0; q < nsel; ++q) W += (size_t)(fields[q] < MPCT_OX_NMOVE ? s->my : s->nu) * op.nseg;
+  return robust_stats_host(s, cx, b, W, nlev, base, out, [&](HostStage& hs, const RobustOut& ro, const DrawStatsOut& dv) {
+    return launch_robust_osc(s, cx, hs.dev, j_bound, opts, op, nsel, fields, nlev, levels, ro, dv, hs.st);
   });
 }
 

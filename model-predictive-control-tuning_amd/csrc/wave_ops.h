@@ -1,5 +1,5 @@
 // wave_ops.h — one-wavefront building blocks shared by the closed-loop kernels (gpc_kernel.hip,
-// mdband_kernel.hip): LDS hand-off fence, readlane broadcast, DPP / permlane reductions over the
+// mdband_kernel.hip): LDS hand-off fence, readlane broadcast, lane masks, DPP / permlane reductions over the
 // QP-row lanes, lane shifts and the per-MV-block prefix sum.  Every helper is force-inlined: the
 // kernels rely on lds_sync() (lgkmcnt only), which is only correct when no helper is outlined
 // into a FLAT-addressed call (checked on the ISA by __graft_entry__.kernel_isa()).
@@ -51,6 +51,11 @@ __device__ __forceinline__ double bcast(double v, int src) {
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
   return __hiloint2double(hi, lo);
 }
+
+// 64-bit lane masks beside __ballot: the lanes below `lane`, and the highest set bit of a non-zero mask
+// (osc_indices.hip orders the events of a block with them)
+__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
+__device__ __forceinline__ int top_bit(unsigned long long m) { return 63 - __clzll((long long)m); }
 
 // DPP moves.  Controls whose every lane has a source within its row (quad_perm, row_mirror,
 // row_half_mirror, row_newbcast) use v_mov_b32_dpp without an `old` operand: the update_dpp(0, ..)

@@ -152,6 +152,20 @@ class MpctSegmentResult(C.Structure):
     _fields_ = [(n, c_int32_p if i else c_double_p) for n, _, i in SEGMENT_FIELDS]
 
 
+class MpctOscParams(C.Structure):
+    _fields_ = [("nseg", C.c_int32), ("tseg", c_int32_p), ("base", C.c_int32), ("band_rel", C.c_double),
+                ("band_abs", C.c_double), ("rev_tol", C.c_double)]
+
+
+# the fields of mpct_osc_result in the struct's order (their positions are MPCT_OX_*): (name, per output row?, integer?)
+OSC_FIELDS = [("ncross", True, True), ("decay", True, False), ("period", True, True), ("a_last", True, False),
+              ("nmove", False, True), ("nrev", False, True), ("t_rev", False, True)]
+
+
+class MpctOscResult(C.Structure):
+    _fields_ = [(n, c_int32_p if i else c_double_p) for n, _, i in OSC_FIELDS]
+
+
 class MpctRobustTail(C.Structure):
     _fields_ = [("quantile", c_double_p), ("cvar", c_double_p), ("q_draw", c_int32_p)]
 
@@ -181,6 +195,8 @@ EXPORTS = [
     "mpct_eval_robust_limit_indices", "mpct_eval_robust_limit_indices_device",
     "mpct_reference_segments", "mpct_segment_indices_device", "mpct_segment_indices", "mpct_eval_segment_indices",
     "mpct_eval_segment_indices_device", "mpct_eval_robust_segment_indices", "mpct_eval_robust_segment_indices_device",
+    "mpct_osc_indices_device", "mpct_osc_indices", "mpct_eval_osc_indices", "mpct_eval_osc_indices_device",
+    "mpct_eval_robust_osc_indices", "mpct_eval_robust_osc_indices_device",
 ]
 
 ABI_VERSION = 7
@@ -373,6 +389,22 @@ def load():
     lib.mpct_eval_robust_segment_indices.restype = C.c_int32
     lib.mpct_eval_robust_segment_indices_device.argtypes = robust_seg_args + [C.c_void_p]
     lib.mpct_eval_robust_segment_indices_device.restype = C.c_int32
+    osc_args = seg_args[:8] + [C.POINTER(MpctOscParams)]
+    lib.mpct_osc_indices_device.argtypes = osc_args + [C.POINTER(MpctOscResult), C.c_void_p]
+    lib.mpct_osc_indices_device.restype = C.c_int32
+    lib.mpct_osc_indices.argtypes = osc_args + [C.c_int32, C.POINTER(MpctOscResult)]
+    lib.mpct_osc_indices.restype = C.c_int32
+    eval_osc_args = batch_args[:10] + [C.POINTER(MpctOscParams), C.POINTER(MpctResult), C.POINTER(MpctOscResult)]
+    lib.mpct_eval_osc_indices.argtypes = eval_osc_args
+    lib.mpct_eval_osc_indices.restype = C.c_int32
+    lib.mpct_eval_osc_indices_device.argtypes = eval_osc_args + [C.c_void_p]
+    lib.mpct_eval_osc_indices_device.restype = C.c_int32
+    robust_osc_args = robust_args[:11] + [C.POINTER(MpctOscParams), C.c_int32, c_int32_p, C.c_int32, c_double_p,
+                                          C.POINTER(MpctRobustResult), C.POINTER(MpctDrawStats)]
+    lib.mpct_eval_robust_osc_indices.argtypes = robust_osc_args
+    lib.mpct_eval_robust_osc_indices.restype = C.c_int32
+    lib.mpct_eval_robust_osc_indices_device.argtypes = robust_osc_args + [C.c_void_p]
+    lib.mpct_eval_robust_osc_indices_device.restype = C.c_int32
     # the largest grid of draw_stats_kernel in workgroups (0: the default): a test hook
     lib.mpct_internal_draw_stats_grid.argtypes = [C.c_int32]
     lib.mpct_internal_draw_stats_grid.restype = C.c_int32

@@ -1961,3 +1961,268 @@ def eval_robust_segment_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, 
     del keep
     if rc != 0:
         raise MpctError("mpct_eval_robust_segment_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+# --------------------------------------------------------------------------------------------
+# oscillation indices per setpoint segment and their statistics over the draws (mpct_osc_indices,
+# mpct_eval_osc_indices, mpct_eval_robust_osc_indices; include/mpct.h)
+OSC_FIELDS = tuple(n for n, _, _ in _lib.OSC_FIELDS)
+
+
+@dataclass
+class OscResult:
+    """One array per field of mpct_osc_result: the output-row fields (C, nref, my, nseg), the input-row fields
+    (C, nref, nu, nseg); a field that was not asked for is None.  An invalid unit (a non-finite sample the
+    segment reads) holds NaN / -1."""
+    ncross: np.ndarray | None = None     # band crossings of the output in the segment
+    decay: np.ndarray | None = None      # A_{k0+2} / A_{k0}; +0.0 = no second peak on the same side
+    period: np.ndarray | None = None     # T_{k0+2} - T_{k0} in samples; -1 = no second peak on the same side
+    a_last: np.ndarray | None = None     # the peak of the last lobe
+    nmove: np.ndarray | None = None      # moves outside the dead zone rev_tol
+    nrev: np.ndarray | None = None       # direction reversals among them
+    t_rev: np.ndarray | None = None      # an absolute sample; -1 = no reversal
+    tseg: np.ndarray | None = None
+    batch: EvalResult | None = None      # eval_osc_indices(want_costs=True): J1, j22, status, qp_iters of the same launch
+
+    def costs(self, names, segments=None, reduce: str = "max") -> np.ndarray:
+        """(C, len(names)) float matrix for ``pareto``: each named field folded over the references, the
+        channels and the ``segments`` (None: all) by ``reduce`` ('max' or 'sum').  The integer fields enter as
+        floats, ``t_rev`` as samples after the segment's start.  A candidate with an invalid unit (NaN / -1)
+        gets NaN in that column, and so does one with a ``period`` or a ``t_rev`` of -1 (no second peak, no
+        reversal: no value): invalid for ``pareto``, last for ``rank``."""
+        tseg = np.asarray(self.tseg)
+        a = tseg[:-1].astype(float)
+
+        def get(name):
+            if name not in OSC_FIELDS:
+                raise ValueError("unknown oscillation field %r" % (name,))
+            arr = getattr(self, name)
+            if arr is None:
+                raise ValueError("this result has no %s" % name)
+            arr = np.asarray(arr)
+            x = arr.reshape(arr.shape[0], -1, arr.shape[-1]).astype(float)
+            if arr.dtype.kind == "i":
+                x = np.where(x < 0, np.nan, x - a if name == "t_rev" else x)
+            return x
+
+        return _segment_cost_table(get, names, tseg, segments, reduce)
+
+
+def _osc_fields(fields):
+    fields = OSC_FIELDS if fields is None else tuple(fields)
+    for f in fields:
+        if f not in OSC_FIELDS:
+            raise ValueError("unknown oscillation field %r" % (f,))
+    return fields
+
+
+def _osc_params(tseg, base, band_rel, band_abs, rev_tol):
+    """The MpctOscParams of a call and the host boundary vector it points to (keep it alive for the call)."""
+    t = np.ascontiguousarray(np.asarray(tseg, dtype=np.int32).reshape(-1))
+    if t.size < 2:
+        raise ValueError("tseg needs at least two boundaries")
+    p = _lib.MpctOscParams(t.size - 1, _ip(t), int(base), float(band_rel), float(band_abs), float(rev_tol))
+    return p, t
+
+
+def _osc_result(Cn, nref, my, nu, tseg, fields):
+    """An OscResult with the arrays of ``fields`` and the MpctOscResult that points into them."""
+    nseg = len(tseg) - 1
+    res = OscResult(tseg=np.array(tseg, dtype=np.int32))
+    r = _lib.MpctOscResult()
+    for name, is_y, is_int in _lib.OSC_FIELDS:
+        if name in fields:
+            a = np.zeros((Cn, nref, my if is_y else nu, nseg), dtype=np.int32 if is_int else np.float64)
+            setattr(res, name, a)
+            setattr(r, name, _ip(a) if is_int else _dp(a))
+    return res, r
+
+
+def _osc_struct(out: dict):
+    r = _lib.MpctOscResult()
+    for name, _, is_int in _lib.OSC_FIELDS:
+        setattr(r, name, _tptr(out.get(name), _lib.c_int32_p if is_int else _lib.c_double_p))
+    return r
+
+
+def osc_indices(y, u, r, tseg, base=1, band_rel=0.02, band_abs=0.0, rev_tol=0.0, fields=None, device=-1) -> OscResult:
+    """mpct_osc_indices: the oscillation indices per setpoint segment of stored trajectories, reduced on the
+    GPU (host arrays in and out).  ``y`` (S, my, nit), ``u`` (S, nu, nit), ``r`` (nref, my, nit); simulation s
+    reads reference set s % nref; ``tseg`` the nseg + 1 boundaries (``reference_segments``).  ``y`` and ``r``
+    may be None when ``fields`` names no output-row field, ``u`` when it names no input-row field.  The arrays
+    of the result are (S / nref, nref, my, nseg) and (S / nref, nref, nu, nseg)."""
+    y = None if y is None else np.ascontiguousarray(y, dtype=np.float64)
+    u = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
+    r = None if r is None else np.ascontiguousarray(r, dtype=np.float64)
+    if (y is not None and y.ndim != 3) or (u is not None and u.ndim != 3) or (r is not None and r.ndim != 3):
+        raise ValueError("y, u and r must be 3-d: (S, my, nit), (S, nu, nit), (nref, my, nit)")
+    if y is None and u is None:
+        raise ValueError("y or u is needed")
+    some = y if y is not None else u
+    S, nit = some.shape[0], some.shape[2]
+    my = y.shape[1] if y is not None else 0
+    nu = u.shape[1] if u is not None else 0
+    nref = r.shape[0] if r is not None else 1
+    if (u is not None and u.shape[::2] != (S, nit)) or (r is not None and y is not None and r.shape[1:] != (my, nit)):
+        raise ValueError("y, u and r disagree on S, my or nit")
+    if fields is None:
+        fields = tuple(n for n, is_y, _ in _lib.OSC_FIELDS if (y if is_y else u) is not None)
+    fields = _osc_fields(fields)
+    if S % nref:
+        raise ValueError("S must be a multiple of nref")
+    p, t = _osc_params(tseg, base, band_rel, band_abs, rev_tol)
+    res, out = _osc_result(S // nref, nref, my, nu, t, fields)
+    ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+    rc = _lib.load().mpct_osc_indices(ptr(y), ptr(u), ptr(r), S, nref, my, nu, nit, C.byref(p), int(device), C.byref(out))
+    if rc != 0:
+        raise MpctError("mpct_osc_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return res
+
+
+def osc_indices_device(y, u, r, out: dict, tseg, base=1, band_rel=0.02, band_abs=0.0, rev_tol=0.0):
+    """mpct_osc_indices_device: ``y`` [S, my, nit], ``u`` [S, nu, nit], ``r`` [nref, my, nit] are contiguous
+    float64 CUDA (HIP) tensors (None where no field needs them), ``tseg`` a HOST sequence; the records are
+    written into the tensors of ``out`` (keys as the fields of OscResult: float64 / int32, [S, my, nseg] or
+    [S, nu, nseg]; any may be absent).  Enqueued on the current torch stream of the tensors' device and not
+    synchronised."""
+    import torch
+
+    some = y if y is not None else u
+    for t in (y, u, r):
+        if t is not None and (t.dtype != torch.float64 or t.dim() != 3 or not t.is_contiguous()):
+            raise ValueError("y, u and r must be contiguous float64 tensors with three dimensions")
+    S, nit = some.shape[0], some.shape[2]
+    my = y.shape[1] if y is not None else 0
+    nu = u.shape[1] if u is not None else 0
+    nref = r.shape[0] if r is not None else 1
+    p, keep = _osc_params(tseg, base, band_rel, band_abs, rev_tol)
+    o = _osc_struct(out)
+    stream = torch.cuda.current_stream(some.device).cuda_stream
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    with torch.cuda.device(some.device):
+        rc = _lib.load().mpct_osc_indices_device(ptr(y), ptr(u), ptr(r), S, nref, my, nu, nit, C.byref(p), C.byref(o),
+                                                 C.c_void_p(stream))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_osc_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+def eval_osc_indices(sc, N2, Nu, delta, lam, refs, v=None, tseg=None, extra=(), base=1, band_rel=0.02, band_abs=0.0,
+                     rev_tol=0.0, fields=None, want_costs=False, device=-1, max_qp_iter=0, feas_tol=0.0) -> OscResult:
+    """mpct_eval_osc_indices: score C candidates against nref reference sets and return only the oscillation
+    records of the closed loops (host arrays in and out); the trajectories stay on the device.  ``tseg``
+    defaults to ``reference_segments(refs, extra)``.  ``want_costs`` adds ``batch``: J1, j22, status and
+    qp_iters of the same launch, as eval_batch returns them."""
+    fields = _osc_fields(fields)
+    N2, Nu, delta, lam, refs, Cn, nref, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    if tseg is None:
+        tseg = reference_segments(refs, extra)
+    p, t = _osc_params(tseg, base, band_rel, band_abs, rev_tol)
+    res, out = _osc_result(Cn, nref, sc.my, sc.nu, t, fields)
+    br = None
+    if want_costs:
+        res.batch, br = _eval_result(sc, Cn * nref, nref, False, False)
+    o = _opts(False, False, device, max_qp_iter, feas_tol)
+    rc = sc.lib.mpct_eval_osc_indices(sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data, lam.ctypes.data,
+                                      nref, refs.ctypes.data, vv.ctypes.data if vv is not None else None, C.byref(o),
+                                      C.byref(p), C.byref(br) if br is not None else None, C.byref(out))
+    if rc != 0:
+        raise MpctError("mpct_eval_osc_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return res
+
+
+def eval_osc_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, tseg, v=None, base=1, band_rel=0.02, band_abs=0.0,
+                            rev_tol=0.0, device=-1, stream=None):
+    """Device-pointer entry of eval_osc_indices: every argument is a CUDA (HIP) torch tensor (``tseg`` is a
+    HOST sequence); the records are written into the tensors of ``out`` (the keys of osc_indices_device,
+    [C * nref, my, nseg] / [C * nref, nu, nseg], plus the optional J1, j21, j22, Jnu, status, qp_iters of
+    eval_batch_device).  Enqueued on ``stream`` (torch stream; default: current) and not synchronised."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    br = _lib.MpctResult()
+    br.J1, br.j21 = _tptr(out.get("J1"), _lib.c_double_p), _tptr(out.get("j21"), _lib.c_double_p)
+    br.j22, br.Jnu = _tptr(out.get("j22"), _lib.c_double_p), _tptr(out.get("Jnu"), _lib.c_double_p)
+    br.status, br.qp_iters = _tptr(out.get("status"), _lib.c_int32_p), _tptr(out.get("qp_iters"), _lib.c_int64_p)
+    p, keep = _osc_params(tseg, base, band_rel, band_abs, rev_tol)
+    o = _opts(False, False, device)
+    so = _osc_struct(out)
+    rc = sc.lib.mpct_eval_osc_indices_device(
+        sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+        C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+        C.c_void_p(v.data_ptr()) if v is not None else None, C.byref(o), C.byref(p), C.byref(br), C.byref(so),
+        C.c_void_p(stream.cuda_stream))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_eval_osc_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+def _osc_field_ids(sc, fields, nseg):
+    """The MPCT_OX_* ids of the selected fields as the int32 vector the library reads, and the (field, channel,
+    segment) columns."""
+    fields = _osc_fields(fields)
+    ids = np.ascontiguousarray([OSC_FIELDS.index(f) for f in fields], dtype=np.int32)
+    is_y = {n: y for n, y, _ in _lib.OSC_FIELDS}
+    cols = [(f, ch, g) for f in fields for ch in range(sc.my if is_y[f] else sc.nu) for g in range(nseg)]
+    return ids, cols
+
+
+def eval_robust_osc_indices(sc, N2, Nu, delta, lam, refs, v=None, tseg=None, extra=(), fields=None, levels=None,
+                            j_bound=0.0, base=1, band_rel=0.02, band_abs=0.0, rev_tol=0.0, device=-1, max_qp_iter=0,
+                            feas_tol=0.0) -> RobustSegmentResult:
+    """mpct_eval_robust_osc_indices: score C candidates over the D = len(refs) draws and reduce, on the device,
+    the oscillation indices ``fields`` (default: all seven) of the C x D closed loops to per-candidate
+    statistics over the surviving draws (host arrays in and out): eval_robust_segment_indices for the
+    oscillation fields, returned as a RobustSegmentResult (``.costs(stat, names, segments)``).  A draw without
+    a value in a column (an invalid unit, a period or a t_rev of -1) does not enter that column.  ``base``
+    here is the base-level rule of the segments; the robust J1 record is the result's ``.base``."""
+    N2, Nu, delta, lam, refs, Cn, D, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    if tseg is None:
+        tseg = reference_segments(refs, extra)
+    p, t = _osc_params(tseg, base, band_rel, band_abs, rev_tol)
+    ids, cols = _osc_field_ids(sc, fields, t.size - 1)
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    arr, out = _stats_arrays(Cn, len(cols), nlev)
+    rb = RobustResult(mean=np.zeros((Cn, sc.my)), worst=np.zeros((Cn, sc.my)), n_failed=np.zeros(Cn, dtype=np.int32),
+                      worst_draw=np.zeros(Cn, dtype=np.int32), status=np.zeros(Cn, dtype=np.int32), draws=D)
+    br = _lib.MpctRobustResult()
+    br.mean, br.worst = _dp(rb.mean), _dp(rb.worst)
+    br.n_failed, br.worst_draw, br.status = _ip(rb.n_failed), _ip(rb.worst_draw), _ip(rb.status)
+    o = _opts(False, False, device, max_qp_iter, feas_tol)
+    rc = sc.lib.mpct_eval_robust_osc_indices(
+        sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data, lam.ctypes.data, D, refs.ctypes.data,
+        vv.ctypes.data if vv is not None else None, float(j_bound), C.byref(o), C.byref(p), ids.size, _ip(ids), nlev,
+        _dp(lv) if nlev else None, C.byref(br), C.byref(out))
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_osc_indices failed (%d): %s" % (rc, _lib.last_error()))
+    return RobustSegmentResult(columns=cols, levels=lv, base=rb, tseg=t.copy(), **arr)
+
+
+def eval_robust_osc_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, tseg, base_out: dict | None = None, v=None,
+                                   fields=None, levels=None, j_bound=0.0, base=1, band_rel=0.02, band_abs=0.0,
+                                   rev_tol=0.0, device=-1, stream=None):
+    """Device-pointer entry of eval_robust_osc_indices: every argument is a CUDA (HIP) torch tensor (``tseg``,
+    ``fields`` and ``levels`` are HOST sequences); ``out`` as in eval_robust_indices_device, and ``base_out``
+    its ``base`` (the tensors of the robust J1 record).  Enqueued on ``stream`` (torch stream; default:
+    current) and not synchronised."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    p, keep = _osc_params(tseg, base, band_rel, band_abs, rev_tol)
+    ids, _ = _osc_field_ids(sc, fields, keep.size - 1)
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    br = _robust_struct(base_out or {})
+    o = _opts(False, False, device)
+    so = _stats_struct(out)
+    rc = sc.lib.mpct_eval_robust_osc_indices_device(
+        sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+        C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+        C.c_void_p(v.data_ptr()) if v is not None else None, float(j_bound), C.byref(o), C.byref(p), ids.size, _ip(ids),
+        nlev, _dp(lv) if nlev else None, C.byref(br), C.byref(so), C.c_void_p(stream.cuda_stream))
+    del keep
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_osc_indices_device failed (%d): %s" % (rc, _lib.last_error()))
