@@ -1574,6 +1574,90 @@ int32_t mpct_eval_robust_osc_indices_device(mpct_scenario* s, int64_t C, const i
                                             int32_t nlev, const double* levels, mpct_robust_result* base,
                                             const mpct_draw_stats_result* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Goal attainment: goal-attainment selection over a scored grid, on the device (goal_attain.hip; DESIGN.md
+ * §23).  The discrete counterpart of the reference's fgoalattain call: for each of G goal / weight vectors,
+ * the candidates of the [C][k] table that minimise the attainment factor
+ *     gamma = max_j (F_j - goal_j) / w_j ,
+ * where a weight of 0 makes objective j a hard constraint F_j <= goal_j.  mpct_rank_device's weighted sum
+ * cannot reach a candidate on a non-convex part of the front, mpct_pareto's front is not a decision and
+ * neither takes a specification ("overshoot at most 10 %"); this call does all three, and a sweep of weight
+ * directions says which few candidates win for most of them (wins).
+ *
+ * costs is [C][k] row-major, mpct_pareto's table: 1 <= k <= MPCT_PARETO_MAX_OBJ, 0 <= C <= MPCT_PARETO_MAX_C.
+ * goals and weights are [G][k] row-major, 0 <= G <= MPCT_GOAL_MAX_G; 0 <= n_best <= MPCT_GOAL_MAX_BEST.
+ *
+ * Goal vector g is VALID when every w_j is either 0 or a finite positive value whose rounded reciprocal
+ * iw_j = 1.0 / w_j is finite (a subnormal weight whose reciprocal overflows is not), at least one w_j > 0,
+ * every goal_j with w_j > 0 is finite, and every goal_j with w_j = 0 is not NaN (+INFINITY there: no
+ * constraint).  Negative weights (fgoalattain's over-attainment) are not supported: such a g is invalid.
+ *
+ * For a valid g and a candidate c:
+ *   c is VALID by mpct_pareto's rule: none of its k costs is NaN; +-INFINITY are ordinary values.
+ *   Hard objectives (w_j = 0): c must satisfy F_cj <= goal_j for each of them.
+ *   Soft objectives (w_j > 0), in ascending j: d = F_cj - goal_j, rounded; term = d * iw_j, rounded -- two
+ *   IEEE double operations, never a fused multiply-add, and iw_j the one correctly rounded division above.
+ *   gamma starts at -INFINITY and active at the first soft j; whenever term > gamma, gamma = term and
+ *   active = j.  So active is the SMALLEST j that attains the maximum.
+ *   c is FEASIBLE for g when it is valid, passes every hard objective and has no NaN term.  (With a valid g
+ *   a valid c has none: a soft goal is finite and 0 < iw_j < INFINITY.)  A feasible gamma may be +-INFINITY.
+ *   Order among the feasible candidates: ascending gamma by `<`, so -0.0 equals +0.0; ties by ascending
+ *   candidate index.  This is a total order, and it is what makes every result independent of the launch
+ *   geometry: the candidate range is split into chunks whose partial lists and integer counts are merged, and
+ *   neither the minimum of a total order nor an integer sum depends on the split.
+ *
+ *   best[g][0 .. n)     the first n = min(n_best, n_feasible[g]) candidates in that order
+ *   gamma[g][0 .. n)    their attainment factors, as computed (a -0.0 stays -0.0)
+ *   active[g][0 .. n)   their active objectives
+ *                       the entries n .. n_best of the three rows are -1 / NaN / -1
+ *   n_feasible[g]       the number of feasible candidates
+ *   n_attained[g]       the number of feasible candidates with gamma <= 0 (every goal met)
+ *   wins[c]             the number of g with best[g][0] == c; the call sets it to zero first
+ * An INVALID g writes -1 / NaN / -1 to its rows and -1 to both counts and adds nothing to wins.
+ * Any of the six pointers may be NULL, not all of them.  gamma or active needs n_best >= 1, neither needs
+ * best; n_best = 0 with the counts or wins alone is fine.  A repeated call is bitwise identical; permuting the
+ * goal vectors permutes the rows and counts and leaves wins unchanged.
+ *
+ * Argument errors, in this order and before any device is touched:
+ *   MPCT_EINVAL  k < 1 or k > MPCT_PARETO_MAX_OBJ
+ *   MPCT_EINVAL  C < 0 or G < 0
+ *   MPCT_ERANGE  C > MPCT_PARETO_MAX_C or G > MPCT_GOAL_MAX_G
+ *   MPCT_EINVAL  n_best < 0
+ *   MPCT_ERANGE  n_best > MPCT_GOAL_MAX_BEST
+ *   MPCT_EINVAL  costs NULL (with C > 0)
+ *   MPCT_EINVAL  goals or weights NULL (with G > 0)
+ *   MPCT_EINVAL  out NULL, or all six of its pointers NULL
+ *   MPCT_EINVAL  best, gamma or active non-NULL with n_best = 0
+ *   MPCT_EINVAL  mpct_goal_attain only: an invalid goal vector; the message names its row.  The device entry
+ *                cannot read the arrays and applies the invalid-g rule above instead.
+ * G = 0 returns MPCT_OK with wins zeroed (where given).  C = 0 is legal: every count of a valid g is 0 and
+ * the rows are padded. */
+#define MPCT_GOAL_MAX_G 1048576
+#define MPCT_GOAL_MAX_BEST 16
+typedef struct mpct_goal_result {
+  int32_t* best;       /* [G][n_best] */
+  double* gamma;       /* [G][n_best] */
+  int32_t* active;     /* [G][n_best] */
+  int32_t* n_feasible; /* [G] */
+  int32_t* n_attained; /* [G] */
+  int32_t* wins;       /* [C] */
+} mpct_goal_result;
+
+/* All pointers DEVICE pointers; enqueued on `stream` (NULL = default stream) and NOT synchronised.  Scratch
+ * comes from hipMallocAsync / hipFreeAsync on that stream, as in mpct_pareto_device, so calls on different
+ * streams are independent.  The work is bounded by C, G, k and n_best alone. */
+int32_t mpct_goal_attain_device(const double* costs, int64_t C, int32_t k, const double* goals,
+                                const double* weights, int64_t G, int32_t n_best, const mpct_goal_result* out,
+                                void* stream);
+
+/* Host pointers (MATLAB and C callers); needs no scenario.  device: HIP ordinal, -1 = the current device
+ * (an ordinal out of range is MPCT_EINVAL).  Stages on a stream of its own and waits for that stream only,
+ * as mpct_pareto does; the calling thread's current device is unchanged on return.  G = 0 and C = 0 need no
+ * device.  Without a device: MPCT_EDEVICE with a message.  An argument error, a missing device and a device
+ * ordinal out of range leave every output buffer, wins included, as it was. */
+int32_t mpct_goal_attain(const double* costs, int64_t C, int32_t k, const double* goals, const double* weights,
+                         int64_t G, int32_t n_best, int32_t device, const mpct_goal_result* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,16 @@
  *                                                    defines them, -1: a candidate with a NaN cost); layer is
  *                                                    [] with max_layers = 0; max_layers and device optional
  *                                                    (0: no layers; -1: the current device)
+ *   S = mpct_mex('goal_attain', costs, goals, weights, n_best, device)
+ *                                                    goal-attainment selection over the C x k cost table
+ *                                                    (mpct_goal_attain; no scenario needed): goals and weights are
+ *                                                    G x k or vectors of k elements (one row for every g), a weight
+ *                                                    of 0 a hard constraint costs(:, j) <= goal; struct with best
+ *                                                    (G x n_best, 1-BASED candidates by ascending attainment
+ *                                                    factor, 0: none), gamma (G x n_best, NaN: none), active
+ *                                                    (G x n_best, 1-BASED objective, 0: none), n_feasible,
+ *                                                    n_attained (G x 1) and wins (C x 1); n_best (1) and device
+ *                                                    (-1) optional
  *   H = mpct_mex('hypervolume', costs, members, lo, ref, n_samples, seed, device)
  *                                                    Monte-Carlo hypervolume the rows `members` of the C x k cost
  *                                                    table dominate inside the box [lo, ref] (mpct_hypervolume;
@@ -642,6 +652,81 @@ static double opt_integer(int nrhs, const mxArray* prhs[], int i, const char* wh
   const double v = (nrhs > i && !mxIsEmpty(prhs[i])) ? scalar(prhs[i], what) : dflt;
   if (v != floor(v) || v < lo || v > hi) mexErrMsgIdAndTxt("mpct:arg", "'%s' must be an integer in range", what);
   return v;
+}
+
+/* a G x k column-major matrix as the library's [G][k] rows; a vector of k elements is one row, repeated G times */
+static double* goal_rows(const mxArray* a, long G, long k, const char* what) {
+  if (!a || !mxIsNumeric(a) || mxIsComplex(a) || mxIsSparse(a) || mxGetNumberOfDimensions(a) != 2)
+    mexErrMsgIdAndTxt("mpct:arg", "'%s' must be a real full G x k matrix", what);
+  const long m = (long)mxGetM(a), n = (long)mxGetN(a);
+  const int vec = (m == 1 || n == 1) && m * n == k && !(m == G && n == k);
+  if (!vec && !(m == G && n == k)) mexErrMsgIdAndTxt("mpct:arg", "'%s' must be G x k or a vector of k elements", what);
+  double* cm = doubles(a, m * n, what);
+  double* rows = (double*)mxMalloc((size_t)(G * k + 1) * sizeof(double));
+  for (long g = 0; g < G; ++g)
+    for (long j = 0; j < k; ++j) rows[g * k + j] = vec ? cm[j] : cm[(size_t)j * G + g];
+  return rows;
+}
+
+/* S = mpct_mex('goal_attain', costs, goals, weights [, n_best, device]): costs is C x k, goals and weights G x k
+ * column-major (a vector of k elements: one row for every g), transposed here into the library's rows; the
+ * sizes and the goal vectors are the library's to judge (its message is surfaced) */
+static void cmd_goal_attain(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 4 || nrhs > 6)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: S = mpct_mex('goal_attain', costs, goals, weights [, n_best, device])");
+  const mxArray* a = prhs[1];
+  if (!a || !mxIsNumeric(a) || mxIsComplex(a) || mxIsSparse(a) || mxGetNumberOfDimensions(a) != 2)
+    mexErrMsgIdAndTxt("mpct:arg", "'costs' must be a real full C x k matrix");
+  const long C = (long)mxGetM(a), k = (long)mxGetN(a);
+  if (k > 1000000) mexErrMsgIdAndTxt("mpct:arg", "'costs' has too many columns");
+  const long nb = (long)opt_integer(nrhs, prhs, 4, "n_best", 1.0, -1e6, 1e6);
+  const double dv = opt_integer(nrhs, prhs, 5, "device", -1.0, -1e6, 1e6);
+  /* G: the rows of whichever of goals / weights is a matrix of k columns; two vectors are one goal vector */
+  long G = 1;
+  for (int i = 2; i <= 3; ++i)
+    if (prhs[i] && mxGetNumberOfDimensions(prhs[i]) == 2 && (long)mxGetN(prhs[i]) == k && (long)mxGetM(prhs[i]) > G)
+      G = (long)mxGetM(prhs[i]);
+  double* cm = doubles(a, C * k, "costs");
+  double* rows = (double*)mxMalloc((size_t)(C * k + 1) * sizeof(double));
+  for (long c = 0; c < C; ++c)
+    for (long j = 0; j < k; ++j) rows[c * k + j] = cm[(size_t)j * C + c];
+  double* gl = goal_rows(prhs[2], G, k, "goals");
+  double* w = goal_rows(prhs[3], G, k, "weights");
+  const long n = nb > 0 ? nb : 0;
+  mpct_goal_result r;
+  r.best = n ? (int32_t*)mxCalloc((size_t)(G * n + 1), sizeof(int32_t)) : NULL;
+  r.gamma = n ? (double*)mxCalloc((size_t)(G * n + 1), sizeof(double)) : NULL;
+  r.active = n ? (int32_t*)mxCalloc((size_t)(G * n + 1), sizeof(int32_t)) : NULL;
+  r.n_feasible = (int32_t*)mxCalloc((size_t)(G + 1), sizeof(int32_t));
+  r.n_attained = (int32_t*)mxCalloc((size_t)(G + 1), sizeof(int32_t));
+  r.wins = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  if (mpct_goal_attain(rows, C, (int32_t)k, gl, w, G, (int32_t)nb, (int32_t)dv, &r) != MPCT_OK) lib_error("mpct:goal_attain");
+  const char* names[6] = {"best", "gamma", "active", "n_feasible", "n_attained", "wins"};
+  mxArray* S = mxCreateStructMatrix(1, 1, 6, names);
+  mxArray* b = mxCreateDoubleMatrix((mwSize)G, (mwSize)n, mxREAL);
+  mxArray* gm = mxCreateDoubleMatrix((mwSize)G, (mwSize)n, mxREAL);
+  mxArray* ac = mxCreateDoubleMatrix((mwSize)G, (mwSize)n, mxREAL);
+  for (long g = 0; g < G; ++g)
+    for (long i = 0; i < n; ++i) {
+      mxGetPr(b)[(size_t)i * G + g] = (double)r.best[g * n + i] + 1.0;    /* 1-based candidate, 0: none */
+      mxGetPr(gm)[(size_t)i * G + g] = r.gamma[g * n + i];
+      mxGetPr(ac)[(size_t)i * G + g] = (double)r.active[g * n + i] + 1.0; /* 1-based objective, 0: none */
+    }
+  mxSetField(S, 0, "best", b);
+  mxSetField(S, 0, "gamma", gm);
+  mxSetField(S, 0, "active", ac);
+  mxArray* nf = mxCreateDoubleMatrix((mwSize)G, 1, mxREAL);
+  mxArray* na = mxCreateDoubleMatrix((mwSize)G, 1, mxREAL);
+  for (long g = 0; g < G; ++g) {
+    mxGetPr(nf)[g] = r.n_feasible[g];
+    mxGetPr(na)[g] = r.n_attained[g];
+  }
+  mxSetField(S, 0, "n_feasible", nf);
+  mxSetField(S, 0, "n_attained", na);
+  mxArray* wn = mxCreateDoubleMatrix((mwSize)C, 1, mxREAL);
+  for (long c = 0; c < C; ++c) mxGetPr(wn)[c] = r.wins[c];
+  mxSetField(S, 0, "wins", wn);
+  plhs[0] = S;
 }
 
 /* H = mpct_mex('hypervolume', costs, members, lo, ref [, n_samples, seed, device]): costs is C x k column-major,
@@ -1778,6 +1863,8 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_eval_robust(plhs, nrhs, prhs, 1);
   } else if (!strcmp(cmd, "pareto")) {
     cmd_pareto(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "goal_attain")) {
+    cmd_goal_attain(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "hypervolume")) {
     cmd_hypervolume(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "hv_select")) {

@@ -17,6 +17,7 @@
 #include "work_order.h"
 #include "dtc_robust.h"
 #include "pareto.h"
+#include "goal_attain.h"
 #include "hv_select.h"
 #include "hypervolume.h"
 #include "hypervolume_exact.h"
@@ -619,6 +620,125 @@ extern "C" int32_t mpct_pareto(const double* costs, int64_t C, int32_t k, int32_
     d.front = cs.at<int32_t>(s_front);
     d.n_front = cs.at<int32_t>(s_nfront);
     rc = pareto_launch(cs.at<double>(s_costs), C, k, max_layers, &d, cs.st, 0, 0);
+  }
+  return cs.close(rc);
+}
+
+// ---- Goal-attainment selection (goal_attain.hip).  The argument checks of both entries, in the order
+// include/mpct.h states, before any device is touched; nothing is dereferenced
+static int goal_check(const double* costs, int64_t C, int32_t k, const double* goals, const double* weights, int64_t G,
+                      int32_t n_best, const mpct_goal_result* out) {
+  if (k < 1 || k > MPCT_PARETO_MAX_OBJ) return fail(MPCT_EINVAL, "k must be 1 .. MPCT_PARETO_MAX_OBJ");
+  if (C < 0 || G < 0) return fail(MPCT_EINVAL, "C < 0 or G < 0");
+  if (C > MPCT_PARETO_MAX_C || G > MPCT_GOAL_MAX_G) return fail(MPCT_ERANGE, "C exceeds MPCT_PARETO_MAX_C or G exceeds MPCT_GOAL_MAX_G");
+  if (n_best < 0) return fail(MPCT_EINVAL, "n_best < 0");
+  if (n_best > MPCT_GOAL_MAX_BEST) return fail(MPCT_ERANGE, "n_best exceeds MPCT_GOAL_MAX_BEST");
+  if (C > 0 && !costs) return fail(MPCT_EINVAL, "costs is NULL");
+  if (G > 0 && (!goals || !weights)) return fail(MPCT_EINVAL, "goals or weights is NULL");
+  if (!out || !(out->best || out->gamma || out->active || out->n_feasible || out->n_attained || out->wins))
+    return fail(MPCT_EINVAL, "no output pointer in mpct_goal_result");
+  if (n_best == 0 && (out->best || out->gamma || out->active))
+    return fail(MPCT_EINVAL, "best, gamma and active need n_best >= 1");
+  return MPCT_OK;
+}
+
+// the number of chunks of the candidate range (0: the default, else 1 .. 1024) and the tile length (0: the
+// default, 128 or 256) of goal_pair_kernel.  A test hook, not part of include/mpct.h: the tests reach the
+// merge stage, partial and empty chunks at small shapes with it
+static int32_t g_goal_split = 0, g_goal_tile = 0;
+extern "C" int32_t mpct_internal_goal_grid(int32_t split, int32_t tile) {
+  if (split < 0 || split > kGoalMaxSplit || (tile != 0 && tile != 128 && tile != 256))
+    return fail(MPCT_EINVAL, "split must be 0 .. 1024, tile 0, 128 or 256");
+  g_goal_split = split;
+  g_goal_tile = tile;
+  return MPCT_OK;
+}
+
+// the grid the device entry launches for G goal vectors and C candidates under the hook's current setting:
+// {tile, chunks of the candidate range, candidates per chunk}
+extern "C" int32_t mpct_internal_goal_geometry(int64_t G, int64_t C, int32_t* tile_split_chunk) {
+  if (C < 0 || C > MPCT_PARETO_MAX_C || G < 0 || G > MPCT_GOAL_MAX_G || !tile_split_chunk) return fail(MPCT_EINVAL, "bad argument");
+  const int tile = g_goal_tile ? g_goal_tile : kGoalTile;
+  int split = 1, chunk = tile;
+  goal_grid(G, C, tile, g_goal_split, &split, &chunk);
+  tile_split_chunk[0] = tile;
+  tile_split_chunk[1] = split;
+  tile_split_chunk[2] = chunk;
+  return MPCT_OK;
+}
+
+static int32_t goal_launch(const double* costs, int64_t C, int32_t k, const double* goals, const double* weights, int64_t G,
+                           int32_t n_best, const mpct_goal_result* out, hipStream_t stream) {
+  std::string err;
+  const GoalOut go{out->best, out->gamma, out->active, out->n_feasible, out->n_attained, out->wins};
+  return launch_rc(goal_attain_device(costs, C, k, goals, weights, G, n_best, go, stream, &err, g_goal_tile, g_goal_split), err);
+}
+
+extern "C" int32_t mpct_goal_attain_device(const double* costs, int64_t C, int32_t k, const double* goals,
+                                           const double* weights, int64_t G, int32_t n_best, const mpct_goal_result* out,
+                                           void* stream) {
+  const int rc = goal_check(costs, C, k, goals, weights, G, n_best, out);
+  if (rc) return rc;
+  return goal_launch(costs, C, k, goals, weights, G, n_best, out, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_goal_attain(const double* costs, int64_t C, int32_t k, const double* goals, const double* weights,
+                                    int64_t G, int32_t n_best, int32_t device, const mpct_goal_result* out) {
+  int rc = goal_check(costs, C, k, goals, weights, G, n_best, out);
+  if (rc) return rc;
+  // the check that reads the caller's arrays, which only this entry can make: the validity rule of include/mpct.h
+  for (int64_t g = 0; g < G; ++g) {
+    bool ok = true, soft = false;
+    for (int j = 0; j < k; ++j) {
+      const double w = weights[g * k + j], gl = goals[g * k + j];
+      if (w == 0.0) {
+        ok = ok && !std::isnan(gl);
+      } else if (w > 0.0 && std::isfinite(w)) {
+        ok = ok && std::isfinite(1.0 / w) && std::isfinite(gl);
+        soft = true;
+      } else {
+        ok = false;
+      }
+    }
+    if (!ok || !soft)
+      return fail(MPCT_EINVAL, "goal vector " + std::to_string(g) + " is invalid: a weight is 0 or finite and positive with a "
+                  "finite reciprocal, one weight at least is positive, a goal is finite (not NaN where the weight is 0)");
+  }
+  if (G == 0) {  // nothing to stage: wins is all there is to write.  Otherwise the device zeroes it, so a call
+                 // that fails to open its device has written to none of the caller's buffers
+    if (out->wins) std::memset(out->wins, 0, (size_t)C * sizeof(int32_t));
+    return MPCT_OK;
+  }
+  if (C == 0) {  // nothing to stage either (wins has no entry): no candidate is feasible for the (valid) goal vectors
+    const double nan = std::nan("");
+    for (int64_t e = 0; e < G * n_best; ++e) {
+      if (out->best) out->best[e] = -1;
+      if (out->gamma) out->gamma[e] = nan;
+      if (out->active) out->active[e] = -1;
+    }
+    for (int64_t g = 0; g < G; ++g) {
+      if (out->n_feasible) out->n_feasible[g] = 0;
+      if (out->n_attained) out->n_attained[g] = 0;
+    }
+    return MPCT_OK;
+  }
+  CallStage cs{"mpct_goal_attain", "goal-attainment staging", "costs, goals and weights", "goal-attainment results"};
+  const size_t rows = (size_t)G * n_best;
+  const int s_costs = cs.in(costs, (size_t)C * k * sizeof(double));
+  const int s_goals = cs.in(goals, (size_t)G * k * sizeof(double)), s_w = cs.in(weights, (size_t)G * k * sizeof(double));
+  const int s_best = cs.out(out->best, rows * sizeof(int32_t)), s_gamma = cs.out(out->gamma, rows * sizeof(double)),
+            s_active = cs.out(out->active, rows * sizeof(int32_t)), s_nf = cs.out(out->n_feasible, (size_t)G * sizeof(int32_t)),
+            s_na = cs.out(out->n_attained, (size_t)G * sizeof(int32_t)), s_wins = cs.out(out->wins, (size_t)C * sizeof(int32_t));
+  rc = cs.open(device);
+  if (rc == MPCT_OK) {
+    mpct_goal_result d{};
+    d.best = cs.at<int32_t>(s_best);
+    d.gamma = cs.at<double>(s_gamma);
+    d.active = cs.at<int32_t>(s_active);
+    d.n_feasible = cs.at<int32_t>(s_nf);
+    d.n_attained = cs.at<int32_t>(s_na);
+    d.wins = cs.at<int32_t>(s_wins);
+    rc = goal_launch(cs.at<double>(s_costs), C, k, cs.at<double>(s_goals), cs.at<double>(s_w), G, n_best, &d, cs.st);
   }
   return cs.close(rc);
 }

@@ -90,6 +90,11 @@ class MpctParetoResult(C.Structure):
     _fields_ = [("dom_count", c_int32_p), ("layer", c_int32_p), ("front", c_int32_p), ("n_front", c_int32_p)]
 
 
+class MpctGoalResult(C.Structure):
+    _fields_ = [("best", c_int32_p), ("gamma", c_double_p), ("active", c_int32_p), ("n_feasible", c_int32_p),
+                ("n_attained", c_int32_p), ("wins", c_int32_p)]
+
+
 class MpctHvResult(C.Structure):
     _fields_ = [("n_covered", c_int64_p), ("excl", c_int64_p), ("depth_hist", c_int64_p), ("hv", c_double_p)]
 
@@ -197,11 +202,13 @@ EXPORTS = [
     "mpct_eval_segment_indices_device", "mpct_eval_robust_segment_indices", "mpct_eval_robust_segment_indices_device",
     "mpct_osc_indices_device", "mpct_osc_indices", "mpct_eval_osc_indices", "mpct_eval_osc_indices_device",
     "mpct_eval_robust_osc_indices", "mpct_eval_robust_osc_indices_device",
+    "mpct_goal_attain_device", "mpct_goal_attain",
 ]
 
 ABI_VERSION = 7
 TAIL_MAX_LEVELS, TAIL_MAX_DRAWS = 8, 4096
 PARETO_MAX_OBJ, PARETO_MAX_C, PARETO_MAX_LAYERS = 16, 1048576, 64
+GOAL_MAX_G, GOAL_MAX_BEST = 1048576, 16
 HV_MAX_SAMPLES, HV_BINS = 1073741824, 8
 HVSEL_MAX_PICKS = 1024
 HVX_MAX_OBJ, HVX_MAX_M = 3, 65536
@@ -405,6 +412,17 @@ def load():
     lib.mpct_eval_robust_osc_indices.restype = C.c_int32
     lib.mpct_eval_robust_osc_indices_device.argtypes = robust_osc_args + [C.c_void_p]
     lib.mpct_eval_robust_osc_indices_device.restype = C.c_int32
+    goal_args = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    lib.mpct_goal_attain_device.argtypes = goal_args + [C.POINTER(MpctGoalResult), C.c_void_p]
+    lib.mpct_goal_attain_device.restype = C.c_int32
+    lib.mpct_goal_attain.argtypes = goal_args + [C.c_int32, C.POINTER(MpctGoalResult)]
+    lib.mpct_goal_attain.restype = C.c_int32
+    # the chunks of the candidate range (0: the default) and the tile length (0, 128, 256) of goal_pair_kernel, and
+    # the grid {tile, chunks, candidates per chunk} that setting gives for G goal vectors and C candidates: test hooks
+    lib.mpct_internal_goal_grid.argtypes = [C.c_int32, C.c_int32]
+    lib.mpct_internal_goal_grid.restype = C.c_int32
+    lib.mpct_internal_goal_geometry.argtypes = [C.c_int64, C.c_int64, c_int32_p]
+    lib.mpct_internal_goal_geometry.restype = C.c_int32
     # the largest grid of draw_stats_kernel in workgroups (0: the default): a test hook
     lib.mpct_internal_draw_stats_grid.argtypes = [C.c_int32]
     lib.mpct_internal_draw_stats_grid.restype = C.c_int32

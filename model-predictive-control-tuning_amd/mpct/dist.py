@@ -198,6 +198,98 @@ def pareto_candidates(costs: torch.Tensor, C: int | None = None, max_layers: int
     return res
 
 
+def _goal_torch(costs: torch.Tensor, goals: torch.Tensor, weights: torch.Tensor, n_best: int, chunk: int = 128) -> dict:
+    """The contract of mpct_goal_attain_device (include/mpct.h) as chunked torch expressions, on the tensor's
+    device: the CPU path of goal_attain_candidates.  Elementwise float64 operations round one by one, so the
+    attainment factors are the kernel's bit for bit."""
+    Cn, k = costs.shape
+    G, dev = goals.shape[0], costs.device
+    inf = float("inf")
+    soft, hard = weights > 0, weights == 0
+    iw = torch.where(soft, 1.0 / weights, torch.zeros_like(weights))
+    ok = torch.where(soft, torch.isfinite(weights) & torch.isfinite(iw) & torch.isfinite(goals), hard & ~torch.isnan(goals))
+    valid = ok.all(dim=1) & soft.any(dim=1)
+    cvalid = ~torch.isnan(costs).any(dim=1)
+    best = torch.full((G, n_best), -1, dtype=torch.int32, device=dev)
+    gamma = torch.full((G, n_best), float("nan"), dtype=torch.float64, device=dev)
+    active = torch.full((G, n_best), -1, dtype=torch.int32, device=dev)
+    nf = torch.full((G,), -1, dtype=torch.int32, device=dev)
+    na = torch.full((G,), -1, dtype=torch.int32, device=dev)
+    wins = torch.zeros(Cn, dtype=torch.int32, device=dev)
+    for g0 in range(0, G, chunk):
+        v = torch.nonzero(valid[g0:g0 + chunk]).flatten() + g0
+        if v.numel() == 0:
+            continue
+        gl, sf, hd = goals[v][:, None, :], soft[v][:, None, :], hard[v][:, None, :]
+        term = (costs[None, :, :] - gl) * iw[v][:, None, :]
+        feas = cvalid[None, :] & ((costs[None, :, :] <= gl) | ~hd).all(dim=2) & ~(torch.isnan(term) & sf).any(dim=2)
+        tm = torch.where(sf & ~torch.isnan(term), term, torch.full_like(term, -inf))
+        top = tm.max(dim=2, keepdim=True).values
+        act = ((tm == top) & sf).to(torch.int8).argmax(dim=2)           # the smallest soft j that attains the maximum
+        gam = tm.gather(2, act[:, :, None])[:, :, 0]                     # its term, sign of a zero included
+        nf[v] = feas.sum(dim=1).to(torch.int32)
+        na[v] = (feas & (gam <= 0)).sum(dim=1).to(torch.int32)
+        if not Cn:
+            continue
+        # NaN sorts last and the sort is stable: ascending gamma, ties by ascending candidate index
+        ranked = torch.sort(torch.where(feas, gam, torch.full_like(gam, float("nan"))), dim=1, stable=True).indices
+        wins += torch.bincount(ranked[:, 0][feas.any(dim=1)], minlength=Cn).to(torch.int32)
+        n = min(n_best, Cn)
+        if n:
+            order = ranked[:, :n]
+            keep = feas.gather(1, order)
+            best[v, :n] = torch.where(keep, order, torch.full_like(order, -1)).to(torch.int32)
+            gamma[v, :n] = torch.where(keep, gam.gather(1, order), torch.full_like(gam[:, :n], float("nan")))
+            active[v, :n] = torch.where(keep, act.gather(1, order), torch.full_like(order, -1)).to(torch.int32)
+    return dict(best=best, gamma=gamma, active=active, n_feasible=nf, n_attained=na, wins=wins)
+
+
+def goal_attain_candidates(costs: torch.Tensor, goals, weights, n_best: int = 1, C: int | None = None) -> dict:
+    """Goal-attainment selection over the gathered cost records (contract: mpct_goal_attain_device in
+    include/mpct.h): per goal / weight vector the ``n_best`` candidates with the smallest attainment factor
+    gamma = max_j (F_j - goal_j) / w_j among those meeting every hard objective (w_j = 0).  ``goals`` and
+    ``weights`` are (k,) or (G, k), a (k,) one is broadcast.  Returns a dict of tensors on the costs' device: best,
+    active [G, n_best] int32, gamma [G, n_best] float64, n_feasible, n_attained [G] int32, wins [C] int32; an
+    invalid goal vector has -1 / NaN rows and -1 counts.  Identical on every rank, because every rank analyses the
+    same gathered tensor in a fixed order.  GPU tensors go through mpct_goal_attain_device on the current stream;
+    CPU tensors (the gloo tests) through chunked torch expressions."""
+    if C is not None:
+        costs = costs[:C]
+    if costs.dim() == 1:
+        costs = costs[:, None]
+    n_best = int(n_best)
+    if not 0 <= n_best <= 16:
+        raise ValueError("n_best must be 0 .. 16")
+    c = costs.to(torch.float64).contiguous()
+    n, k = c.shape
+    if not 1 <= k <= 16:
+        raise ValueError("k must be 1 .. 16")
+    gl = torch.as_tensor(goals, dtype=torch.float64, device=c.device)
+    w = torch.as_tensor(weights, dtype=torch.float64, device=c.device)
+    G = next((int(x.shape[0]) for x in (gl, w) if x.dim() == 2), 1)
+    gl = (gl if gl.dim() == 2 else gl[None, :].expand(G, -1)).contiguous()
+    w = (w if w.dim() == 2 else w[None, :].expand(G, -1)).contiguous()
+    if gl.shape != (G, k) or w.shape != (G, k):
+        raise ValueError("goals and weights must be (k,) or (G, k)")
+    if not c.is_cuda:
+        return _goal_torch(c, gl, w, n_best)
+    from . import engine
+
+    out = dict(n_feasible=torch.empty(G, dtype=torch.int32, device=c.device),
+               n_attained=torch.empty(G, dtype=torch.int32, device=c.device),
+               wins=torch.empty(n, dtype=torch.int32, device=c.device))
+    if n_best:
+        out.update(best=torch.empty((G, n_best), dtype=torch.int32, device=c.device),
+                   gamma=torch.empty((G, n_best), dtype=torch.float64, device=c.device),
+                   active=torch.empty((G, n_best), dtype=torch.int32, device=c.device))
+    engine.goal_attain_device(c, gl, w, out, n_best=n_best)
+    if not n_best:
+        out.update(best=torch.empty((G, 0), dtype=torch.int32, device=c.device),
+                   gamma=torch.empty((G, 0), dtype=torch.float64, device=c.device),
+                   active=torch.empty((G, 0), dtype=torch.int32, device=c.device))
+    return out
+
+
 def _hv_points(lo: torch.Tensor, ref: torch.Tensor, seed: int, i0: int, i1: int) -> torch.Tensor:
     """Sample points i0 .. i1 - 1 of the hypervolume contract (include/mpct.h), [i1 - i0, k] on lo's device.
     torch has no uint64 arithmetic: int64 products wrap to the same bits, and a logical right shift is an

@@ -6,6 +6,8 @@
   closedloop_toolbox  drop-in for closedloop_toolbox.m:1 (one candidate, full trajectories)
   pareto              mpct_pareto: front, domination counts and layers of a [C, k] cost table
   pareto_device       mpct_pareto_device (torch CUDA tensors, enqueued on the current stream)
+  goal_attain         mpct_goal_attain: per goal / weight vector, the candidates that minimise the attainment factor
+  goal_attain_device  mpct_goal_attain_device (torch CUDA tensors, enqueued on the current stream)
   hypervolume         mpct_hypervolume: Monte-Carlo hypervolume of a front in a box, per-member contributions
   hypervolume_device  mpct_hypervolume_device (torch CUDA tensors, enqueued on the current stream)
   hv_select           mpct_hv_select: the n members that carry a front, by greedy selection on the coverage count
@@ -428,6 +430,12 @@ class RobustResult:
         (name, j) with name 'quantile' or 'cvar' and j the level's index."""
         return pareto(self._cost_table(stat, max_failed, columns), max_layers=max_layers, device=device)
 
+    def goal_attain(self, goals, weights, n_best: int = 1, stat: str = "worst", max_failed: int = 0, columns=(),
+                    device: int = -1):
+        """Goal-attainment selection (``goal_attain``) over the cost table ``pareto`` analyses (same ``stat``,
+        ``max_failed`` and ``columns``): a candidate over ``max_failed`` is feasible for no goal vector."""
+        return goal_attain(self._cost_table(stat, max_failed, columns), goals, weights, n_best=n_best, device=device)
+
     def hypervolume(self, stat: str = "worst", max_failed: int = 0, columns=(), device: int = -1, **kw):
         """``hypervolume`` of the front of the cost table ``pareto`` analyses (same ``stat``, ``max_failed`` and
         ``columns``); ``kw`` are hypervolume's lo, ref, n_samples and seed."""
@@ -622,6 +630,87 @@ def pareto_device(costs, out: dict, max_layers: int = 0):
                                             int(max_layers), C.byref(r), C.c_void_p(stream))
     if rc != 0:
         raise MpctError("mpct_pareto_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+# --------------------------------------------------------------------------------------------
+# Goal-attainment selection over a scored grid (mpct_goal_attain, include/mpct.h)
+@dataclass
+class GoalResult:
+    """Per goal / weight vector g, the candidates that minimise gamma = max_j (F_j - goal_j) / w_j among those
+    that meet every hard objective (w_j = 0: F_j <= goal_j); ties by ascending candidate index."""
+    best: np.ndarray | None         # (G, n_best) candidates by ascending (gamma, index); -1 beyond n_feasible; None with n_best = 0
+    gamma: np.ndarray | None        # (G, n_best) their attainment factors; NaN beyond n_feasible
+    active: np.ndarray | None       # (G, n_best) the smallest j that attains the maximum; -1 beyond n_feasible
+    n_feasible: np.ndarray          # (G,) feasible candidates
+    n_attained: np.ndarray          # (G,) feasible candidates with gamma <= 0
+    wins: np.ndarray                # (C,) goal vectors whose best[g, 0] is c
+
+    def winners(self) -> np.ndarray:
+        """The distinct ``best[:, 0]`` by descending ``wins``, ties by ascending index."""
+        c = np.flatnonzero(self.wins > 0)
+        return c[np.argsort(-self.wins[c].astype(np.int64), kind="stable")].astype(np.int32)
+
+
+def _goal_rows(x, G, k, what):
+    """goals or weights as a contiguous (G, k) float64 array; a (k,) one is broadcast (G None: one row)"""
+    a = np.asarray(x, dtype=np.float64)
+    if a.ndim == 1:
+        a = np.broadcast_to(a, (1 if G is None else G, a.shape[0]))
+    if a.ndim != 2 or a.shape[1] != k or (G is not None and a.shape[0] != G):
+        raise ValueError("%s must be (k,) or (G, k) with k = %d" % (what, k))
+    return np.ascontiguousarray(a)
+
+
+def _goal_shapes(goals, weights, k):
+    """goals and weights as (G, k) arrays, a (k,) one broadcast to the other's G"""
+    G = next((np.shape(x)[0] for x in (goals, weights) if np.ndim(x) == 2), None)
+    return _goal_rows(goals, G, k, "goals"), _goal_rows(weights, G, k, "weights")
+
+
+def goal_attain(costs, goals, weights, n_best: int = 1, device: int = -1) -> GoalResult:
+    """mpct_goal_attain: goal-attainment selection over the (C, k) cost table for the goal / weight vectors
+    ``goals`` and ``weights`` ((k,) or (G, k); a (k,) one is broadcast), computed on the GPU (host arrays in
+    and out).  A weight of 0 makes that objective a hard constraint ``F_j <= goal_j``."""
+    a = _pareto_costs(costs)
+    Cn, k = a.shape
+    gl, w = _goal_shapes(goals, weights, k)
+    G, nb = gl.shape[0], int(n_best)
+    rows = max(nb, 0)
+    best = np.zeros((G, rows), dtype=np.int32) if nb else None
+    gam = np.zeros((G, rows), dtype=np.float64) if nb else None
+    act = np.zeros((G, rows), dtype=np.int32) if nb else None
+    nf, na = np.zeros(G, dtype=np.int32), np.zeros(G, dtype=np.int32)
+    wins = np.zeros(Cn, dtype=np.int32)
+    r = _lib.MpctGoalResult(_ip(best) if nb else None, _dp(gam) if nb else None, _ip(act) if nb else None, _ip(nf), _ip(na),
+                            _ip(wins))
+    rc = _lib.load().mpct_goal_attain(a.ctypes.data, Cn, k, gl.ctypes.data, w.ctypes.data, G, nb, int(device), C.byref(r))
+    if rc != 0:
+        raise MpctError("mpct_goal_attain failed (%d): %s" % (rc, _lib.last_error()))
+    return GoalResult(best=best, gamma=gam, active=act, n_feasible=nf, n_attained=na, wins=wins)
+
+
+def goal_attain_device(costs, goals, weights, out: dict, n_best: int = 1):
+    """mpct_goal_attain_device: ``costs`` [C, k], ``goals`` and ``weights`` [G, k] are contiguous float64 CUDA (HIP)
+    tensors; the results are written into the tensors of ``out`` (keys best, active: int32 [G, n_best]; gamma:
+    float64 [G, n_best]; n_feasible, n_attained: int32 [G]; wins: int32 [C]; any may be absent).  Enqueued on the
+    current torch stream of the tensor's device and not synchronised.  An invalid goal vector gets -1 / NaN rows."""
+    import torch
+
+    for t, what in ((costs, "costs"), (goals, "goals"), (weights, "weights")):
+        if t.dtype != torch.float64 or t.dim() != 2 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous float64 tensor [rows, k]" % what)
+    if goals.shape != weights.shape or goals.shape[1] != costs.shape[1]:
+        raise ValueError("goals and weights must both be [G, k]")
+    types = dict(best=_lib.c_int32_p, gamma=_lib.c_double_p, active=_lib.c_int32_p, n_feasible=_lib.c_int32_p,
+                 n_attained=_lib.c_int32_p, wins=_lib.c_int32_p)
+    r = _lib.MpctGoalResult(*[_tptr(out.get(f), ty) for f, ty in types.items()])
+    stream = torch.cuda.current_stream(costs.device).cuda_stream
+    with torch.cuda.device(costs.device):
+        rc = _lib.load().mpct_goal_attain_device(C.c_void_p(costs.data_ptr()), costs.shape[0], costs.shape[1],
+                                                 C.c_void_p(goals.data_ptr()), C.c_void_p(weights.data_ptr()),
+                                                 goals.shape[0], int(n_best), C.byref(r), C.c_void_p(stream))
+    if rc != 0:
+        raise MpctError("mpct_goal_attain_device failed (%d): %s" % (rc, _lib.last_error()))
 
 
 # --------------------------------------------------------------------------------------------
@@ -965,6 +1054,10 @@ class IndexResult:
             cols.append(x.max(axis=1) if reduce == "max" else x.sum(axis=1))
         return np.stack(cols, axis=1) if cols else np.zeros((0, 0))
 
+    def goal_attain(self, names, goals, weights, n_best: int = 1, device: int = -1, **kw):
+        """Goal-attainment selection (``goal_attain``) over the table ``costs(names, **kw)`` returns."""
+        return goal_attain(self.costs(names, **kw), goals, weights, n_best=n_best, device=device)
+
 
 def _index_fields(fields):
     fields = INDEX_FIELDS if fields is None else tuple(fields)
@@ -1239,6 +1332,10 @@ class RobustIndexResult:
         """Pareto analysis (``pareto``) of the table ``costs`` returns."""
         return pareto(self.costs(stat, names, max_failed), max_layers=max_layers, device=device)
 
+    def goal_attain(self, stat, names, goals, weights, n_best: int = 1, max_failed: int = 0, device: int = -1):
+        """Goal-attainment selection (``goal_attain``) over the table ``costs`` returns."""
+        return goal_attain(self.costs(stat, names, max_failed=max_failed), goals, weights, n_best=n_best, device=device)
+
     def hypervolume(self, stat="hi", names=None, max_failed: int = 0, device: int = -1, **kw):
         """``hypervolume`` of the front of the table ``costs`` returns; ``kw`` are hypervolume's lo, ref,
         n_samples and seed."""
@@ -1381,6 +1478,10 @@ class LimitResult:
             col = np.where(neutral.all(axis=1) & (x.shape[1] > 0), np.nan, col)
             cols.append(col)
         return np.stack(cols, axis=1) if cols else np.zeros((0, 0))
+
+    def goal_attain(self, names, goals, weights, n_best: int = 1, device: int = -1, **kw):
+        """Goal-attainment selection (``goal_attain``) over the table ``costs(names, **kw)`` returns."""
+        return goal_attain(self.costs(names, **kw), goals, weights, n_best=n_best, device=device)
 
 
 def _limit_fields(fields):
@@ -1713,6 +1814,10 @@ class SegmentResult:
 
         return _segment_cost_table(get, names, tseg, segments, reduce)
 
+    def goal_attain(self, names, goals, weights, n_best: int = 1, device: int = -1, **kw):
+        """Goal-attainment selection (``goal_attain``) over the table ``costs(names, **kw)`` returns."""
+        return goal_attain(self.costs(names, **kw), goals, weights, n_best=n_best, device=device)
+
 
 def _segment_fields(fields):
     fields = SEGMENT_FIELDS if fields is None else tuple(fields)
@@ -2006,6 +2111,10 @@ class OscResult:
             return x
 
         return _segment_cost_table(get, names, tseg, segments, reduce)
+
+    def goal_attain(self, names, goals, weights, n_best: int = 1, device: int = -1, **kw):
+        """Goal-attainment selection (``goal_attain``) over the table ``costs(names, **kw)`` returns."""
+        return goal_attain(self.costs(names, **kw), goals, weights, n_best=n_best, device=device)
 
 
 def _osc_fields(fields):
