@@ -42,7 +42,10 @@
  *     mpct_eval_robust_segment_indices, mpct_eval_robust_segment_indices_device), and the oscillation
  *     indices per setpoint segment (mpct_osc_params, mpct_osc_result, mpct_osc_indices_device,
  *     mpct_osc_indices, mpct_eval_osc_indices, mpct_eval_osc_indices_device, mpct_eval_robust_osc_indices,
- *     mpct_eval_robust_osc_indices_device).
+ *     mpct_eval_robust_osc_indices_device), and the goal-attainment selection (mpct_goal_result,
+ *     mpct_goal_attain_device, mpct_goal_attain), and the trajectory envelopes over the plant draws
+ *     (mpct_envelope_spread, mpct_envelope_device, mpct_envelope, mpct_eval_robust_envelope,
+ *     mpct_eval_robust_envelope_device).
  */
 #ifndef MPCT_H
 #define MPCT_H
@@ -1657,6 +1660,105 @@ int32_t mpct_goal_attain_device(const double* costs, int64_t C, int32_t k, const
  * ordinal out of range leave every output buffer, wins included, as it was. */
 int32_t mpct_goal_attain(const double* costs, int64_t C, int32_t k, const double* goals, const double* weights,
                          int64_t G, int32_t n_best, int32_t device, const mpct_goal_result* out);
+
+/* ---------------------------------------------------------------------------------------------
+ * Trajectory envelopes over plant draws, on the device (envelope.hip).  The robust entries
+ * reduce a candidate's D draws to numbers; these return what the loop did over time, across the draws: per
+ * candidate, row and sample the band the signal stays in, its mean, its quantile lines and the draw that sits
+ * on the edge -- the figure a Monte-Carlo study draws with `hold on` -- without C*D trajectories leaving the
+ * device, and per candidate and row how wide that band is.
+ *
+ * Trajectories in mpct_result's layout, y[S][my][nit] and u[S][nu][nit] with simulation s = c*D + k.  Read as
+ * it lies in memory, y is the table x[C][D][m] of mpct_draw_stats with m = my*nit (u: m = nu*nit), x_type
+ * MPCT_STAT_F64, and the ENVELOPE of a side IS mpct_draw_stats of that table: alive is [C][D] or NULL, draw k
+ * survives at sample (c, row, t) when it is alive and its value there is finite, and every field of
+ * mpct_draw_stats_result is defined exactly as there -- n, mean (one accumulator from 0.0 over the survivors
+ * in ascending k, divided by (double)n), lo / hi with the lowest draw that holds them and that draw's bits
+ * (-0.0 == +0.0), the type-1 quantile, q_draw and cvar per level; n = 0 gives NaN / -1.  The arrays are
+ * [C][rows][nit] and [C][rows][nit][nlev].  The envelope covers every sample, 0 .. nit-1.
+ *
+ * The spread of a side, per (c, row), element c*rows + row, over the samples t = t0 .. nit-1:
+ *   spread        sum_t d(t), d(t) = hi(t) - lo(t) rounded once, in the fixed order of the performance indices:
+ *                 lane (t - t0) mod 64 accumulates its d in ascending t from 0.0, then the 64 partials are
+ *                 combined as a pairwise tree in lane order
+ *   spread_max    max_t d(t);  t_spread_max  the first t that attains it
+ * A row with n(t) = 0 at any t in the range gives NaN, NaN, -1.  The spread reads the lo and hi of its side
+ * that the same call has just written, so those two pointers must be given with it.
+ *
+ * Any pointer of the two mpct_draw_stats_result and the two mpct_envelope_spread may be NULL, and each of the
+ * four structs itself; a side without a result pointer is not read (its trajectory pointer may be NULL).
+ * levels is a HOST pointer in every entry; nlev may be 0.  A repeated call is bitwise identical and a record
+ * depends neither on C nor on the candidate's place in the batch.  Two kernels serve the levels, one lane per
+ * column up to a draw count fixed by measurement and mpct_draw_stats' kernel above it; both implement the
+ * one contract and give the same bits.
+ *
+ * Argument errors of mpct_envelope_device and mpct_envelope, in this order and before any device is touched:
+ *   MPCT_EINVAL  C < 0, D < 1, my < 0, nu < 0 or nit < 1
+ *   MPCT_EINVAL  t0 < 0 or t0 >= nit
+ *   MPCT_EINVAL  nlev < 0 or nlev > MPCT_TAIL_MAX_LEVELS; nlev > 0 with levels NULL; a level that is NaN, <= 0 or > 1
+ *   MPCT_EINVAL  a spread pointer of a side whose lo or hi is NULL
+ *   MPCT_EINVAL  no result pointer at all in out_y and out_u
+ *   MPCT_EINVAL  a quantile, cvar or q_draw pointer with nlev = 0
+ *   MPCT_EINVAL  a result pointer in out_y with my < 1 or (C > 0) y NULL; the same for out_u, nu and u
+ *   MPCT_ERANGE  D > MPCT_TAIL_MAX_DRAWS with nlev > 0
+ *   MPCT_ERANGE  C*my*nit or C*nu*nit > MPCT_INDEX_MAX_ROWS
+ * C = 0 is MPCT_OK and writes nothing. */
+typedef struct mpct_envelope_spread {
+  double* spread;        /* [C*rows] */
+  double* spread_max;    /* [C*rows] */
+  int32_t* t_spread_max; /* [C*rows] */
+} mpct_envelope_spread;
+
+/* All pointers DEVICE pointers (levels excepted); enqueued on `stream` (NULL = default stream) and NOT
+ * synchronised.  Needs no scenario and no scratch: at most two kernel launches per side. */
+int32_t mpct_envelope_device(const double* y, const double* u, const int32_t* alive, int64_t C, int32_t D, int32_t my,
+                             int32_t nu, int32_t nit, int32_t t0, int32_t nlev, const double* levels,
+                             const mpct_draw_stats_result* out_y, const mpct_draw_stats_result* out_u,
+                             const mpct_envelope_spread* spread_y, const mpct_envelope_spread* spread_u, void* stream);
+
+/* Host pointers (MATLAB and C callers), for trajectories from any source.  device: HIP ordinal, -1 = the
+ * current device (an ordinal out of range is MPCT_EINVAL).  Stages on a stream of its own and waits for that
+ * stream only; the calling thread's current device is unchanged on return.  Without a device: MPCT_EDEVICE
+ * with a message. */
+int32_t mpct_envelope(const double* y, const double* u, const int32_t* alive, int64_t C, int32_t D, int32_t my, int32_t nu,
+                      int32_t nit, int32_t t0, int32_t nlev, const double* levels, int32_t device,
+                      const mpct_draw_stats_result* out_y, const mpct_draw_stats_result* out_u,
+                      const mpct_envelope_spread* spread_y, const mpct_envelope_spread* spread_u);
+
+/* Score C candidates x D = nref draws and return the envelopes of their closed loops (host pointers; arguments
+ * as mpct_eval_robust).  Per chunk of whole candidates (the chunking of mpct_eval_indices,
+ * MPCT_INDEX_SCRATCH_BYTES of trajectory scratch) the closed loops run with their trajectories, J1 and status
+ * written to scratch of the scenario's context; a classify kernel writes alive[c][k] by the rule of
+ * mpct_eval_robust (status 0, J = sum_i J1_i finite, summed over i = 0 .. my-1 in that order, J <= j_bound with
+ * 0 = 1e100; a candidate carrying MPCT_ST_SKIPPED or MPCT_ST_BADHORIZON on any draw has no live draw); and the
+ * envelope kernels reduce the chunk's trajectories there.  Every record is bitwise independent of the chunk size.
+ *   base     optional: mean and worst of J1, n_failed, worst_draw and status exactly as mpct_eval_robust
+ *            defines them, from the same launch.  base->J1 must be NULL: the sample lives per chunk.
+ *   opts     open_loop = 1 is MPCT_EINVAL; want_traj is ignored (the call sets it).
+ * Errors, in this order and before any device is touched.  MPCT_EINVAL: s NULL; open_loop set; nref < 1; a
+ * negative or NaN j_bound; t0 < 0 or t0 >= nit; nlev < 0 or > MPCT_TAIL_MAX_LEVELS, nlev > 0 with levels NULL, a
+ * level that is NaN, <= 0 or > 1; a spread pointer of a side whose lo or hi is NULL; no result pointer at all
+ * in base, out_y and out_u; base->J1 set; a quantile / cvar / q_draw pointer with nlev = 0; then everything
+ * mpct_eval_batch rejects.  Then MPCT_ERANGE for nref > MPCT_TAIL_MAX_DRAWS with nlev > 0, and for C*my*nit or
+ * C*nu*nit > MPCT_INDEX_MAX_ROWS.  C = 0 is MPCT_OK and writes nothing.  Without a device: MPCT_EDEVICE with a
+ * message. */
+int32_t mpct_eval_robust_envelope(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu, const double* delta,
+                                  const double* lambda, int32_t nref, const double* r, const double* v, double j_bound,
+                                  const mpct_opts* opts, int32_t t0, int32_t nlev, const double* levels,
+                                  mpct_robust_result* base, const mpct_draw_stats_result* out_y,
+                                  const mpct_draw_stats_result* out_u, const mpct_envelope_spread* spread_y,
+                                  const mpct_envelope_spread* spread_u);
+
+/* Same, all pointers DEVICE pointers except levels, enqueued on `stream` (NULL = default stream) and NOT
+ * synchronised: the contract of mpct_eval_robust_indices_device, whose scratch and stream-ordering rule it
+ * shares. */
+int32_t mpct_eval_robust_envelope_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                         const double* delta, const double* lambda, int32_t nref, const double* r,
+                                         const double* v, double j_bound, const mpct_opts* opts, int32_t t0, int32_t nlev,
+                                         const double* levels, mpct_robust_result* base,
+                                         const mpct_draw_stats_result* out_y, const mpct_draw_stats_result* out_u,
+                                         const mpct_envelope_spread* spread_y, const mpct_envelope_spread* spread_u,
+                                         void* stream);
 
 #ifdef __cplusplus
 }

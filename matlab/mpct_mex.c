@@ -114,6 +114,20 @@
  *                                                    each column), the arrays of 'draw_stats' as C x W (x nlev), and
  *                                                    the robust record of J1: J1_mean, J1_worst (C x my), n_failed,
  *                                                    worst_draw, status (C x 1)
+ *   E = mpct_mex('envelope', y, u, D, alive, params) envelopes of stored trajectories over the draws (mpct_envelope; no
+ *                                                    scenario needed): y my x nit x S, u nu x nit x S with page
+ *                                                    s = (c-1)*D + k draw k of candidate c (either may be []), alive
+ *                                                    D x C or [], params optional (levels, t0, device).  Struct with,
+ *                                                    for each side p = y, u, the arrays of 'draw_stats' p_n, p_mean,
+ *                                                    p_lo, p_lo_draw, p_hi, p_hi_draw (C x rows*nit, sample (row, t) in
+ *                                                    column (row-1)*nit + t + 1), p_quantile, p_cvar, p_q_draw
+ *                                                    (C x rows*nit x nlev) and p_spread, p_spread_max, p_t_spread_max
+ *                                                    (C x rows) over the samples from t0 on, and levels; t0, the draws
+ *                                                    and p_t_spread_max are 0-BASED, -1: none
+ *   E = mpct_mex('eval_robust_envelope', h, N2, Nu, delta, lambda, r, v, params)
+ *                                                    the same for the C x D closed loops over the D pages of r
+ *                                                    (mpct_eval_robust_envelope; params also takes j_bound), plus the
+ *                                                    robust record of J1: J1_mean, J1_worst, n_failed, worst_draw, status
  *   mpct_mex('destroy', h)
  *
  * MATLAB layouts (column-major, what the callers already hold):
@@ -1382,6 +1396,148 @@ static void cmd_eval_robust_indices(mxArray* plhs[], int nrhs, const mxArray* pr
   plhs[0] = T;
 }
 
+/* ---- trajectory envelopes over the draws (mpct_envelope, mpct_eval_robust_envelope; include/mpct.h) */
+#define ENV_NSIDE 12 /* the nine arrays of 'draw_stats' and the three of the spread, per side */
+static const char* const kEnvNames[2 * ENV_NSIDE + 1] = {
+    "y_n", "y_mean", "y_lo", "y_lo_draw", "y_hi", "y_hi_draw", "y_quantile", "y_cvar", "y_q_draw", "y_spread", "y_spread_max",
+    "y_t_spread_max",
+    "u_n", "u_mean", "u_lo", "u_lo_draw", "u_hi", "u_hi_draw", "u_quantile", "u_cvar", "u_q_draw", "u_spread", "u_spread_max",
+    "u_t_spread_max", "levels"};
+
+static mpct_envelope_spread spread_buffers(long rows) {
+  mpct_envelope_spread s;
+  s.spread = (double*)mxCalloc((size_t)(rows + 1), sizeof(double));
+  s.spread_max = (double*)mxCalloc((size_t)(rows + 1), sizeof(double));
+  s.t_spread_max = (int32_t*)mxCalloc((size_t)(rows + 1), sizeof(int32_t));
+  return s;
+}
+
+/* one side's twelve fields into struct E from name k0 on: C x (rows*nit) (x nlev), sample (row, t) in column
+ * (row-1)*nit + t + 1, and C x rows for the spread; [] for a side that was not computed */
+static void set_envelope_side(mxArray* E, int k0, int with, const mpct_draw_stats_result* r, const mpct_envelope_spread* s,
+                              long nlev, long C, int rows, int nit) {
+  mxArray* a[ENV_NSIDE];
+  if (with) {
+    const int w = rows * nit;
+    a[0] = out_int_rows(r->n, C, w), a[1] = out_rows(r->mean, C, w), a[2] = out_rows(r->lo, C, w);
+    a[3] = out_int_rows(r->lo_draw, C, w), a[4] = out_rows(r->hi, C, w), a[5] = out_int_rows(r->hi_draw, C, w);
+    a[6] = out_levels(r->quantile, NULL, C, w, nlev), a[7] = out_levels(r->cvar, NULL, C, w, nlev);
+    a[8] = out_levels(NULL, r->q_draw, C, w, nlev);
+    a[9] = out_rows(s->spread, C, rows), a[10] = out_rows(s->spread_max, C, rows), a[11] = out_int_rows(s->t_spread_max, C, rows);
+  } else {
+    for (int k = 0; k < ENV_NSIDE; ++k) a[k] = mxCreateDoubleMatrix(0, 0, mxREAL);
+  }
+  for (int k = 0; k < ENV_NSIDE; ++k) mxSetField(E, 0, kEnvNames[k0 + k], a[k]);
+}
+
+/* params struct of the two envelope commands (all fields optional): levels, t0 (0-based first sample of the spread),
+ * device, and for the scoring command j_bound */
+static void read_envelope_params(const mxArray* o, int32_t* t0, double* device, double** levels, long* nlev, double* j_bound) {
+  *t0 = 0, *device = -1.0, *levels = NULL, *nlev = 0, *j_bound = 0.0;
+  if (!o || mxIsEmpty(o)) return;
+  if (!mxIsStruct(o)) mexErrMsgIdAndTxt("mpct:arg", "params must be a struct (levels, t0, j_bound, device)");
+  const double t = fscalar(o, "t0", 0.0);
+  *device = fscalar(o, "device", -1.0);
+  if (t != floor(t) || fabs(t) > 2147483647.0) mexErrMsgIdAndTxt("mpct:arg", "'t0' must be an integer");
+  if (*device != floor(*device) || fabs(*device) > 1e6) mexErrMsgIdAndTxt("mpct:arg", "'device' must be an integer");
+  *t0 = (int32_t)t;
+  *levels = read_levels(mxGetField(o, 0, "levels"), nlev);
+  *j_bound = fscalar(o, "j_bound", 0.0);
+}
+
+/* E = mpct_mex('envelope', y, u, D [, alive, params]): y my x nit x S, u nu x nit x S (the layouts 'eval' returns; page
+ * s = (c-1)*D + k is draw k of candidate c), either may be []; alive D x C or [].  t0, the draws and t_spread_max are
+ * the library's 0-based indices, -1: none */
+static void cmd_envelope(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 4 || nrhs > 6) mexErrMsgIdAndTxt("mpct:arg", "usage: E = mpct_mex('envelope', y, u, D [, alive, params])");
+  int my, nity, nu, nitu;
+  long Sy, Su;
+  signal_dims(prhs[1], "y", &my, &nity, &Sy);
+  signal_dims(prhs[2], "u", &nu, &nitu, &Su);
+  const int with_y = Sy > 0, with_u = Su > 0;
+  if (!with_y && !with_u) mexErrMsgIdAndTxt("mpct:arg", "'y' and 'u' are both empty");
+  if (with_y && with_u && (Sy != Su || nity != nitu)) mexErrMsgIdAndTxt("mpct:arg", "'y' and 'u' must agree on nit and S");
+  const long S = with_y ? Sy : Su;
+  const int nit = with_y ? nity : nitu;
+  const double Dd = scalar(prhs[3], "D");
+  if (Dd != floor(Dd) || Dd < 1.0 || Dd > 2147483647.0 || S % (long)Dd != 0)
+    mexErrMsgIdAndTxt("mpct:arg", "'D' must be an integer >= 1 that divides the number of pages");
+  const long D = (long)Dd, C = S / D;
+  const mxArray* al = nrhs > 4 && !mxIsEmpty(prhs[4]) ? prhs[4] : NULL;
+  if (al && ((long)mxGetM(al) != D || (long)mxGetN(al) != C)) mexErrMsgIdAndTxt("mpct:arg", "'alive' must be D x C");
+  int32_t t0;
+  long nlev;
+  double device, j_bound, *levels;
+  read_envelope_params(nrhs > 5 ? prhs[5] : NULL, &t0, &device, &levels, &nlev, &j_bound);
+  if (!with_y) my = 0;
+  if (!with_u) nu = 0;
+  int pg = 0;
+  double* y = with_y ? signals(prhs[1], my, nit, &pg, "y") : NULL;
+  pg = 0;
+  double* u = with_u ? signals(prhs[2], nu, nit, &pg, "u") : NULL;
+  int32_t* alive = NULL;
+  if (al) { /* D x C column-major is [C][D] row-major already */
+    double* av = doubles(al, C * D, "alive");
+    alive = (int32_t*)mxMalloc(((size_t)(C * D) + 1) * sizeof(int32_t));
+    for (long e = 0; e < C * D; ++e) alive[e] = av[e] != 0.0;
+  }
+  const mpct_draw_stats_result ry = stats_buffers(C * my * nit, nlev), ru = stats_buffers(C * nu * nit, nlev);
+  const mpct_envelope_spread sy = spread_buffers(C * my), su = spread_buffers(C * nu);
+  if (mpct_envelope(y, u, alive, C, (int32_t)D, my, nu, nit, t0, (int32_t)nlev, levels, (int32_t)device, with_y ? &ry : NULL,
+                    with_u ? &ru : NULL, with_y ? &sy : NULL, with_u ? &su : NULL) != MPCT_OK)
+    lib_error("mpct:envelope");
+  mxArray* E = mxCreateStructMatrix(1, 1, 2 * ENV_NSIDE + 1, (const char**)kEnvNames);
+  set_envelope_side(E, 0, with_y, &ry, &sy, nlev, C, my, nit);
+  set_envelope_side(E, ENV_NSIDE, with_u, &ru, &su, nlev, C, nu, nit);
+  mxSetField(E, 0, "levels", nlev > 0 ? out_rows(levels, 1, (int)nlev) : mxCreateDoubleMatrix(0, 0, mxREAL));
+  plhs[0] = E;
+}
+
+/* E = mpct_mex('eval_robust_envelope', h, N2, Nu, delta, lambda, r [, v, params]): the fields of 'envelope' for the
+ * C x D closed loops over the D pages of r, and the robust record of J1 of the same launch */
+static void cmd_eval_robust_envelope(mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  if (nrhs < 7 || nrhs > 9)
+    mexErrMsgIdAndTxt("mpct:arg", "usage: E = mpct_mex('eval_robust_envelope', h, N2, Nu, delta, lambda, r [, v, params])");
+  int32_t t0;
+  long nlev;
+  double device, j_bound, *levels;
+  read_envelope_params(nrhs > 8 ? prhs[8] : NULL, &t0, &device, &levels, &nlev, &j_bound);
+  const batch_args b = read_batch(nrhs, prhs, 2);
+  mpct_opts o = read_opts(NULL);
+  o.device = (int32_t)device;
+  const long C = b.C;
+  const int my = b.my, nu = b.nu, nit = b.nit;
+  const mpct_draw_stats_result ry = stats_buffers(C * my * nit, nlev), ru = stats_buffers(C * nu * nit, nlev);
+  const mpct_envelope_spread sy = spread_buffers(C * my), su = spread_buffers(C * nu);
+  mpct_robust_result base;
+  memset(&base, 0, sizeof base);
+  base.mean = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
+  base.worst = (double*)mxCalloc((size_t)(C * my + 1), sizeof(double));
+  base.n_failed = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  base.worst_draw = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  base.status = (int32_t*)mxCalloc((size_t)(C + 1), sizeof(int32_t));
+  if (mpct_eval_robust_envelope(b.s, C, b.N2, b.Nu, b.delta, b.lambda, b.nref, b.r, b.v, j_bound, &o, t0, (int32_t)nlev, levels,
+                                &base, &ry, &ru, &sy, &su) != MPCT_OK)
+    lib_error("mpct:eval_robust_envelope");
+  const char* names[2 * ENV_NSIDE + 6];
+  for (int k = 0; k < 2 * ENV_NSIDE + 1; ++k) names[k] = kEnvNames[k];
+  names[2 * ENV_NSIDE + 1] = "J1_mean";
+  names[2 * ENV_NSIDE + 2] = "J1_worst";
+  names[2 * ENV_NSIDE + 3] = "n_failed";
+  names[2 * ENV_NSIDE + 4] = "worst_draw";
+  names[2 * ENV_NSIDE + 5] = "status";
+  mxArray* E = mxCreateStructMatrix(1, 1, 2 * ENV_NSIDE + 6, names);
+  set_envelope_side(E, 0, 1, &ry, &sy, nlev, C, my, nit);
+  set_envelope_side(E, ENV_NSIDE, 1, &ru, &su, nlev, C, nu, nit);
+  mxSetField(E, 0, "levels", nlev > 0 ? out_rows(levels, 1, (int)nlev) : mxCreateDoubleMatrix(0, 0, mxREAL));
+  mxSetField(E, 0, "J1_mean", out_rows(base.mean, C, my));
+  mxSetField(E, 0, "J1_worst", out_rows(base.worst, C, my));
+  mxSetField(E, 0, "n_failed", out_int_rows(base.n_failed, C, 1));
+  mxSetField(E, 0, "worst_draw", out_int_rows(base.worst_draw, C, 1));
+  mxSetField(E, 0, "status", out_int_rows(base.status, C, 1));
+  plhs[0] = E;
+}
+
 /* ---- step-response indices per setpoint segment (mpct_reference_segments, mpct_segment_indices,
  * mpct_eval_segment_indices, mpct_eval_robust_segment_indices; include/mpct.h) */
 static const char* const kSegNames[15] = {"iae", "ise", "itae", "emax", "t_emax", "over", "under", "e_final",
@@ -1877,6 +2033,10 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     cmd_eval_indices(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "draw_stats")) {
     cmd_draw_stats(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "envelope")) {
+    cmd_envelope(plhs, nrhs, prhs);
+  } else if (!strcmp(cmd, "eval_robust_envelope")) {
+    cmd_eval_robust_envelope(plhs, nrhs, prhs);
   } else if (!strcmp(cmd, "eval_robust_indices")) {
     cmd_eval_robust_indices(plhs, nrhs, prhs, 0);
   } else if (!strcmp(cmd, "limit_indices")) {

@@ -26,6 +26,7 @@
 #include "osc_indices.h"
 #include "segment_indices.h"
 #include "draw_stats.h"
+#include "envelope.h"
 
 namespace mpct {
 // defined in gpc_kernel_launch.hip
@@ -477,7 +478,7 @@ struct CallStage {
   // the entry's words in the messages: "<entry> failed on the device", "hipMalloc failed (<staging>)",
   // "hipMemcpyAsync failed (<inputs>)", "hipMemcpyAsync failed (<results>)"
   const char *entry, *staging, *inputs, *results;
-  static constexpr int kMaxSlots = 18;  // mpct_segment_indices, the widest entry: 3 trajectories and 15 fields
+  static constexpr int kMaxSlots = 27;  // mpct_envelope, the widest entry: y, u, alive, two records of 9 and two spreads of 3
   struct Slot {
     void* host;  // NULL: nothing reserved
     size_t bytes, off;
@@ -1027,7 +1028,7 @@ struct HostStage {
   size_t off = 0;
   size_t o_N2, o_Nu, o_d, o_l;  // the candidates' slots
   Batch dev{};                  // the candidates and signals on the device, after upload()
-  static constexpr int kMaxSlots = 25;  // mpct_eval_segment_indices, the widest entry: an mpct_result and 15 fields
+  static constexpr int kMaxSlots = 29;  // mpct_eval_robust_envelope, the widest entry: a base of 5, two records of 9, two spreads of 3
   struct Slot {
     void* host;  // NULL: nothing to copy back
     size_t bytes, off;
@@ -1847,36 +1848,29 @@ static int check_robust_indices(mpct_scenario* s, const Batch& b, double j_bound
 // bits of the int32 ones, records(rec, y, u, S) enqueues the chunk's reduction kernel with rec[id] the
 // selected fields' device records)
 constexpr int kMaxRobustFields = 15;
-template <class Records>
-static int walk_robust_chunks(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
-                              int ny_fields, int per_row, unsigned int_mask, int32_t nsel, const int32_t* fields, int32_t nlev,
-                              const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream,
-                              Records records) {
-  auto field_width = [&](const mpct_scenario* sc, int id) { return (id < ny_fields ? sc->my : sc->nu) * per_row; };
-  auto field_is_int = [&](int id) { return (int_mask >> id & 1u) != 0; };
+
+// The walk itself, shared with the trajectory envelopes (envelope.hip), whose "record" is the trajectory:
+// extra(Sc) is the scratch in bytes a chunk of Sc simulations needs behind alive; records(ex, y, u, S) enqueues
+// what reduces the chunk's S simulations into that scratch `ex`; reduce(ex, y, u, alive, c0, n) enqueues the
+// statistics of the chunk's n candidates, the batch's c0 onwards, once alive is written
+template <class Extra, class Records, class Reduce>
+static int walk_draw_chunks(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
+                            const RobustOut& base, hipStream_t stream, Extra extra, Records records, Reduce reduce) {
   if (b.C == 0) return MPCT_OK;
   const int my = s->my, nu = s->nu, nit = s->nit;
   const int64_t C = b.C;
   const int32_t nref = b.nref;
   const double bound = j_bound == 0.0 ? kRobustDefaultBound : j_bound;
   const int64_t cc = index_chunk(C, nref, my, nu, nit);  // launch_indices' chunking
-  // the chunk's scratch: y | u | J1 | status | alive | the selected fields' records, each 256-B aligned
+  // the chunk's scratch: y | u | J1 | status | alive | the walk's own records, each 256-B aligned
   auto al = [](size_t n) { return (n + 255) & ~(size_t)255; };
   const size_t Sc = (size_t)cc * nref;
   const size_t o_j1 = al((size_t)cc * traj_bytes(nref, my, nu, nit)), o_st = o_j1 + al(Sc * my * 8), o_al = o_st + al(Sc * 4);
-  size_t o_f[kMaxRobustFields], off = o_al + al(Sc * 4);
-  int W = 0;
-  for (int q = 0; q < nsel; ++q) {
-    o_f[q] = off;
-    off += al(Sc * field_width(s, fields[q]) * (field_is_int(fields[q]) ? 4 : 8));
-    W += field_width(s, fields[q]);
-  }
+  const size_t o_ex = o_al + al(Sc * 4);
   char* scr = nullptr;
-  int rc = cx->index.acquire(off, stream, "trajectory scratch", &scr);
+  int rc = cx->index.acquire(o_ex + extra(Sc), stream, "trajectory scratch", &scr);
   if (rc) return rc;
   const mpct_opts o = traj_opts(opts);
-  void* rec[kMaxRobustFields] = {nullptr};
-  for (int q = 0; q < nsel; ++q) rec[fields[q]] = scr + o_f[q];
   const bool any_base = base.mean || base.worst || base.n_failed || base.worst_draw || base.status;
   std::string err;
   for (int64_t c0 = 0; c0 < C && rc == MPCT_OK; c0 += cc) {
@@ -1888,7 +1882,7 @@ static int walk_robust_chunks(mpct_scenario* s, DevCtx* cx, const Batch& b, doub
     per_chunk.u = per_chunk.y + (size_t)n * nref * my * nit;
     int32_t* alive = reinterpret_cast<int32_t*>(scr + o_al);
     rc = launch_batch(s, cx, b.sub(c0, n, my, nu), &o, &per_chunk, stream);
-    if (rc == MPCT_OK) rc = records(rec, per_chunk.y, per_chunk.u, n * nref);
+    if (rc == MPCT_OK) rc = records(scr + o_ex, per_chunk.y, per_chunk.u, n * nref);
     if (rc != MPCT_OK) break;
     int lrc = launch_draw_alive(n, nref, my, bound, per_chunk.J1, per_chunk.status, alive, stream, &err);
     if (lrc == 0 && any_base) {
@@ -1902,17 +1896,49 @@ static int walk_robust_chunks(mpct_scenario* s, DevCtx* cx, const Batch& b, doub
       rc = fail(MPCT_EDEVICE, err);
       break;
     }
-    if (!out.any()) continue;
-    int col = 0;
-    for (int q = 0; q < nsel && rc == MPCT_OK; ++q) {
-      const int w = field_width(s, fields[q]);
-      rc = stats_launch(rec[fields[q]], field_is_int(fields[q]) ? MPCT_STAT_I32 : MPCT_STAT_F64, alive, n, nref, w, nlev,
-                        levels, out.from(c0, W, nlev), W, col, stream);
-      col += w;
-    }
+    rc = reduce(scr + o_ex, per_chunk.y, per_chunk.u, alive, c0, n);
   }
   cx->index.mark(stream);
   return rc;
+}
+
+template <class Records>
+static int walk_robust_chunks(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
+                              int ny_fields, int per_row, unsigned int_mask, int32_t nsel, const int32_t* fields, int32_t nlev,
+                              const double* levels, const RobustOut& base, const DrawStatsOut& out, hipStream_t stream,
+                              Records records) {
+  auto field_width = [&](const mpct_scenario* sc, int id) { return (id < ny_fields ? sc->my : sc->nu) * per_row; };
+  auto field_is_int = [&](int id) { return (int_mask >> id & 1u) != 0; };
+  // the selected fields' records, each 256-B aligned
+  size_t o_f[kMaxRobustFields];
+  int W = 0;
+  for (int q = 0; q < nsel; ++q) W += field_width(s, fields[q]);
+  void* rec[kMaxRobustFields] = {nullptr};
+  return walk_draw_chunks(
+      s, cx, b, j_bound, opts, base, stream,
+      [&](size_t Sc) {
+        size_t off = 0;
+        for (int q = 0; q < nsel; ++q) {
+          o_f[q] = off;
+          off += (Sc * field_width(s, fields[q]) * (field_is_int(fields[q]) ? 4 : 8) + 255) & ~(size_t)255;
+        }
+        return off;
+      },
+      [&](char* ex, const double* y, const double* u, int64_t S) {
+        for (int q = 0; q < nsel; ++q) rec[fields[q]] = ex + o_f[q];
+        return records(rec, y, u, S);
+      },
+      [&](char*, const double*, const double*, const int32_t* alive, int64_t c0, int64_t n) {
+        int rc = MPCT_OK, col = 0;
+        if (!out.any()) return rc;
+        for (int q = 0; q < nsel && rc == MPCT_OK; ++q) {
+          const int w = field_width(s, fields[q]);
+          rc = stats_launch(rec[fields[q]], field_is_int(fields[q]) ? MPCT_STAT_I32 : MPCT_STAT_F64, alive, n, b.nref, w,
+                            nlev, levels, out.from(c0, W, nlev), W, col, stream);
+          col += w;
+        }
+        return rc;
+      });
 }
 
 static int launch_robust_indices(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
@@ -2868,6 +2894,242 @@ extern "C" int32_t mpct_eval_robust_osc_indices(mpct_scenario* s, int64_t C, con
   return robust_stats_host(s, cx, b, W, nlev, base, out, [&](HostStage& hs, const RobustOut& ro, const DrawStatsOut& dv) {
     return launch_robust_osc(s, cx, hs.dev, j_bound, opts, op, nsel, fields, nlev, levels, ro, dv, hs.st);
   });
+}
+
+// ------------------------------------------------------------------------------------------
+// trajectory envelopes over the plant draws (envelope.hip; include/mpct.h)
+
+static EnvSpreadOut spread_out(const mpct_envelope_spread* o) {
+  return o ? EnvSpreadOut{o->spread, o->spread_max, o->t_spread_max} : EnvSpreadOut{};
+}
+
+// the checks both kinds of entry share from t0 on, in the header's order; base: the robust entries' optional record
+static int envelope_check_out(int32_t nit, int32_t t0, int32_t nlev, const double* levels, const mpct_robust_result* base,
+                              const mpct_draw_stats_result* out_y, const mpct_draw_stats_result* out_u,
+                              const mpct_envelope_spread* spread_y, const mpct_envelope_spread* spread_u) {
+  if (t0 < 0 || t0 >= nit) return fail(MPCT_EINVAL, "t0 must lie in [0, nit)");
+  const int rc = stats_check_levels(nlev, levels);
+  if (rc) return rc;
+  const DrawStatsOut oy = out_y ? stats_out(out_y) : DrawStatsOut{}, ou = out_u ? stats_out(out_u) : DrawStatsOut{};
+  if ((spread_out(spread_y).any() && !(oy.lo && oy.hi)) || (spread_out(spread_u).any() && !(ou.lo && ou.hi)))
+    return fail(MPCT_EINVAL, "a spread pointer needs the lo and hi of its side: the spread reads them");
+  const bool any_base = base && (base->mean || base->worst || base->n_failed || base->worst_draw || base->status);
+  if (!any_base && !oy.any() && !ou.any()) return fail(MPCT_EINVAL, "every output pointer is NULL");
+  if (base && base->J1) return fail(MPCT_EINVAL, "base->J1 must be NULL: the sample lives per chunk");
+  if (nlev == 0 && (oy.any_level() || ou.any_level())) return fail(MPCT_EINVAL, "quantile, cvar and q_draw need nlev >= 1");
+  return MPCT_OK;
+}
+
+static int envelope_check_range(int64_t C, int32_t D, int32_t my, int32_t nu, int32_t nit, int32_t nlev) {
+  if (nlev > 0 && D > MPCT_TAIL_MAX_DRAWS)
+    return fail(MPCT_ERANGE, "D > MPCT_TAIL_MAX_DRAWS (4096) with levels: the kernel's LDS holds no more draws");
+  if (C * (int64_t)my * nit > kIndexMaxRows || C * (int64_t)nu * nit > kIndexMaxRows)
+    return fail(MPCT_ERANGE, "C*my*nit or C*nu*nit exceeds MPCT_INDEX_MAX_ROWS");
+  return MPCT_OK;
+}
+
+// the argument checks of the two stored-trajectory entries, in the header's order; nothing here touches a device
+static int envelope_check(const double* y, const double* u, int64_t C, int32_t D, int32_t my, int32_t nu, int32_t nit,
+                          int32_t t0, int32_t nlev, const double* levels, const mpct_draw_stats_result* out_y,
+                          const mpct_draw_stats_result* out_u, const mpct_envelope_spread* spread_y,
+                          const mpct_envelope_spread* spread_u) {
+  if (C < 0 || D < 1 || my < 0 || nu < 0 || nit < 1) return fail(MPCT_EINVAL, "bad shape: C < 0, D < 1, my < 0, nu < 0 or nit < 1");
+  int rc = envelope_check_out(nit, t0, nlev, levels, nullptr, out_y, out_u, spread_y, spread_u);
+  if (rc) return rc;
+  if (out_y && stats_out(out_y).any() && (my < 1 || (C > 0 && !y))) return fail(MPCT_EINVAL, "out_y needs my >= 1 and y");
+  if (out_u && stats_out(out_u).any() && (nu < 1 || (C > 0 && !u))) return fail(MPCT_EINVAL, "out_u needs nu >= 1 and u");
+  return envelope_check_range(C, D, my, nu, nit, nlev);
+}
+
+// test / bench hooks, not part of include/mpct.h.  The largest grid of draw_envelope_kernel in workgroups
+// (0: kEnvGridCap): the tests force the workgroups to stride at small sizes with it.  And the draws up to which
+// the levels run on the lane kernel (0: kEnvDefaultDlane; at most kEnvLaneMaxDraws): the tests and the bench run
+// both kernels on one shape with it
+static int32_t g_env_grid = 0, g_env_dlane = 0;
+extern "C" int32_t mpct_internal_envelope_grid(int32_t groups) {
+  if (groups < 0) return fail(MPCT_EINVAL, "groups < 0");
+  g_env_grid = groups;
+  return MPCT_OK;
+}
+extern "C" int32_t mpct_internal_envelope_dlane(int32_t draws) {
+  if (draws < 0 || draws > kEnvLaneMaxDraws) return fail(MPCT_EINVAL, "draws must be 0 .. 227");
+  g_env_dlane = draws;
+  return MPCT_OK;
+}
+
+// one side: the table x [C][D][rows * nit], its records and its spread
+static int32_t envelope_side(const double* x, const int32_t* alive, int64_t C, int32_t D, int32_t rows, int32_t nit,
+                             int32_t t0, int32_t nlev, const double* levels, const DrawStatsOut& out,
+                             const EnvSpreadOut& sp, hipStream_t stream) {
+  if (!out.any() || C == 0) return MPCT_OK;
+  const int m = rows * nit;
+  const int dlane = g_env_dlane > 0 ? g_env_dlane : kEnvDefaultDlane;
+  if (nlev > 0 && out.any_level() && D > dlane) {
+    const int rc = stats_launch(x, MPCT_STAT_F64, alive, C, D, m, nlev, levels, out, m, 0, stream);
+    if (rc) return rc;
+  } else {
+    std::string err;
+    if (launch_draw_envelope(x, alive, C, D, m, nlev, levels, out, g_env_grid, stream, &err)) return fail(MPCT_EDEVICE, err);
+  }
+  std::string err;
+  if (launch_envelope_spread(out.lo, out.hi, C * rows, nit, t0, sp, stream, &err)) return fail(MPCT_EDEVICE, err);
+  return MPCT_OK;
+}
+
+static int32_t envelope_launch(const double* y, const double* u, const int32_t* alive, int64_t C, int32_t D, int32_t my,
+                               int32_t nu, int32_t nit, int32_t t0, int32_t nlev, const double* levels,
+                               const DrawStatsOut& oy, const DrawStatsOut& ou, const EnvSpreadOut& sy, const EnvSpreadOut& su,
+                               hipStream_t stream) {
+  const int rc = envelope_side(y, alive, C, D, my, nit, t0, nlev, levels, oy, sy, stream);
+  return rc ? rc : envelope_side(u, alive, C, D, nu, nit, t0, nlev, levels, ou, su, stream);
+}
+
+extern "C" int32_t mpct_envelope_device(const double* y, const double* u, const int32_t* alive, int64_t C, int32_t D,
+                                        int32_t my, int32_t nu, int32_t nit, int32_t t0, int32_t nlev, const double* levels,
+                                        const mpct_draw_stats_result* out_y, const mpct_draw_stats_result* out_u,
+                                        const mpct_envelope_spread* spread_y, const mpct_envelope_spread* spread_u,
+                                        void* stream) {
+  const int rc = envelope_check(y, u, C, D, my, nu, nit, t0, nlev, levels, out_y, out_u, spread_y, spread_u);
+  if (rc) return rc;
+  return envelope_launch(y, u, alive, C, D, my, nu, nit, t0, nlev, levels, out_y ? stats_out(out_y) : DrawStatsOut{},
+                         out_u ? stats_out(out_u) : DrawStatsOut{}, spread_out(spread_y), spread_out(spread_u),
+                         static_cast<hipStream_t>(stream));
+}
+
+// the slots of one side's records and spread in a staging blob: want(host, bytes) reserves one and returns it
+template <class Want>
+static void envelope_slots(Want want, const mpct_draw_stats_result& o, const mpct_envelope_spread& sp, size_t C, size_t rows,
+                           size_t nit, size_t nlev, int* slot) {
+  const size_t cols = C * rows * nit, lev = cols * nlev, cr = C * rows;
+  slot[0] = want(o.n, cols * 4), slot[1] = want(o.mean, cols * 8), slot[2] = want(o.lo, cols * 8);
+  slot[3] = want(o.lo_draw, cols * 4), slot[4] = want(o.hi, cols * 8), slot[5] = want(o.hi_draw, cols * 4);
+  slot[6] = want(o.quantile, lev * 8), slot[7] = want(o.cvar, lev * 8), slot[8] = want(o.q_draw, lev * 4);
+  slot[9] = want(sp.spread, cr * 8), slot[10] = want(sp.spread_max, cr * 8), slot[11] = want(sp.t_spread_max, cr * 4);
+}
+template <class Stage>
+static DrawStatsOut envelope_dev_out(const Stage& st, const int* slot) {
+  return DrawStatsOut{st.template at<int32_t>(slot[0]), st.template at<double>(slot[1]), st.template at<double>(slot[2]),
+                      st.template at<int32_t>(slot[3]), st.template at<double>(slot[4]), st.template at<int32_t>(slot[5]),
+                      st.template at<double>(slot[6]),  st.template at<double>(slot[7]), st.template at<int32_t>(slot[8])};
+}
+template <class Stage>
+static EnvSpreadOut envelope_dev_spread(const Stage& st, const int* slot) {
+  return EnvSpreadOut{st.template at<double>(slot[9]), st.template at<double>(slot[10]), st.template at<int32_t>(slot[11])};
+}
+
+extern "C" int32_t mpct_envelope(const double* y, const double* u, const int32_t* alive, int64_t C, int32_t D, int32_t my,
+                                 int32_t nu, int32_t nit, int32_t t0, int32_t nlev, const double* levels, int32_t device,
+                                 const mpct_draw_stats_result* out_y, const mpct_draw_stats_result* out_u,
+                                 const mpct_envelope_spread* spread_y, const mpct_envelope_spread* spread_u) {
+  int rc = envelope_check(y, u, C, D, my, nu, nit, t0, nlev, levels, out_y, out_u, spread_y, spread_u);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage
+  CallStage cs{"mpct_envelope", "envelope staging", "trajectories", "envelopes"};
+  const mpct_draw_stats_result hy = out_y ? *out_y : mpct_draw_stats_result{}, hu = out_u ? *out_u : mpct_draw_stats_result{};
+  const mpct_envelope_spread py = spread_y ? *spread_y : mpct_envelope_spread{}, pu = spread_u ? *spread_u : mpct_envelope_spread{};
+  // a side without a result pointer is not uploaded
+  const size_t S = (size_t)C * D;
+  const int s_y = cs.in(stats_out(&hy).any() ? y : nullptr, S * my * nit * 8);
+  const int s_u = cs.in(stats_out(&hu).any() ? u : nullptr, S * nu * nit * 8), s_alive = cs.in(alive, S * 4);
+  int sy[12], su[12];
+  auto want = [&](void* host, size_t bytes) { return cs.out(host, bytes); };
+  envelope_slots(want, hy, py, (size_t)C, (size_t)my, (size_t)nit, (size_t)nlev, sy);
+  envelope_slots(want, hu, pu, (size_t)C, (size_t)nu, (size_t)nit, (size_t)nlev, su);
+  rc = cs.open(device);
+  if (rc == MPCT_OK)
+    rc = envelope_launch(cs.at<double>(s_y), cs.at<double>(s_u), cs.at<int32_t>(s_alive), C, D, my, nu, nit, t0, nlev, levels,
+                         envelope_dev_out(cs, sy), envelope_dev_out(cs, su), envelope_dev_spread(cs, sy),
+                         envelope_dev_spread(cs, su), cs.st);
+  return cs.close(rc);
+}
+
+// the argument checks of the two scoring entries, in the header's order; nothing here touches a device
+static int check_robust_envelope(mpct_scenario* s, const Batch& b, double j_bound, const mpct_opts* opts, int32_t t0,
+                                 int32_t nlev, const double* levels, const mpct_robust_result* base,
+                                 const mpct_draw_stats_result* out_y, const mpct_draw_stats_result* out_u,
+                                 const mpct_envelope_spread* spread_y, const mpct_envelope_spread* spread_u) {
+  if (!s) return fail(MPCT_EINVAL, "null scenario");
+  if (opts && opts->open_loop) return fail(MPCT_EINVAL, "the envelope entries are closed-loop only: open_loop must be 0");
+  if (b.nref < 1) return fail(MPCT_EINVAL, "nref < 1: the statistics need at least one draw");
+  if (!(j_bound >= 0.0)) return fail(MPCT_EINVAL, "j_bound must be >= 0 (0 = 1e100, +inf allowed), not negative or NaN");
+  int rc = envelope_check_out(s->nit, t0, nlev, levels, base, out_y, out_u, spread_y, spread_u);
+  if (rc) return rc;
+  const mpct_result any{};
+  rc = check_args(s, b, opts, &any);
+  if (rc) return rc;
+  return envelope_check_range(b.C, b.nref, s->my, s->nu, s->nit, nlev);
+}
+
+// enqueue one batch with device pointers on `stream`: the walk of the robust index entries, whose record is the
+// chunk's trajectories themselves
+static int launch_robust_envelope(mpct_scenario* s, DevCtx* cx, const Batch& b, double j_bound, const mpct_opts* opts,
+                                  int32_t t0, int32_t nlev, const double* levels, const RobustOut& base,
+                                  const DrawStatsOut& oy, const DrawStatsOut& ou, const EnvSpreadOut& sy, const EnvSpreadOut& su,
+                                  hipStream_t stream) {
+  const int my = s->my, nu = s->nu, nit = s->nit;
+  return walk_draw_chunks(
+      s, cx, b, j_bound, opts, base, stream, [](size_t) { return (size_t)0; },
+      [](char*, const double*, const double*, int64_t) { return (int)MPCT_OK; },
+      [&](char*, const double* y, const double* u, const int32_t* alive, int64_t c0, int64_t n) {
+        return (int)envelope_launch(y, u, alive, n, b.nref, my, nu, nit, t0, nlev, levels, oy.from(c0, my * nit, nlev),
+                                    ou.from(c0, nu * nit, nlev), sy.from(c0 * my), su.from(c0 * nu), stream);
+      });
+}
+
+extern "C" int32_t mpct_eval_robust_envelope_device(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                                    const double* delta, const double* lambda, int32_t nref,
+                                                    const double* r, const double* v, double j_bound, const mpct_opts* opts,
+                                                    int32_t t0, int32_t nlev, const double* levels, mpct_robust_result* base,
+                                                    const mpct_draw_stats_result* out_y, const mpct_draw_stats_result* out_u,
+                                                    const mpct_envelope_spread* spread_y,
+                                                    const mpct_envelope_spread* spread_u, void* stream) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_robust_envelope(s, b, j_bound, opts, t0, nlev, levels, base, out_y, out_u, spread_y, spread_u);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to enqueue, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  const RobustOut ro = base ? RobustOut{base->mean, base->worst, base->n_failed, base->worst_draw, base->status} : RobustOut{};
+  return launch_robust_envelope(s, cx, b, j_bound, opts, t0, nlev, levels, ro, out_y ? stats_out(out_y) : DrawStatsOut{},
+                                out_u ? stats_out(out_u) : DrawStatsOut{}, spread_out(spread_y), spread_out(spread_u),
+                                static_cast<hipStream_t>(stream));
+}
+
+extern "C" int32_t mpct_eval_robust_envelope(mpct_scenario* s, int64_t C, const int32_t* N2, const int32_t* Nu,
+                                             const double* delta, const double* lambda, int32_t nref, const double* r,
+                                             const double* v, double j_bound, const mpct_opts* opts, int32_t t0, int32_t nlev,
+                                             const double* levels, mpct_robust_result* base,
+                                             const mpct_draw_stats_result* out_y, const mpct_draw_stats_result* out_u,
+                                             const mpct_envelope_spread* spread_y, const mpct_envelope_spread* spread_u) {
+  const Batch b{C, N2, Nu, delta, lambda, nref, r, v};
+  int rc = check_robust_envelope(s, b, j_bound, opts, t0, nlev, levels, base, out_y, out_u, spread_y, spread_u);
+  if (rc) return rc;
+  if (C == 0) return MPCT_OK;  // nothing to stage, no device needed
+  DevCtx* cx = nullptr;
+  rc = ctx_for(s, opts, &cx);
+  if (rc) return rc;
+  // host buffers in, the records out on the context's own stream, staged as robust_stats_host does: every
+  // field lives on the device only where it is asked for
+  const size_t Cn = (size_t)C, cm = Cn * s->my * 8;
+  const mpct_robust_result hb = base ? *base : mpct_robust_result{};
+  const mpct_draw_stats_result hy = out_y ? *out_y : mpct_draw_stats_result{}, hu = out_u ? *out_u : mpct_draw_stats_result{};
+  const mpct_envelope_spread py = spread_y ? *spread_y : mpct_envelope_spread{}, pu = spread_u ? *spread_u : mpct_envelope_spread{};
+  HostStage hs(s, cx, C);
+  const int s_mean = hs.want(hb.mean, cm), s_worst = hs.want(hb.worst, cm), s_nf = hs.want(hb.n_failed, Cn * 4),
+            s_wd = hs.want(hb.worst_draw, Cn * 4), s_st = hs.want(hb.status, Cn * 4);
+  int sy[12], su[12];
+  auto want = [&](void* host, size_t bytes) { return hs.want(host, bytes); };
+  envelope_slots(want, hy, py, Cn, (size_t)s->my, (size_t)s->nit, (size_t)nlev, sy);
+  envelope_slots(want, hu, pu, Cn, (size_t)s->nu, (size_t)s->nit, (size_t)nlev, su);
+  rc = hs.upload(s, b);
+  if (rc) return rc;
+  const RobustOut ro{hs.at<double>(s_mean), hs.at<double>(s_worst), hs.at<int32_t>(s_nf), hs.at<int32_t>(s_wd),
+                     hs.at<int32_t>(s_st)};
+  rc = launch_robust_envelope(s, cx, hs.dev, j_bound, opts, t0, nlev, levels, ro, envelope_dev_out(hs, sy),
+                              envelope_dev_out(hs, su), envelope_dev_spread(hs, sy), envelope_dev_spread(hs, su), hs.st);
+  if (rc) return hs.abandon(rc);
+  return hs.finish();
 }
 
 static int32_t copy_name(const std::string& nm, char* buf, int32_t cap) {

@@ -185,6 +185,10 @@ class MpctDrawStats(C.Structure):
     _fields_ = [(n, c_int32_p if i else c_double_p) for n, i, _ in STATS_FIELDS]
 
 
+class MpctEnvelopeSpread(C.Structure):
+    _fields_ = [("spread", c_double_p), ("spread_max", c_double_p), ("t_spread_max", c_int32_p)]
+
+
 EXPORTS = [
     "mpct_abi_version", "mpct_last_error", "mpct_scenario_create", "mpct_scenario_destroy",
     "mpct_scenario_table", "mpct_eval_batch", "mpct_eval_batch_device", "mpct_lds_bytes", "mpct_lds_bytes_opts",
@@ -203,6 +207,7 @@ EXPORTS = [
     "mpct_osc_indices_device", "mpct_osc_indices", "mpct_eval_osc_indices", "mpct_eval_osc_indices_device",
     "mpct_eval_robust_osc_indices", "mpct_eval_robust_osc_indices_device",
     "mpct_goal_attain_device", "mpct_goal_attain",
+    "mpct_envelope_device", "mpct_envelope", "mpct_eval_robust_envelope", "mpct_eval_robust_envelope_device",
 ]
 
 ABI_VERSION = 7
@@ -216,6 +221,7 @@ INDEX_MAX_ROWS, INDEX_SCRATCH_BYTES = 2147483647, 268435456
 LIMIT_MAX_CH = 32
 SEG_MAX = 16
 STAT_F64, STAT_I32 = 0, 1
+ENVELOPE_DLANE, ENVELOPE_LANE_MAX_DRAWS = 48, 227   # kEnvDefaultDlane, kEnvLaneMaxDraws (csrc/envelope.h)
 ST_QP_MAXITER, ST_QP_INFEAS, ST_NONFINITE, ST_SKIPPED, ST_BADHORIZON = 1, 2, 4, 8, 16
 ST_SQP_MAXITER, ST_BOUNDS, ST_NOT_RUN = 32, 64, 128
 NMPC_VANDEVUSSE = 1
@@ -426,6 +432,24 @@ def load():
     # the largest grid of draw_stats_kernel in workgroups (0: the default): a test hook
     lib.mpct_internal_draw_stats_grid.argtypes = [C.c_int32]
     lib.mpct_internal_draw_stats_grid.restype = C.c_int32
+    env_out = [C.POINTER(MpctDrawStats), C.POINTER(MpctDrawStats), C.POINTER(MpctEnvelopeSpread), C.POINTER(MpctEnvelopeSpread)]
+    env_args = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                C.c_int32, c_double_p]
+    lib.mpct_envelope_device.argtypes = env_args + env_out + [C.c_void_p]
+    lib.mpct_envelope_device.restype = C.c_int32
+    lib.mpct_envelope.argtypes = env_args + [C.c_int32] + env_out
+    lib.mpct_envelope.restype = C.c_int32
+    robust_env_args = robust_args[:11] + [C.c_int32, C.c_int32, c_double_p, C.POINTER(MpctRobustResult)] + env_out
+    lib.mpct_eval_robust_envelope.argtypes = robust_env_args
+    lib.mpct_eval_robust_envelope.restype = C.c_int32
+    lib.mpct_eval_robust_envelope_device.argtypes = robust_env_args + [C.c_void_p]
+    lib.mpct_eval_robust_envelope_device.restype = C.c_int32
+    # the largest grid of draw_envelope_kernel in workgroups (0: the default), and the draws up to which the levels
+    # of an envelope run on that kernel (0: the default; above it draw_stats_kernel takes the table): test hooks
+    lib.mpct_internal_envelope_grid.argtypes = [C.c_int32]
+    lib.mpct_internal_envelope_grid.restype = C.c_int32
+    lib.mpct_internal_envelope_dlane.argtypes = [C.c_int32]
+    lib.mpct_internal_envelope_dlane.restype = C.c_int32
     if lib.mpct_abi_version() != ABI_VERSION:
         raise ImportError("libmpct ABI version mismatch")
     _lib = lib

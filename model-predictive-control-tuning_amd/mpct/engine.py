@@ -33,6 +33,10 @@
   eval_segment_indices_device  mpct_eval_segment_indices_device (torch CUDA tensors, enqueued on a stream)
   eval_robust_segment_indices  mpct_eval_robust_segment_indices: their statistics over the plant draws
   eval_robust_segment_indices_device  mpct_eval_robust_segment_indices_device (torch CUDA tensors, enqueued on a stream)
+  envelope            mpct_envelope: per-sample statistics of stored trajectories over the draws, and the band's spread
+  envelope_device     mpct_envelope_device (torch CUDA tensors, enqueued on the current stream)
+  eval_robust_envelope  mpct_eval_robust_envelope: score C x D closed loops and return their envelopes
+  eval_robust_envelope_device  mpct_eval_robust_envelope_device (torch CUDA tensors, enqueued on a stream)
 
 No CPU fallback: every numerical result comes from the HIP kernel.
 """
@@ -1416,6 +1420,200 @@ def eval_robust_indices_device(sc, N2, Nu, delta, lam, refs, out: dict, base: di
         nlev, _dp(lv) if nlev else None, C.byref(br), C.byref(so), C.c_void_p(stream.cuda_stream))
     if rc != 0:
         raise MpctError("mpct_eval_robust_indices_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+# --------------------------------------------------------------------------------------------
+# trajectory envelopes over the plant draws (mpct_envelope, mpct_eval_robust_envelope; include/mpct.h)
+SPREAD_FIELDS = (("spread", False), ("spread_max", False), ("t_spread_max", True))   # (name, integer?)
+
+
+@dataclass
+class EnvelopeResult:
+    """Per candidate, row and sample, the statistics of the trajectories over the surviving plant draws.  ``y`` and
+    ``u`` are dicts of the fields of DrawStats, each (C, rows, nit) or, per level, (C, rows, nit, nlev); None for
+    a side that was not asked for.  ``spread`` maps 'y' / 'u' to a dict of spread, spread_max and t_spread_max, each
+    (C, rows), over the samples t0 .. nit-1.  ``base`` is the RobustResult of the same launch
+    (eval_robust_envelope), None for stored trajectories."""
+    y: dict | None
+    u: dict | None
+    spread: dict
+    t0: int = 0
+    levels: np.ndarray | None = None
+    base: RobustResult | None = None
+
+    def costs(self, names=("spread",), sides=("y", "u"), max_failed: int | None = None) -> np.ndarray:
+        """(C, k) cost table for ``pareto``: for each of ``names`` ('spread', 'spread_max', 't_spread_max') the rows
+        of each side in ``sides`` that this result holds, side by side.  With a ``base`` and ``max_failed``, NaN
+        for every candidate with more failed draws, as RobustResult.scores masks."""
+        cols = []
+        for nm in names:
+            if nm not in [f for f, _ in SPREAD_FIELDS]:
+                raise ValueError("names take 'spread', 'spread_max' or 't_spread_max'")
+            for sd in sides:
+                if sd in self.spread:
+                    cols.append(np.asarray(self.spread[sd][nm], dtype=float))
+        if not cols:
+            raise ValueError("this result has no spread on the sides asked for")
+        out = np.array(np.hstack(cols), dtype=float, copy=True)
+        if max_failed is not None and self.base is not None:
+            out[np.asarray(self.base.n_failed) > int(max_failed)] = np.nan
+        return out
+
+    def band(self, c: int, row: int, level_lo=None, level_hi=None, side: str = "y"):
+        """The two lines to plot for candidate ``c`` and ``row`` of ``side``, each (nit,): the quantile lines at
+        ``level_lo`` and ``level_hi`` (values of ``levels``), lo / hi where a level is None."""
+        rec = self.y if side == "y" else self.u
+        if rec is None:
+            raise ValueError("this result has no side %r" % (side,))
+
+        def line(level, edge):
+            if level is None:
+                return rec[edge][c, row]
+            hit = np.flatnonzero(self.levels == float(level)) if self.levels is not None else ()
+            if not len(hit):
+                raise ValueError("level %r is not one of this result's levels" % (level,))
+            return rec["quantile"][c, row, :, hit[0]]
+
+        return line(level_lo, "lo"), line(level_hi, "hi")
+
+
+def _envelope_side(Cn, rows, nit, nlev):
+    """One side's record arrays, shaped (C, rows, nit[, nlev]), its spread arrays (C, rows) and the two structs that
+    point into them."""
+    arr, r = _stats_arrays(Cn, rows * nit, nlev)
+    arr = {k: a.reshape((Cn, rows, nit, nlev) if a.ndim == 3 else (Cn, rows, nit)) for k, a in arr.items() if a is not None}
+    sp = {n: np.zeros((Cn, rows), dtype=np.int32 if i else np.float64) for n, i in SPREAD_FIELDS}
+    s = _lib.MpctEnvelopeSpread(_dp(sp["spread"]), _dp(sp["spread_max"]), _ip(sp["t_spread_max"]))
+    return arr, r, sp, s
+
+
+def _envelope_structs(out: dict):
+    """The four structs of a device-pointer envelope call from ``out``: keys 'y' and 'u' (dicts of the tensors of
+    draw_stats_device) and 'spread_y' and 'spread_u' (dicts of spread, spread_max, t_spread_max tensors)."""
+    def sp(d):
+        return _lib.MpctEnvelopeSpread(_tptr(d.get("spread"), _lib.c_double_p), _tptr(d.get("spread_max"), _lib.c_double_p),
+                                       _tptr(d.get("t_spread_max"), _lib.c_int32_p))
+    return (_stats_struct(out.get("y") or {}), _stats_struct(out.get("u") or {}), sp(out.get("spread_y") or {}),
+            sp(out.get("spread_u") or {}))
+
+
+def envelope(y, u, alive=None, levels=None, t0=0, device=-1) -> EnvelopeResult:
+    """mpct_envelope: the envelopes over the draw axis of stored trajectories ``y`` (C, D, my, nit) and ``u``
+    (C, D, nu, nit), either may be None, reduced on the GPU (host arrays in and out).  ``alive`` (C, D): a zero
+    drops the draw from every sample of its candidate; a non-finite sample drops the draw from that sample.
+    ``levels`` (up to 8 values in (0, 1]) adds quantile, cvar and q_draw; the spread covers t0 .. nit-1."""
+    if y is None and u is None:
+        raise ValueError("y and u are both None")
+    ya = None if y is None else np.ascontiguousarray(y, dtype=np.float64)
+    ua = None if u is None else np.ascontiguousarray(u, dtype=np.float64)
+    ref = ya if ya is not None else ua
+    if any(a is not None and (a.ndim != 4 or a.shape[:2] != ref.shape[:2] or a.shape[3] != ref.shape[3]) for a in (ya, ua)):
+        raise ValueError("y must be (C, D, my, nit) and u (C, D, nu, nit)")
+    Cn, D, _, nit = ref.shape
+    al = None
+    if alive is not None:
+        al = np.ascontiguousarray(alive, dtype=np.int32)
+        if al.shape != (Cn, D):
+            raise ValueError("alive must be (C, D)")
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    my, nu = (0 if ya is None else ya.shape[2]), (0 if ua is None else ua.shape[2])
+    sides, structs = {}, []
+    for name, rows in (("y", my), ("u", nu)):
+        if rows:
+            sides[name] = _envelope_side(Cn, rows, nit, nlev)
+            structs += [C.byref(sides[name][1]), C.byref(sides[name][3])]
+        else:
+            structs += [None, None]
+    rc = _lib.load().mpct_envelope(ya.ctypes.data if my else None, ua.ctypes.data if nu else None,
+                                   al.ctypes.data if al is not None else None, Cn, D, my, nu, nit, int(t0), nlev,
+                                   _dp(lv) if nlev else None, int(device), structs[0], structs[2], structs[1], structs[3])
+    if rc != 0:
+        raise MpctError("mpct_envelope failed (%d): %s" % (rc, _lib.last_error()))
+    return EnvelopeResult(y=sides["y"][0] if "y" in sides else None, u=sides["u"][0] if "u" in sides else None,
+                          spread={k: v[2] for k, v in sides.items()}, t0=int(t0), levels=lv)
+
+
+def envelope_device(y, u, out: dict, alive=None, levels=None, t0=0):
+    """mpct_envelope_device: ``y`` [C, D, my, nit] and ``u`` [C, D, nu, nit] are contiguous float64 CUDA (HIP)
+    tensors (either may be None), ``alive`` an int32 tensor [C, D] or None; the records are written into the
+    tensors of ``out``: keys 'y' and 'u', dicts with the keys of draw_stats_device ([C, rows, nit] or
+    [C, rows, nit, nlev]), and 'spread_y' and 'spread_u', dicts of spread, spread_max (float64) and t_spread_max
+    (int32), each [C, rows]; any may be absent.  ``levels`` is a HOST sequence.  Enqueued on the current torch
+    stream of the tensors' device and not synchronised."""
+    import torch
+
+    ref = y if y is not None else u
+    for t in (y, u):
+        if t is not None and (t.dtype != torch.float64 or t.dim() != 4 or not t.is_contiguous() or
+                              tuple(t.shape[:2]) != tuple(ref.shape[:2]) or t.shape[3] != ref.shape[3]):
+            raise ValueError("y and u must be contiguous float64 tensors [C, D, rows, nit]")
+    if alive is not None and (alive.dtype != torch.int32 or tuple(alive.shape) != tuple(ref.shape[:2]) or
+                              not alive.is_contiguous()):
+        raise ValueError("alive must be a contiguous int32 tensor [C, D]")
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    oy, ou, sy, su = _envelope_structs(out)
+    stream = torch.cuda.current_stream(ref.device).cuda_stream
+    with torch.cuda.device(ref.device):
+        rc = _lib.load().mpct_envelope_device(
+            C.c_void_p(y.data_ptr()) if y is not None else None, C.c_void_p(u.data_ptr()) if u is not None else None,
+            C.c_void_p(alive.data_ptr()) if alive is not None else None, ref.shape[0], ref.shape[1],
+            y.shape[2] if y is not None else 0, u.shape[2] if u is not None else 0, ref.shape[3], int(t0), nlev,
+            _dp(lv) if nlev else None, C.byref(oy), C.byref(ou), C.byref(sy), C.byref(su), C.c_void_p(stream))
+    if rc != 0:
+        raise MpctError("mpct_envelope_device failed (%d): %s" % (rc, _lib.last_error()))
+
+
+def eval_robust_envelope(sc, N2, Nu, delta, lam, refs, v=None, levels=None, j_bound=0.0, t0=0, device=-1, max_qp_iter=0,
+                         feas_tol=0.0) -> EnvelopeResult:
+    """mpct_eval_robust_envelope: score C candidates over the D = len(refs) draws and reduce, on the device, the
+    trajectories of the C x D closed loops to their envelopes over the surviving draws (host arrays in and out).
+    A draw survives by eval_robust's rule (status 0, total J1 finite and <= ``j_bound``); ``levels`` adds
+    quantile, cvar and q_draw per sample; the spread covers t0 .. nit-1."""
+    N2, Nu, delta, lam, refs, Cn, D, vv = _batch_args(sc, N2, Nu, delta, lam, refs, v)
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    ay, ry, spy, sy = _envelope_side(Cn, sc.my, sc.nit, nlev)
+    au, ru, spu, su = _envelope_side(Cn, sc.nu, sc.nit, nlev)
+    base = RobustResult(mean=np.zeros((Cn, sc.my)), worst=np.zeros((Cn, sc.my)), n_failed=np.zeros(Cn, dtype=np.int32),
+                        worst_draw=np.zeros(Cn, dtype=np.int32), status=np.zeros(Cn, dtype=np.int32), draws=D)
+    br = _lib.MpctRobustResult()
+    br.mean, br.worst = _dp(base.mean), _dp(base.worst)
+    br.n_failed, br.worst_draw, br.status = _ip(base.n_failed), _ip(base.worst_draw), _ip(base.status)
+    o = _opts(False, False, device, max_qp_iter, feas_tol)
+    rc = sc.lib.mpct_eval_robust_envelope(sc.handle, Cn, N2.ctypes.data, Nu.ctypes.data, delta.ctypes.data, lam.ctypes.data,
+                                          D, refs.ctypes.data, vv.ctypes.data if vv is not None else None, float(j_bound),
+                                          C.byref(o), int(t0), nlev, _dp(lv) if nlev else None, C.byref(br), C.byref(ry),
+                                          C.byref(ru), C.byref(sy), C.byref(su))
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_envelope failed (%d): %s" % (rc, _lib.last_error()))
+    return EnvelopeResult(y=ay, u=au, spread={"y": spy, "u": spu}, t0=int(t0), levels=lv, base=base)
+
+
+def eval_robust_envelope_device(sc, N2, Nu, delta, lam, refs, out: dict, base: dict | None = None, v=None, levels=None,
+                                j_bound=0.0, t0=0, device=-1, stream=None):
+    """Device-pointer entry of eval_robust_envelope: every argument is a CUDA (HIP) torch tensor (``levels`` is a
+    HOST sequence); the envelopes are written into the tensors of ``out`` (the keys of envelope_device) and the
+    robust record of J1 into those of ``base`` (the keys of eval_robust_device without J1).  Enqueued on
+    ``stream`` (torch stream; default: current) and not synchronised."""
+    import torch
+
+    if stream is None:
+        stream = torch.cuda.current_stream()
+    lv = _levels(levels) if levels is not None else None
+    nlev = 0 if lv is None else lv.size
+    br = _robust_struct(base or {})
+    o = _opts(False, False, device)
+    oy, ou, sy, su = _envelope_structs(out)
+    rc = sc.lib.mpct_eval_robust_envelope_device(
+        sc.handle, N2.numel(), C.c_void_p(N2.data_ptr()), C.c_void_p(Nu.data_ptr()), C.c_void_p(delta.data_ptr()),
+        C.c_void_p(lam.data_ptr()), refs.shape[0], C.c_void_p(refs.data_ptr()),
+        C.c_void_p(v.data_ptr()) if v is not None else None, float(j_bound), C.byref(o), int(t0), nlev,
+        _dp(lv) if nlev else None, C.byref(br), C.byref(oy), C.byref(ou), C.byref(sy), C.byref(su),
+        C.c_void_p(stream.cuda_stream))
+    if rc != 0:
+        raise MpctError("mpct_eval_robust_envelope_device failed (%d): %s" % (rc, _lib.last_error()))
 
 
 # --------------------------------------------------------------------------------------------
